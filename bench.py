@@ -13,9 +13,13 @@ region.  metric = captions/sec = N * B * 5 / step_time  (the reference's "ex/sec
 
 Other workloads (same JSON contract):  --workload decode|sparse_decode|sparse_xe|scst  (+ --variant, see WORKLOADS)
 
-The default one-GPU run also times every other BASELINE config in the same process and carries them, compactly, in the line's
-`workloads` object (ms per step, captions/s, roofline fraction, dominant kernel, CPU baseline); the prose that used to ride on
-the line (parity evidence, kernel descriptions, how the traffic figures are read) lives in profiles/bench_notes.json.
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step
+and the configuration); nothing else.  --dump-outputs DIR then also writes what the last timed step computed as DIR/<name>.npy.
+
+--full adds what the headline does not need: the `roofline` of the dominant kernels (HIP events in extra, untimed steps), the CPU
+baseline (unless --no-cpu-baseline) and, on one GPU, every other BASELINE config timed in the same process, carried compactly in
+the line's `workloads` object (unless --no-extra-workloads); the prose that used to ride on the line (parity evidence, kernel
+descriptions, how the traffic figures are read) lives in profiles/bench_notes.json.
 """
 import argparse
 import ctypes as C
@@ -280,10 +284,42 @@ WORKLOADS = {
 GFLOP_FWD_ENC, GFLOP_FWD_DEC = 1.680, 4.674
 GFLOP_DECODE_PER_IMAGE = 6.62       # beam-5 decode, dense (encoder 1.46 + 5 rows x 18 steps x 54.28 MFLOP + attention)
 
+# --dump-outputs: the names of what one step returns, per kind of step, and the size of the seeded sample of the parameter arena
+# (2 Mi positions: their index, the parameter and its running gradient average, 32 MiB in all)
+STEP_OUTPUTS = {"decode": ("seq", "logprobs"), "scst": ("loss", "reward", "seq", "greedy"), "xe": ("loss",)}
+DUMP_PARAMS = 1 << 21
 
-def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, precision=None):
-    """Build the model and the synthetic batch of one workload, time `steps` steps after `warmup` (barrier + synchronize on both
-    sides, MAX over ranks) and measure the roofline of its dominant kernel with HIP events in extra, untimed steps.
+
+def param_sample(model):
+    """Fixed, seeded positions of the trained parameter arena (the same for every run of the same workload)."""
+    n = model._n_train
+    idx = np.unique(np.random.RandomState(20240601).randint(0, n, size=min(n, DUMP_PARAMS)))
+    return torch.from_numpy(idx).to(model._flat.device)
+
+
+def dump_outputs(path, kind, last, model, tr):
+    """Write what the last timed step computed as <path>/<name>.npy: floating outputs as float32, tokens as float64; for a training
+    step (trainer `tr`) also the sampled parameters after it and Adam's first moment there, the running average of the step's
+    gradients.  (Not the parameters' change over the run: Adam moves a weight whose gradient is at rounding level by the full
+    learning rate in a direction that the order of the step's sums decides.)"""
+    os.makedirs(path, exist_ok=True)
+    outs = last if isinstance(last, (tuple, list)) else (last,)
+    arrays = dict(zip(STEP_OUTPUTS[kind], outs))
+    if tr is not None:
+        idx = param_sample(model)
+        arrays.update(param_index=idx, params=model._flat[idx], grad_avg=tr.m[idx])
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach().cpu()
+        t = t.float() if t.is_floating_point() else t.double()
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
+def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, precision=None, full=True, dump=None):
+    """Build the model and the synthetic batch of one workload and time `steps` steps after `warmup` (barrier + synchronize on both
+    sides, MAX over ranks).  `dump`: a directory for what the last timed step computed (rank 0).  `full`: then also measure the
+    roofline of its dominant kernel with HIP events in extra, untimed steps.
     `variant`: "" | "kernels" (sparse_xe: sparse products) | "dense_kernels" (sparse_decode: zero-filled dense weights) | "nodrop"
     (scst) | "fp32" (decode) | a "988" prefix (98.8 % instead of 95 % zeros)."""
     from sparse_image_captioning_amd.utils.config import ort_config
@@ -335,9 +371,10 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
             opt["decode_streams"] = args.decode_streams
 
         def step():
-            model(att_feats=batch["att_feats"], boxes=batch["boxes"], att_masks=batch["att_masks"], opt=opt, mode="sample",
-                  att_max_len=batch["att_max_len"])
+            return model(att_feats=batch["att_feats"], boxes=batch["boxes"], att_masks=batch["att_masks"], opt=opt, mode="sample",
+                         att_max_len=batch["att_max_len"])
         units_per_step = B
+        tr = None
     elif workload == "scst":
         model.train()
         tr = NativeTrainer(model, noamopt_factor=1.0, noamopt_warmup=20000)
@@ -348,9 +385,10 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
         lens = []
 
         def step():
-            _, _, seq_, _ = tr.scst_step(batch, lambda seq, greedy: rw, num_samples=5, baseline="greedy", sample_dropout=sample_dropout)
+            res = tr.scst_step(batch, lambda seq, greedy: rw, num_samples=5, baseline="greedy", sample_dropout=sample_dropout)
             if variant == "hostreward" and len(lens) < 4:
-                lens.append(float((seq_ != 0).sum(-1).float().mean()))
+                lens.append(float((res[2] != 0).sum(-1).float().mean()))
+            return res
         units_per_step = B * 5
     else:
         model.train()
@@ -361,7 +399,7 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
         tr.valid_positions = not args.padded_positions
 
         def step():
-            tr.xe_step(batch)
+            return tr.xe_step(batch)
         units_per_step = B * spi
 
     def barrier():
@@ -374,7 +412,7 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        last = step()
     barrier()
     elapsed = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
     if world > 1:
@@ -382,6 +420,16 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
     elapsed = elapsed.item()
     ms_per_step = elapsed / steps * 1e3
     value = world * units_per_step / (elapsed / steps)
+    wname = workload + ("_" + variant if variant else "")
+    out = {"metric": "captions/sec", "value": round(value, 1), "unit": "captions/sec", "n_gpus": world, "steps": steps,
+           "warmup": warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+           "vs_baseline": None, "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
+           "config": {"workload": WORKLOADS[wname], "images_per_gpu": B, "regions": S, "captions_per_image": spi,
+                      "parallelism": (f"dp{world}" + ("+bf16-allreduce" if args.allreduce_dtype == "bf16" else "")) if world > 1 else "single"}}
+    if dump and rank == 0:
+        dump_outputs(dump, "decode" if decode else "scst" if workload == "scst" else "xe", last, model, tr)
+    if not full:
+        return out if rank == 0 else None
 
     # ---- roofline of the dominant kernel, measured live with HIP events around every launch of extra (untimed) steps on the
     # launch stream: once in the TIMED schedule (ortk_prof_enable(2): side stream on, the figure `achieved` reports) and once
@@ -504,15 +552,9 @@ def run_workload(args, workload, variant, steps, warmup, rank, world, dev, pkg, 
         roofline["whole_step"] = {"executed_tflop": round(exe, 3), "tflops": round(exe / (ms_per_step * 1e-3), 1),
                                   "frac": round(exe / (ms_per_step * 1e-3) / peak, 4),
                                   "padded_equivalent_tflop": round(GFLOP_FWD_PER_IMAGE * 3 * B / 1e3, 3)}
-    wname = workload + ("_" + variant if variant else "")
     if workload == "scst" and variant == "hostreward" and lens:
         roofline["mean_sampled_length"] = round(sum(lens) / len(lens), 2)
-    out = {"metric": "captions/sec", "value": round(value, 1), "unit": "captions/sec", "n_gpus": world, "steps": steps,
-           "warmup": warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
-           "vs_baseline": None, "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
-           "config": {"workload": WORKLOADS[wname], "images_per_gpu": B, "regions": S, "captions_per_image": spi,
-                      "parallelism": (f"dp{world}" + ("+bf16-allreduce" if args.allreduce_dtype == "bf16" else "")) if world > 1 else "single"},
-           "roofline": roofline}
+    out["roofline"] = roofline
     del model
     torch.cuda.empty_cache()
     return out
@@ -568,14 +610,22 @@ def main():
     ap.add_argument("--scst-eos-bias", type=float, default=5.4,
                     help="scst --variant hostreward: EOS logit bias on the x3-scaled random-init generator (5.4: sampled captions of ~13 of 18 "
                          "positions, the length of the XE workload's synthetic captions; the line reports the mean sampled length)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: `roofline` (extra, untimed steps), the CPU baseline and, on one GPU, "
+                         "the `workloads` object (every other BASELINE config timed in this process)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; for a training step "
+                         "also a fixed, seeded sample of the parameters and of Adam's running gradient average)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no cpu_baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=CPU_THREADS, help="threads of the cpu_baseline leg (default: the fastest of the committed sweep)")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="default run on one GPU: do not add the `workloads` object (BASELINE configs[2], [3], [4] timed in this process)")
+                    help="--full on one GPU: do not add the `workloads` object (BASELINE configs[2], [3], [4] timed in this process)")
     ap.add_argument("--selftest", action="store_true",
                     help="launcher check without a GPU: the ranks form a gloo group, all-reduce their rank ids and rank 0 "
                          "prints one JSON line (tests/test_dist_cpu.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     globals()["CPU_THREADS"] = max(1, args.cpu_threads)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -604,8 +654,9 @@ def main():
         "dense_kernels" if (args.workload == "sparse_decode" and args.dense_kernels) else ""))
     if args.workload + ("_" + variant if variant else "") not in WORKLOADS:
         sys.exit(f"bench.py: no workload {args.workload} --variant {variant}")
-    out = run_workload(args, args.workload, variant, args.steps, args.warmup, rank, world, dev, pkg)
-    if rank == 0:
+    out = run_workload(args, args.workload, variant, args.steps, args.warmup, rank, world, dev, pkg, full=args.full,
+                       dump=args.dump_outputs)
+    if rank == 0 and args.full:
         out["notes"] = NOTES
         from sparse_image_captioning_amd.utils.config import ORT_DEFAULTS
         base = {}
@@ -616,7 +667,7 @@ def main():
             if kind not in base:
                 base[kind] = cpu_baseline(kind, dict(ORT_DEFAULTS))
             return base[kind]
-        # The other BASELINE configs, timed in this same process with the same contract (fewer steps: the whole default run
+        # The other BASELINE configs, timed in this same process with the same contract (fewer steps: the whole --full run
         # stays within a couple of minutes).  One GPU only: the driver's scaling runs measure the headline.
         if args.workload == "xe" and not variant and world == 1 and not args.no_extra_workloads and not args.batch:
             extra, cpu_kinds = {}, {}
@@ -638,6 +689,7 @@ def main():
             if cpu_kinds:
                 out["cpu_baselines"] = cpu_kinds       # the oracle on the host cores for the decode / scst workloads (the xe figure: `cpu_baseline`)
         out["cpu_baseline"] = cpu("decode" if "decode" in args.workload else "scst" if args.workload == "scst" else "xe")
+    if rank == 0:
         print(json.dumps(out, separators=(",", ":")), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -4,7 +4,7 @@
 # Separate --pmc run with --kernel-trace only.
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r06; mkdir -p $O
-B="python3 bench.py --no-extra-workloads --no-cpu-baseline --steps 2 --warmup 1"
+B="python3 bench.py --full --no-extra-workloads --no-cpu-baseline --steps 2 --warmup 1"
 for w in xe scst decode; do
   extra=""; [ $w != xe ] && extra="--workload $w"
   rocprofv3 --kernel-trace --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES --output-format csv -d $O/raw_ic_$w -o t -- $B $extra > $O/icache_$w.log 2>&1

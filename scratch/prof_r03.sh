@@ -3,7 +3,7 @@
 # PMC passes are separate runs with --kernel-trace only (never combined with other trace domains).
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r03; mkdir -p $O
-B="python3 bench.py --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
+B="python3 bench.py --full --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
 stats() {   # name, extra args
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$1 -o t -- $B $2 > $O/$1.log 2>&1
   cp $O/raw_$1/t_kernel_stats.csv $O/r03_$1_kernel_stats.csv
@@ -29,5 +29,5 @@ pmc sparse_decode_stack_pmc_sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_AC
 pmc sparse_decode_stack_pmc_insts SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_INSTS_VMEM SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_MFMA -- --workload sparse_decode
 pmc decode_stack_pmc_sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES -- --workload decode
 rm -rf $O/raw_*
-python3 bench.py --steps 50 --warmup 10 > $O/r03_default_bench_line.json 2> $O/bench.err
+python3 bench.py --full --steps 50 --warmup 10 > $O/r03_default_bench_line.json 2> $O/bench.err
 ls -la $O | head -40

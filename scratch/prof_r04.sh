@@ -3,7 +3,7 @@
 # PMC passes are separate runs with --kernel-trace only (never combined with other trace domains).
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r04; mkdir -p $O
-B="python3 bench.py --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
+B="python3 bench.py --full --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
 stats() {   # name, extra args
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$1 -o t -- $B $2 > $O/$1.log 2>&1
   cp $O/raw_$1/t_kernel_stats.csv $O/r04_$1_kernel_stats.csv
@@ -28,6 +28,6 @@ pmc sparse_decode_stack_pmc_fetch_size FETCH_SIZE -- --workload sparse_decode
 pmc sparse_decode_stack_pmc_write_size WRITE_SIZE -- --workload sparse_decode
 pmc scst_pmc_sq SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS -- --workload scst
 rm -rf $O/raw_*
-python3 bench.py --steps 50 --warmup 10 > $O/r04_default_bench_line.json 2> $O/bench.err
+python3 bench.py --full --steps 50 --warmup 10 > $O/r04_default_bench_line.json 2> $O/bench.err
 wc -c $O/r04_default_bench_line.json; tail -2 $O/bench.err
 ls $O | head -40

@@ -7,7 +7,7 @@
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r05; mkdir -p $O
 MD5=$(md5sum sparse-image-captioning_amd/libortk.so | cut -d' ' -f1)
-B="python3 bench.py --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
+B="python3 bench.py --full --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
 stats() {   # name, extra args
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$1 -o t -- $B $2 > $O/$1.log 2>&1
   cp $O/raw_$1/t_kernel_stats.csv $O/r05_$1_kernel_stats.csv
@@ -46,6 +46,6 @@ json.dump({"lib_md5": "$MD5", "git_head": "${GIT_HEAD:-unknown}", "collected_utc
           open("$O/r05_manifest.json", "w"), indent=1)
 PY
 cp $O/r05_manifest.json profiles/r05_manifest.json; cp $O/r05_*_pmc_*.csv profiles/     # (on the box: the bench line below reads them)
-python3 bench.py --steps 50 --warmup 10 > $O/r05_default_bench_line.json 2> $O/bench.err
+python3 bench.py --full --steps 50 --warmup 10 > $O/r05_default_bench_line.json 2> $O/bench.err
 wc -c $O/r05_default_bench_line.json; tail -2 $O/bench.err
 ls $O | head -40

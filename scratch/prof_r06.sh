@@ -10,7 +10,7 @@
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r06; mkdir -p $O
 MD5=$(md5sum sparse-image-captioning_amd/libortk.so | cut -d' ' -f1)
-B="python3 bench.py --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
+B="python3 bench.py --full --no-extra-workloads --no-cpu-baseline --steps 3 --warmup 1"
 stats() {   # name, extra args
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/raw_$1 -o t -- $B $2 > $O/$1.log 2>&1
   cp $O/raw_$1/t_kernel_stats.csv $O/r06_$1_kernel_stats.csv
@@ -54,7 +54,7 @@ if [ "$PART" = sweep ]; then     # (its own call: the 128- and 256-thread settin
 python3 scratch/cpu_thread_sweep.py > $O/r06_cpu_thread_sweep.txt 2>&1
 fi
 if [ "$PART" = final ]; then
-python3 bench.py --steps 50 --warmup 10 > $O/r06_default_bench_line.json 2> $O/bench.err
+python3 bench.py --full --steps 50 --warmup 10 > $O/r06_default_bench_line.json 2> $O/bench.err
 wc -c $O/r06_default_bench_line.json; tail -2 $O/bench.err
 # the round's A/B and kernel-alone figures cited from DESIGN.md / the sources, from this library
 python3 scratch/wgrad_group_ab.py > $O/r06_wgrad_group_ab.txt 2>&1

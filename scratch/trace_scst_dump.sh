@@ -3,7 +3,7 @@
 TAG=${1:-trace_scst}; shift || true
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python3 $R/bench.py --workload scst --steps 5 --warmup 2 --no-cpu-baseline --no-extra-workloads "$@" > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o t -- python3 $R/bench.py --full --workload scst --steps 5 --warmup 2 --no-cpu-baseline --no-extra-workloads "$@" > $O/trace.log 2>&1
 cp $O/trace/t_kernel_stats.csv $O/kernel_stats.csv
 f=$(find $O/trace -name "*kernel_trace.csv" | head -1)
 python3 - <<PY

@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -55,8 +56,13 @@ def golden():
     cache = {}
 
     def load(name):
+        # a fixture above 1 MiB is stored as <name>.npz + <name>.part2.npz ... (tests/golden/common.py: save_golden)
         if name not in cache:
-            cache[name] = dict(np.load(os.path.join(GOLDEN_DIR, name + ".npz"), allow_pickle=False))
+            stem = os.path.join(GOLDEN_DIR, name)
+            parts = sorted(glob.glob(glob.escape(stem) + ".part*.npz"), key=lambda p: int(p[len(stem) + 5:-4]))
+            cache[name] = {}
+            for p in [stem + ".npz"] + parts:
+                cache[name].update(np.load(p, allow_pickle=False))
         return cache[name]
 
     return load

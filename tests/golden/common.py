@@ -152,3 +152,31 @@ def make_collate_fixture(root, seed=4242, n_img=5, feat=16):
         caps = [" ".join(rs.choice(COLLATE_WORDS, size=int(rs.randint(3, 25)))) for _ in range(ncap)]
         items.append((f"/images/{100 + i}.jpg", 100 + i, caps[0], caps, [c.split() for c in caps]))
     return items
+
+
+FIXTURE_MAX_BYTES = 1 << 20          # no committed file above 1 MiB
+
+
+def save_golden(path, arrays, budget=FIXTURE_MAX_BYTES - (64 << 10)):
+    """np.savez_compressed of ``arrays`` to ``<stem>.npz``, spilling keys over to ``<stem>.part2.npz``, ``.part3`` ... so that every
+    file stays below FIXTURE_MAX_BYTES; the `golden` fixture of tests/conftest.py merges the parts (keys in their original order)."""
+    import glob
+    import os
+    stem = path[:-4] if path.endswith(".npz") else path
+    for old in glob.glob(glob.escape(stem) + ".part*.npz"):
+        os.remove(old)
+    parts, cur, used = [], {}, 0
+    for k, v in arrays.items():
+        a = np.asarray(v)
+        est = len(zlib.compress(a.tobytes(), 6)) + 256      # deflate, as savez_compressed writes it, + the member's headers
+        if cur and used + est > budget:
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = a
+        used += est
+    parts.append(cur)
+    for i, part in enumerate(parts):
+        out = stem + (".npz" if i == 0 else f".part{i + 1}.npz")
+        np.savez_compressed(out, **part)
+        if os.path.getsize(out) >= FIXTURE_MAX_BYTES:
+            raise ValueError(f"{out}: {os.path.getsize(out)} bytes, a single array too large for one fixture file")

@@ -290,7 +290,7 @@ def main():
         g3[f"{mtype}/logp_sum_abs"] = np.float64(logp.double().abs().sum().item())
         g3[f"{mtype}/logp_row0"] = logp[0, 0].numpy()
     g3["keep_prob"] = np.float32(KEEP)
-    np.savez_compressed(os.path.join(out_dir, "g3_tiny_prune.npz"), **g3)
+    C.save_golden(os.path.join(out_dir, "g3_tiny_prune.npz"), g3)
     print("g3: sparsity", g3["sparsity/total"], "loss", g3["sparsity_loss"])
 
     # ------------------------------------------------------------------ G2: full-size config-1 (outputs only)

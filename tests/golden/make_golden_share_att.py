@@ -46,7 +46,7 @@ def main():
                 g[f"{tag}/decode_b{bs}/seq"] = seq_o.numpy()
                 g[f"{tag}/decode_b{bs}/logprobs"] = lp_o.numpy()
         print("g9", tag, "loss", float(g[tag + "/xe_loss"]), "params", int(g[tag + "/n_params"]))
-    np.savez_compressed(os.path.join(HERE, "g9_tiny_share_att.npz"), **g)
+    C.save_golden(os.path.join(HERE, "g9_tiny_share_att.npz"), g)
 
 
 if __name__ == "__main__":

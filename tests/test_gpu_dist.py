@@ -70,19 +70,27 @@ def test_rccl_one_rank_group(tmp_path, kind):
 
 
 @pytest.mark.gpu
-def test_bench_under_torch_distributed_run_one_rank():
+def test_bench_under_torch_distributed_run_one_rank(tmp_path):
     """bench.py launched exactly as the driver launches its ranks (torch.distributed.run, one rank): it forms the RCCL group, runs the
-    overlapped XE step (asynchronous split all-reduce on RCCL's stream) and rank 0 prints the one JSON line."""
+    overlapped XE step (asynchronous split all-reduce on RCCL's stream) and rank 0 prints the one JSON line (--full: with the
+    roofline) and writes what the last timed step computed (--dump-outputs)."""
     import json
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     port = 29800 + (os.getpid() % 1000)
+    dump = os.path.join(str(tmp_path), "outputs")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--overlap-allreduce", "on", "--no-extra-workloads", "--no-cpu-baseline"]
+           "--overlap-allreduce", "on", "--full", "--no-extra-workloads", "--no-cpu-baseline", "--dump-outputs", dump]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout.decode()[-2000:]
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 1 and rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["roofline"]["frac"] > 0
+    out = {n[:-4]: np.load(os.path.join(dump, n)) for n in os.listdir(dump)}
+    assert sorted(out) == ["grad_avg", "loss", "param_index", "params"]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in out.values())
+    assert out["loss"].size == 1 and out["loss"].item() > 0
+    assert out["params"].shape == out["grad_avg"].shape == out["param_index"].shape
+    assert np.abs(out["grad_avg"]).max() > 0 and np.abs(out["params"]).max() > 0
