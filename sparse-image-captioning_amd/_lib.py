@@ -246,7 +246,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 2      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 3      # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -1,5 +1,6 @@
 // ortk_scorer.hip — SCST reward scorer on the HOST (no device code in this file; it is built into libortk.so with the
-// rest of the C-ABI): CIDEr-D and per-sentence BLEU-1..4 over integer n-grams, multi-threaded over items.
+// rest of the C-ABI): CIDEr-D and per-sentence BLEU-1..4 over integer n-grams, multi-threaded over items.  The second half
+// cooks the reference pack of the device scorer (ortk_scorer_dev.hip) and walks a pack on the host.
 //
 // Follows, operation for operation in double precision:
 //   precook / cook_refs / cook_test / counts2vec / sim / compute_cider   ciderD_scorer.py:18-214
@@ -13,7 +14,9 @@
 #include <thread>
 #include <unordered_map>
 #include <vector>
+#include <cstring>
 #include "../../include/ortk_scorer.h"
+#include "ortk_scorer_core.h"
 
 namespace {
 
@@ -215,6 +218,236 @@ extern "C" int ortk_scorer_score(const ortk_scorer* s, const int32_t* cap_tok, c
             if (ratio < 1.0) for (int k = 0; k < 4; ++k) out[k] *= std::exp(1.0 - 1.0 / ratio);
             for (int k = 0; k < 4; ++k) bleu_out[(int64_t)k * nitems + i] = out[k];
         });
+    }
+    return 0;
+}
+
+// =====================================================================================================================
+// Reference pack of the device scorer (format: ortk_scorer_core.h) and its host walk
+// =====================================================================================================================
+namespace {
+namespace sc = ortk_sc;
+
+int64_t df_table_bytes(size_t nkeys, uint64_t* nslots_out) {
+    uint64_t nslots = 0;
+    if (nkeys > 0) { nslots = 16; while (nslots < 2 * (uint64_t)nkeys) nslots <<= 1; }
+    if (nslots_out) *nslots_out = nslots;
+    return (int64_t)(sizeof(sc::DfHdr) + nslots * sizeof(sc::DfSlot));
+}
+
+// keys are inserted in ascending order, so the bytes of a table depend on its content only
+void df_table_write(std::vector<std::pair<uint64_t, double>>& kv, unsigned char* out) {
+    uint64_t nslots;
+    const int64_t bytes = df_table_bytes(kv.size(), &nslots);
+    std::memset(out, 0, (size_t)bytes);
+    sc::DfHdr* h = (sc::DfHdr*)out;
+    h->nslots = nslots; h->nkeys = kv.size();
+    sc::DfSlot* slot = (sc::DfSlot*)(out + sizeof(sc::DfHdr));
+    std::sort(kv.begin(), kv.end());
+    for (const auto& e : kv) {
+        uint64_t i = sc::df_hash(e.first, nslots - 1);
+        while (slot[i].key != 0) i = (i + 1) & (nslots - 1);
+        slot[i].key = e.first; slot[i].df = e.second;
+    }
+}
+
+}  // namespace
+
+extern "C" int ortk_scorer_pack_refs(const ortk_scorer* s, const int32_t* cap_tok, const int64_t* cap_off, const int64_t* img_ref_off,
+                                     int64_t n_images, int32_t items_per_image, void* pack_out, int64_t pack_bytes, void* df_out,
+                                     int64_t df_bytes, int64_t* need, double* ref_len_log_out) {
+    if (!s || !cap_off || !img_ref_off || !need || n_images < 1 || n_images > INT32_MAX || items_per_image < 1) return -1;
+    if (img_ref_off[0] < 0) return -1;
+    for (int64_t i = 0; i < n_images; ++i) if (img_ref_off[i + 1] <= img_ref_off[i]) return -1;      // an image without references
+    const int64_t c0 = img_ref_off[0], ncaps = img_ref_off[n_images] - c0;
+    const int n = s->n;
+    std::vector<Cooked> caps((size_t)ncaps);
+    for (int64_t c = 0; c < ncaps; ++c) {
+        const int64_t a = cap_off[c0 + c], b = cap_off[c0 + c + 1];
+        if (b < a || b - a > INT32_MAX / 8 || (b > a && !cap_tok)) return -1;
+        if (!cook(cap_tok + a, (int)(b - a), MAXN, caps[(size_t)c])) return -1;
+    }
+    // sizes
+    int64_t bytes = (int64_t)sizeof(sc::PackHdr) + n_images * 8;
+    for (int64_t i = 0; i < n_images; ++i) {
+        int64_t nkeys = 0;
+        for (int64_t c = img_ref_off[i] - c0; c < img_ref_off[i + 1] - c0; ++c) nkeys += (int64_t)caps[(size_t)c].key.size();
+        if (nkeys > INT32_MAX / 32) return -1;
+        bytes += sc::img_block_bytes((int)(img_ref_off[i + 1] - img_ref_off[i]), (int)nkeys);
+    }
+    // document frequencies: cached table, or the batch's own — one document per hypothesis item, so an image counts
+    // items_per_image times (computed per image: the items of an image share one reference list)
+    std::unordered_map<uint64_t, double> local;
+    const std::unordered_map<uint64_t, double>* df = &s->df;
+    double ref_len_log = s->ref_len_log;
+    if (!s->cached) {
+        std::vector<uint64_t> seen;
+        for (int64_t i = 0; i < n_images; ++i) {
+            seen.clear();
+            for (int64_t c = img_ref_off[i] - c0; c < img_ref_off[i + 1] - c0; ++c) {
+                const Cooked& k = caps[(size_t)c];
+                for (size_t j = 0; j < k.key.size(); ++j) if (k.ord[j] < n) seen.push_back(k.key[j]);
+            }
+            std::sort(seen.begin(), seen.end());
+            seen.erase(std::unique(seen.begin(), seen.end()), seen.end());
+            for (uint64_t k : seen) local[k] += (double)items_per_image;
+        }
+        df = &local;
+        ref_len_log = std::log((double)n_images * (double)items_per_image);
+    }
+    need[0] = bytes;
+    need[1] = s->cached ? 0 : df_table_bytes(local.size(), nullptr);
+    if (ref_len_log_out) *ref_len_log_out = ref_len_log;
+    if (!pack_out) return 0;
+    if (pack_bytes < need[0] || (need[1] > 0 && (!df_out || df_bytes < need[1]))) return -2;
+
+    unsigned char* out = (unsigned char*)pack_out;
+    std::memset(out, 0, (size_t)bytes);
+    sc::PackHdr* h = (sc::PackHdr*)out;
+    h->magic = sc::PACK_MAGIC; h->version = sc::PACK_VERSION;
+    h->n_images = (int32_t)n_images; h->items_per_image = items_per_image;
+    h->n = n; h->cached = s->cached ? 1 : 0;
+    h->bytes = bytes; h->ref_len_log = ref_len_log;
+    int64_t* img_off = (int64_t*)(out + sizeof(sc::PackHdr));
+    int64_t at = (int64_t)sizeof(sc::PackHdr) + n_images * 8;
+    std::vector<int> order;
+    for (int64_t i = 0; i < n_images; ++i) {
+        const int nref = (int)(img_ref_off[i + 1] - img_ref_off[i]);
+        int nkeys = 0;
+        for (int r = 0; r < nref; ++r) nkeys += (int)caps[(size_t)(img_ref_off[i] - c0 + r)].key.size();
+        img_off[i] = at;
+        unsigned char* blk = out + at;
+        sc::ImgHdr* ih = (sc::ImgHdr*)blk;
+        ih->nref = nref; ih->nkeys = nkeys; ih->bytes = (int32_t)sc::img_block_bytes(nref, nkeys);
+        sc::RefHdr* rh = (sc::RefHdr*)(blk + sizeof(sc::ImgHdr));
+        uint64_t* key = (uint64_t*)(rh + nref);
+        double* vec = (double*)(key + nkeys);
+        int32_t* cnt = (int32_t*)(vec + nkeys);
+        int first = 0;
+        for (int r = 0; r < nref; ++r) {
+            const Cooked& c = caps[(size_t)(img_ref_off[i] - c0 + r)];
+            const int nk = (int)c.key.size();
+            // counts2vec in the reference's insertion order (the norms are sums in that order), then stored sorted by key
+            std::vector<double> v((size_t)nk, 0.0);
+            double nsq[MAXN] = {0, 0, 0, 0};
+            int length = 0;
+            for (int j = 0; j < nk; ++j) {
+                const int o = c.ord[j];
+                if (o >= n) continue;
+                const auto it = df->find(c.key[j]);
+                v[j] = sc::tfidf(c.cnt[j], it == df->end() ? 0.0 : it->second, ref_len_log);
+                nsq[o] += std::pow(v[j], 2);
+                if (o == 1) length += c.cnt[j];
+            }
+            rh[r].first = first; rh[r].nkeys = nk; rh[r].len = c.len; rh[r].length = length;
+            for (int o = 0; o < MAXN; ++o) rh[r].norm[o] = std::sqrt(nsq[o]);
+            order.resize((size_t)nk);
+            for (int j = 0; j < nk; ++j) order[j] = j;
+            std::sort(order.begin(), order.end(), [&](int a, int b) { return c.key[a] < c.key[b]; });
+            for (int j = 0; j < nk; ++j) {
+                key[first + j] = c.key[order[j]]; vec[first + j] = v[order[j]]; cnt[first + j] = c.cnt[order[j]];
+            }
+            first += nk;
+        }
+        at += ih->bytes;
+    }
+    if (need[1] > 0) {
+        std::vector<std::pair<uint64_t, double>> kv(local.begin(), local.end());
+        df_table_write(kv, (unsigned char*)df_out);
+    }
+    return 0;
+}
+
+extern "C" int ortk_scorer_df_table(const ortk_scorer* s, void* out, int64_t out_bytes, int64_t* need) {
+    if (!s || !need || !s->cached) return -1;
+    *need = df_table_bytes(s->df.size(), nullptr);
+    if (!out) return 0;
+    if (out_bytes < *need) return -2;
+    std::vector<std::pair<uint64_t, double>> kv(s->df.begin(), s->df.end());
+    df_table_write(kv, (unsigned char*)out);
+    return 0;
+}
+
+extern "C" int ortk_scorer_score_pack_host(const ortk_scorer_pack_args* a) {
+    if (!sc::args_ok(a)) return -1;
+    const unsigned char* pack = (const unsigned char*)a->pack;
+    const sc::PackHdr* h = (const sc::PackHdr*)pack;
+    if (h->magic != sc::PACK_MAGIC || h->version != sc::PACK_VERSION || h->n_images != a->n_images) return -1;
+    const unsigned char* dft = (const unsigned char*)a->df_table;
+    const int n = a->n, L = a->L, ns = a->ns, rows = ns + (a->greedy ? 1 : 0);
+    const bool use_c = a->cider_weight > 0.0, use_b = sc::use_bleu(a->bleu_weight);
+    for (int64_t r = 0; r < (int64_t)a->n_images * ns; ++r)
+        for (int t = 0; t < L; ++t) { const int64_t w = a->sample[r * a->sample_stride + t]; if (w < 0 || w >= 65535) return -1; }
+    if (a->greedy)
+        for (int64_t r = 0; r < a->n_images; ++r)
+            for (int t = 0; t < L; ++t) { const int64_t w = a->greedy[r * a->greedy_stride + t]; if (w < 0 || w >= 65535) return -1; }
+    std::vector<double> score((size_t)rows);
+    for (int img = 0; img < a->n_images; ++img) {
+        const unsigned char* blk = pack + sc::pack_img_off(pack)[img];
+        const sc::RefHdr* rf = sc::img_refs(blk);
+        const uint64_t* rkey = sc::img_keys(blk);
+        const double* rvec = sc::img_vec(blk);
+        const int32_t* rcnt = sc::img_cnt(blk);
+        const int nref = sc::img_hdr(blk)->nref;
+        for (int row = 0; row < rows; ++row) {      // row ns = the greedy row
+            const int64_t* tok64 = row < ns ? a->sample + ((int64_t)img * ns + row) * a->sample_stride : a->greedy + (int64_t)img * a->greedy_stride;
+            const int len = sc::cut_len(tok64, L, a->eos, a->pad);
+            int32_t tok[sc::MAX_L];
+            for (int t = 0; t < len; ++t) tok[t] = (int32_t)tok64[t];
+            const int total = sc::slot_total(len);
+            uint64_t key[sc::MAX_SLOTS];
+            int cnt[sc::MAX_SLOTS];
+            double hvec[sc::MAX_SLOTS];
+            for (int sidx = 0; sidx < total; ++sidx) {
+                int k, i, b, e;
+                sc::slot_pos(len, sidx, k, i, b, e);
+                key[sidx] = sc::pack_key(tok + i, k);
+            }
+            double nsq[MAXN] = {0, 0, 0, 0};
+            for (int sidx = 0; sidx < total; ++sidx) {
+                int k, i, b, e;
+                sc::slot_pos(len, sidx, k, i, b, e);
+                cnt[sidx] = sc::slot_count(key, sidx, b, e);
+                hvec[sidx] = 0.0;
+                if (use_c && cnt[sidx] > 0 && k <= n) {
+                    hvec[sidx] = sc::tfidf(cnt[sidx], sc::df_lookup(dft, key[sidx]), a->ref_len_log);
+                    nsq[k - 1] += hvec[sidx] * hvec[sidx];
+                }
+            }
+            const int hlength = sc::hyp_length(len, n);
+            double hnorm[MAXN], cscore[MAXN] = {0, 0, 0, 0};
+            for (int o = 0; o < MAXN; ++o) hnorm[o] = std::sqrt(nsq[o]);
+            int mx[sc::MAX_SLOTS];
+            for (int sidx = 0; sidx < total; ++sidx) mx[sidx] = 0;
+            for (int r = 0; r < nref; ++r) {
+                double val[MAXN] = {0, 0, 0, 0};
+                for (int sidx = 0; sidx < total; ++sidx) {
+                    if (cnt[sidx] == 0) continue;
+                    const int q = sc::ref_find(rkey, rf[r], key[sidx]);
+                    if (q < 0) continue;
+                    mx[sidx] = std::max(mx[sidx], (int)rcnt[q]);
+                    const int o = sc::key_order(key[sidx]);
+                    if (o < n) val[o] += std::min(hvec[sidx], rvec[q]) * rvec[q];
+                }
+                if (use_c) for (int o = 0; o < n; ++o) cscore[o] += sc::cider_ref_term(val[o], hnorm[o], rf[r].norm[o], hlength, rf[r].length, a->sigma);
+            }
+            const double cider = use_c ? sc::cider_finish(cscore, n, nref) : 0.0;
+            double bleu[4] = {0, 0, 0, 0};
+            if (use_b) {
+                int correct[4] = {0, 0, 0, 0};
+                for (int sidx = 0; sidx < total; ++sidx)
+                    if (cnt[sidx] > 0) correct[sc::key_order(key[sidx])] += std::min(mx[sidx], cnt[sidx]);
+                sc::bleu_finish(correct, len, sc::closest_reflen(blk, len), bleu);
+            }
+            score[(size_t)row] = sc::combine(cider, bleu, a->cider_weight, a->bleu_weight);
+        }
+        for (int j = 0; j < ns; ++j) {
+            const double base = sc::baseline_score(score.data(), ns, j, a->baseline, a->greedy ? score[(size_t)ns] : 0.0);
+            const int64_t o = (int64_t)img * ns + j;
+            a->reward[o] = (float)(score[(size_t)j] - base);
+            if (a->score_sample) a->score_sample[o] = score[(size_t)j];
+            if (a->score_baseline) a->score_baseline[o] = base;
+        }
     }
     return 0;
 }

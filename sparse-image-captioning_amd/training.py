@@ -343,12 +343,36 @@ class NativeTrainer:
         L.check(lib.ortk_masked_adam_step(C.byref(k), L.stream_ptr()), "ortk_masked_adam_step")
 
     @staticmethod
-    def scorer_reward_fn(scorer, refs, eos_idx=3, pad_idx=0, decode=None):
+    def scorer_reward_fn(scorer, refs, eos_idx=3, pad_idx=0, decode=None, device=False, vocab_size=None):
         """``reward_fn`` for :meth:`scst_step` from a :class:`..scst.CaptionScorer` and the images' reference captions:
         reward = score(sample) - score(baseline), as ``compute_scst_loss`` does (utils/training.py:239-254).  With
         ``decode`` (``tokenizer.decode``) the rows are decoded to strings and ``refs`` are the reference strings (``gts``) —
         the reference's flow, required for its word-keyed df pickles; without it ``refs`` are token-id lists and the scorer's
-        document frequencies must be in token-id space (see ``CaptionScorer.score_sequences``)."""
+        document frequencies must be in token-id space (see ``CaptionScorer.score_sequences``).
+
+        ``device=True``: the reward is scored on the GPU (``CaptionScorer.score_device``: one kernel on the current stream reads
+        the sampled tokens where the decode left them) and returned as a device tensor, so ``scst_step`` takes its device-reward
+        branch and the step runs without a host synchronisation.  ``refs`` are token-id lists, or the result of
+        ``scorer.pack_refs`` / ``scorer.device_refs`` cooked ahead of time (e.g. in the data loader); ``vocab_size`` (the
+        model's, required) must be at most 65534.  ``decode`` does not apply: there is no string path on the device."""
+        if device:
+            from .scst.scorers import MAX_DEVICE_VOCAB
+            if decode is not None:
+                raise ValueError("scorer_reward_fn(device=True): no string path on the device, `decode` does not apply")
+            if vocab_size is None or int(vocab_size) > MAX_DEVICE_VOCAB:
+                raise ValueError(f"scorer_reward_fn(device=True) needs the model's vocab_size, at most {MAX_DEVICE_VOCAB} (got {vocab_size})")
+            cooked = {}
+
+            def dev_fn(seq, greedy):
+                items = seq.size(1) + (greedy is not None)
+                key = (items, str(seq.device))
+                if key not in cooked:       # host work only (cook + asynchronous upload); nothing here waits for the device
+                    from .scst.scorers import RefPack
+                    on_dev = isinstance(refs, RefPack) and torch.is_tensor(refs.pack)
+                    cooked[key] = refs if on_dev else scorer.device_refs(refs, items, seq.device, vocab_size=vocab_size)
+                return scorer.score_device(cooked[key], seq, greedy, eos_idx=eos_idx, pad_idx=pad_idx)[0]
+            return dev_fn
+
         def fn(seq, greedy):
             sc_sample, sc_baseline = scorer.score_sequences(refs, seq, greedy, eos_idx=eos_idx, pad_idx=pad_idx, decode=decode)
             return torch.from_numpy(sc_sample - sc_baseline).float()
