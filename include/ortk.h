@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 3      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 4      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -313,7 +313,6 @@ int ortk_row_bchain(const ortk_bchain_args* a, ortk_stream stream);
 /* Process-wide A/B switches for measurements (the scripts under scratch/); the defaults are the product path and nothing in the library reads the
  * environment.  Not thread-safe against running calls: set them before the work starts. */
 typedef struct ortk_tuning {
-    int32_t gemm_impl;       /* 0 automatic | 1 register-staged GEMM kernel only | 2 128 x 128 LDS-DMA tiles for every layout | 3 256 x 256 whenever legal */
     int32_t gemm_t64;        /* 64 x 64 LDS-DMA tiles while the 128 x 128 grid has at most this many workgroups (640; -1 never) */
     int32_t attn_impl;       /* 0 automatic | 1 wave kernels | 3 fp32-MFMA kernels | 4 small register-only kernels (ortk_attn.hip dispatch) */
     int32_t attn16_min_lq;   /* fp32-input query blocks shorter than this stay off the bf16-operand attention kernels (33) */
@@ -349,7 +348,7 @@ typedef struct ortk_tuning {
                                      (ortk_gemm ln_mode 2 on short row panels).  OFF by default: alone the fused launch ties the two it replaces
                                      (59.5 vs 62.0 us at 16 640 x 512 x 512), inside the step it needs a free compute unit per workgroup and waits for
                                      the units the side stream's weight gradients hold: 11.65 vs 10.40 ms per XE step (scratch/wgrad_group_ab.py)
-                                     | bit 1: ln_mode 2 on the 128-row panels of round 3 (measurement) | bit 2: the LayerNorm backward of width 512 with four
+                                     | bit 1: unused, refused (it selected the 128-row backward panels of round 3, removed) | bit 2: the LayerNorm backward of width 512 with four
                                      instead of eight consecutive columns per lane (measurement) | bit 3: the executor keeps the LayerNorm output gradients
                                      (data gradient -> ortk_layernorm_bwd_dt) in fp32 in mixed precision too; default: bf16 there, as every other gradient
                                      that is a GEMM operand in that mode */

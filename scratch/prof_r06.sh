@@ -58,7 +58,7 @@ python3 bench.py --full --steps 50 --warmup 10 > $O/r06_default_bench_line.json 
 wc -c $O/r06_default_bench_line.json; tail -2 $O/bench.err
 # the round's A/B and kernel-alone figures cited from DESIGN.md / the sources, from this library
 python3 scratch/wgrad_group_ab.py > $O/r06_wgrad_group_ab.txt 2>&1
-python3 scratch/wgrad_group_ab.py gemm_epilogue=1 gemm_epilogue=0 ln_fuse=8 ln_fuse=0 wgrad_group_wgs=64 wgrad_group_wgs=96 ln_fuse=1 gemm_impl=2 gemm_impl=3 > $O/r06_xe_step_switches_ab.txt 2>&1
+python3 scratch/wgrad_group_ab.py gemm_epilogue=1 gemm_epilogue=0 ln_fuse=8 ln_fuse=0 wgrad_group_wgs=64 wgrad_group_wgs=96 ln_fuse=1 > $O/r06_xe_step_switches_ab.txt 2>&1
 python3 scratch/wgrad_group_bench.py 0 > $O/r06_wgrad_group.txt 2>&1
 python3 scratch/box_bwd_bench.py > $O/r06_box_bwd.txt 2>&1
 python3 scratch/gemm_fixed_cost.py > $O/r06_gemm_fixed_cost.txt 2>&1

@@ -3,23 +3,35 @@
 // Replaces torch.nn.functional.linear + its autograd in the reference
 // (models/transformer.py:238,280,324-325,412; models/relation_transformer.py:168-176,191,331-333).
 //
-// One kernel template covers the three operand layouts the path needs, all on row-major fp32 storage:
-//   forward   Y  = X  W^T   : A (M,K)        , B = W  (N,K)  -> transA=0, transB=0
-//   dgrad     dX = dY W     : A (M,K'=N_out) , B = W  stored (K',N') -> transA=0, transB=1
-//   wgrad     dW = dY^T X   : A = dY stored (K'=rows, M'=N_out), B = X stored (K', N'=K_in) -> transA=1, transB=1
+// Operand layouts, all row-major:  forward Y = X W^T (A (M,K), B (N,K); transA = transB = 0) | dgrad dX = dY W (B stored (K,N);
+// transB = 1) | wgrad dW = dY^T X (both stored k-major; transA = transB = 1).  One entry point, ortk_gemm() at the bottom of the file:
+// validate -> plan (one plan_* function per kernel family, tried in the order of this table) -> one launch tail.
 //
-// Tiling (gfx950, wave64): 128x128 output tile per 256-thread workgroup, 4 waves as 2x2, each wave 64x64 =
-// 4x4 MFMA 16x16 tiles; K is consumed 16 (fp32) or 32 (bf16) at a time through a double-buffered LDS image
-// that is ALWAYS k-major ([k][m] / [k][n]); only the global->LDS staging differs per layout, so the fragment
-// reads are identical for all three.  The MFMA is issued "swapped" (B-tile as the A operand) so that each lane
-// ends up with 4 consecutive n for one m: epilogue loads/stores are float4 along the contiguous C dimension.
+//   kernel family                  operands / layouts             shapes                                    picked by
+//   -----------------------------  -----------------------------  ----------------------------------------  ---------------------------------
+//   gemm_bf16_rowln_bwd_kernel<MT> bf16 x bf16, forward           N = 512, K % 64 == 0, 32-bit offsets      plan_ln: ln_mode 2 and ln_fused()
+//   gemm_bf16_row512_kernel        bf16 x bf16, forward           N = 512, K % 64 == 0                      plan_ln: ln_mode 1 and ln_fused()
+//     (any other ln_mode call: the plain product below + ortk_layernorm_fwd / _bwd_drop_rows)
+//   gemm_f32x3_kernel / x3p        fp32 x fp32, forward           K % 32 == 0, 16-byte aligned rows         plan_f32x3: f32_split != 0
+//   gemm_f32x3t_kernel<TA, ACC>    fp32 x fp32, dgrad / wgrad     N % 4 == 0 (wgrad: M % 4 == 0), split-K   plan_f32x3t: f32_split != 0
+//   gemm_f32_kernel<TA, TB>        fp32 x fp32, all three         any                                       plan_f32: what is left of fp32
+//   gemm_bf16_dma64_kernel<NS>     bf16 x bf16, forward           M <= 6 144, N <= 2 048, N % 128 == 0,     plan_dma64: bf16_fast4(), no dropout /
+//                                                                 K % 64 == 0, <= gemm_t64 128 x 128 tiles  gate / row scale / statistics
+//   gemm_bf16_dma256_kernel<EPI>   bf16 x bf16, forward           N % 256 == 0 (or 256 n + 128: remainder   plan_dma: `big` (its grid fills half of
+//                                                                 on the 128 x 128 kernel), K % 64 == 0     its last round), no split-K, no statistics
+//   gemm_bf16_glds_kernel<BIG,EPI> bf16 x bf16, forward           N % 128 == 0, K % 32 == 0; ragged M       plan_dma: the rest of the forward layout
+//                                                                 without split-K, else M % 128 == 0        with full tiles; BIG: `big` and K = 32 (mod 64)
+//   gemm_bf16_kernel<TA,TB,AT,BT,  fp32 or bf16 operands, all     any (FAST: full tiles, aligned)           plan_bf16: what is left of precision 1
+//                    FAST>         three, split-K, column sums                                              (every k-major layout among it)
+//
+// EPI >= 0 instances run the lean epilogue (epilogue_lean: options compiled out), EPI = -1 the general one (epilogue_tile), which
+// every other kernel uses as well.  Common tiling (gfx950, wave64): MFMA issued "swapped" (B tile as the A operand) so that a lane
+// holds 4 consecutive n of one m and the epilogue's loads / stores are float4 along the contiguous C dimension.
 //
 // Workgroup ids are remapped so that the blocks resident on one XCD (ids b, b+8, ...) walk CONSECUTIVE tiles
 // (n fastest): they share the A panel in that XCD's L2 instead of fetching it 8 times.
-#include <cstdlib>
-#include <mutex>
+#include <algorithm>
 #include <type_traits>
-#include <vector>
 #include "ortk_internal.h"
 
 namespace {
@@ -745,21 +757,14 @@ typedef __attribute__((address_space(1))) const void glb_void;
 // 4 waves; 256: 16 instructions over 8 waves)
 // rmax: last valid row of an [m][k] operand (a partial last row tile re-reads it; its results are dropped by the epilogue)
 // (PERM: the [n][k] image of the permuted column order, see swz_mkp)
-template <bool T, int TM, bool PERM = false>
+template <bool PERM = false>
 __device__ __forceinline__ void glds_tile(const __bf16* __restrict__ base, int64_t ld, int tile0, int k0, __bf16* img, int wave, int lane,
                                           int rmax = 0x7FFFFFFF) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int inst = wave * 2 + u;
-        const __bf16* g;
-        if (!T) {
-            const int r = inst * 16 + (lane >> 2), c = (lane & 3) ^ (PERM ? swz_mkp(r) : swz_mk(r));
-            g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
-        } else {
-            constexpr int CPR = TM / 8;                       // 16-byte chunks per k-row
-            const int f = inst * 64 + lane, kr = f / CPR, c = (f % CPR) ^ swz_km(kr);
-            g = base + (int64_t)(k0 + kr) * ld + tile0 + c * 8;
-        }
+        const int r = inst * 16 + (lane >> 2), c = (lane & 3) ^ (PERM ? swz_mkp(r) : swz_mk(r));
+        const __bf16* g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
         __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)(img + inst * 512), 16, 0, 0);
     }
 }
@@ -771,27 +776,15 @@ __device__ __forceinline__ bf16x8 gfragp(const __bf16* img, int n0, int j, int l
     return *reinterpret_cast<const bf16x8*>(img + row * GBK + ((lg ^ swz_mkp(row)) << 3));
 }
 
-template <bool T, int TM>
 __device__ __forceinline__ bf16x8 gfrag(const __bf16* img, int m0, int lane) {
     const int lr = lane & 15, lg = lane >> 4;
-    if (!T) {
-        return *reinterpret_cast<const bf16x8*>(img + (m0 + lr) * GBK + ((lg ^ swz_mk(lr)) << 3));
-    } else {
-        // lane 4q+p of a 16-lane group supplies &img[k = 8*lg + q][m0 + 4p]; it receives column (lane & 15) of 4 k-rows
-        const int q = lr >> 2, pp = lane & 3;
-        const int chunk = ((m0 >> 3) + (pp >> 1)) ^ (2 * q + 8 * (lg & 1));
-        const __bf16* a = img + (8 * lg + q) * TM + (chunk << 3) + 4 * (pp & 1);
-        const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * TM);      // k + 4: same swizzle (bit 2 of k is not used)
-        return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
+    return *reinterpret_cast<const bf16x8*>(img + (m0 + lr) * GBK + ((lg ^ swz_mk(lr)) << 3));
 }
 
 // BIG = false: 128 x 128 tile, 4 waves (2 x 2), 64 KB ring, two workgroups per CU.
 // BIG = true : 256 x 256 tile, 8 waves (2 x 4, each 128 x 64), 128 KB ring, one workgroup per CU: half the operand
 //              bytes fetched per FLOP (128 FLOP/B instead of 64) — the measured bound of the small tile is the
 //              L2 -> CU fetch rate (~13 B/clk/CU sustained), not MFMA issue.
-// NS = ring depth (4, or 8 for grids of at most one workgroup per CU: with 7 tiles in flight almost the whole K = 512
-// panel of a decode-sized GEMM is requested up front and the K loop stops being a chain of fetch latencies).
 // Soft-max partials {max, sum exp(. - max)} of a wave's (16 MI) rows x 64 columns at (m0, n0) (ortk_gemm_args.tile_stats; natural column order)
 template <int MI>
 __device__ __forceinline__ void stats_partials(const ortk_gemm_args& p, int m0, int n0, int lane, f32x4 (&acc)[MI][4]) {
@@ -894,12 +887,13 @@ __device__ __forceinline__ void samp_candidates(const ortk_gemm_args& p, int m0,
     }
 }
 
-// EPI (128 x 128 forward layout without split-K accumulation or row scale; the launcher chooses): -1 = the general epilogue; 0..3 = the
+// EPI (128 x 128 tile without split-K accumulation or row scale; the launcher chooses): -1 = the general epilogue; 0..3 = the
 // lean one (epilogue_lean: bit 0 dropout, bit 1 gate) on the permuted column order; 4 = soft-max partials, 5 = partials + sampling
 // candidates, then the lean store.
-template <bool TA, bool TB, bool BIG, int NS, int EPI = -1>
-__global__ __launch_bounds__(BIG ? 512 : 256, (BIG || NS > 4) ? 1 : 2) void gemm_bf16_glds_kernel(ortk_gemm_args p, int tilesM, int tilesN, int kchunk) {
-    static_assert(EPI < 0 || (!TA && !TB && !BIG), "lean epilogues: the 128 x 128 forward layout");
+template <bool BIG, int EPI = -1>
+__global__ __launch_bounds__(BIG ? 512 : 256, BIG ? 1 : 2) void gemm_bf16_glds_kernel(ortk_gemm_args p, int tilesM, int tilesN, int kchunk) {
+    static_assert(EPI < 0 || !BIG, "lean epilogues: the 128 x 128 tile");
+    constexpr int NS = GNS;                         // ring depth
     constexpr bool PERM = EPI >= 0 && EPI < 4;      // (the statistics' column blocks keep the natural order)
     constexpr int TM = BIG ? 256 : 128;             // tile rows = tile columns
     constexpr int MI = BIG ? 8 : 4;                 // 16-row fragments per wave
@@ -925,18 +919,11 @@ __global__ __launch_bounds__(BIG ? 512 : 256, (BIG || NS > 4) ? 1 : 2) void gemm
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // fused bias gradient (wgrad layout): column sums of the k-major A tile = one more output column against a vector of
-    // ones, taken by the wn = 0 waves of the first N-tile's workgroups with MI extra MFMAs per tile
-    const bool do_cs = TA && p.colsum != nullptr && nt == 0 && wn == 0;
-    f32x4 acc_cs[MI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) acc_cs[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bf16x8 ones = {(__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f, (__bf16)1.f};
 
     auto issue = [&](int t) {
         __bf16* st = smem16 + (size_t)(t & (NS - 1)) * 2 * IMG;
-        glds_tile<TA, TM>(Ap, p.lda, mb, k_begin + t * GBK, st, wave, lane, TA ? 0x7FFFFFFF : p.M - 1);
-        glds_tile<TB, TM, PERM>(Bp, p.ldb, nb, k_begin + t * GBK, st + IMG, wave, lane);
+        glds_tile(Ap, p.lda, mb, k_begin + t * GBK, st, wave, lane, p.M - 1);
+        glds_tile<PERM>(Bp, p.ldb, nb, k_begin + t * GBK, st + IMG, wave, lane);
     };
     for (int t = 0; t < NS - 1 && t < T; ++t) issue(t);
     for (int t = 0; t < T; ++t) {
@@ -959,26 +946,18 @@ __global__ __launch_bounds__(BIG ? 512 : 256, (BIG || NS > 4) ? 1 : 2) void gemm
         const __bf16* sB = sA + IMG;
         bf16x8 a[MI], b[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = PERM ? gfragp(sB, wn * 64, j, lane) : gfrag<TB, TM>(sB, wn * 64 + 16 * j, lane);
+        for (int j = 0; j < 4; ++j) b[j] = PERM ? gfragp(sB, wn * 64, j, lane) : gfrag(sB, wn * 64 + 16 * j, lane);
 #pragma unroll
-        for (int i = 0; i < MI; ++i) a[i] = gfrag<TA, TM>(sA, wm * (16 * MI) + 16 * i, lane);
-        if (TA && do_cs) {
-#pragma unroll
-            for (int i = 0; i < MI; ++i) acc_cs[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, a[i], acc_cs[i], 0, 0, 0);
-        }
+        for (int i = 0; i < MI; ++i) a[i] = gfrag(sA, wm * (16 * MI) + 16 * i, lane);
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
     }
-    if (TA && do_cs && lane < 16) {
-#pragma unroll
-        for (int i = 0; i < MI; ++i) atomicAdd(p.colsum + mb + wm * (16 * MI) + 16 * i + lane, acc_cs[i][0]);
-    }
-    if ((EPI < 0 || EPI >= 4) && !BIG && !TA && !TB && p.tile_stats)
+    if ((EPI < 0 || EPI >= 4) && !BIG && p.tile_stats)
         stats_partials<MI>(p, mb + wm * (16 * MI), nb + wn * 64, lane, *reinterpret_cast<f32x4(*)[MI][4]>(&acc[0]));
-    if ((EPI < 0 || EPI == 5) && !BIG && !TA && !TB && p.tile_samp) {
+    if ((EPI < 0 || EPI == 5) && !BIG && p.tile_samp) {
         // (one instance per draw function, chosen once: the per-element choice doubled the straight-line code of the block)
         if (p.samp_fast) samp_candidates<true, MI>(p, mb + wm * (16 * MI), nb + wn * 64, lane, *reinterpret_cast<f32x4(*)[MI][4]>(&acc[0]));
         else             samp_candidates<false, MI>(p, mb + wm * (16 * MI), nb + wn * 64, lane, *reinterpret_cast<f32x4(*)[MI][4]>(&acc[0]));
@@ -1000,7 +979,7 @@ __global__ __launch_bounds__(BIG ? 512 : 256, (BIG || NS > 4) ? 1 : 2) void gemm
         for (int hh = 0; hh < MI / 4; ++hh)
             epilogue_tile<true>(e, mb + wm * (16 * MI) + 64 * hh + (lane & 15), nb + wn * 64 + 4 * (lane >> 4),
                                 *reinterpret_cast<f32x4(*)[4][4]>(&acc[4 * hh]));
-    } else {              // partial last row tile (forward layout, ragged M): bounds-checked stores
+    } else {              // partial last row tile (ragged M): bounds-checked stores
 #pragma unroll
         for (int hh = 0; hh < MI / 4; ++hh)
             epilogue_tile<false>(e, mb + wm * (16 * MI) + 64 * hh + (lane & 15), nb + wn * 64 + 4 * (lane >> 4),
@@ -1019,37 +998,25 @@ constexpr size_t GLDS_LDS_BYTES_BIG = (size_t)GNS * 2 * 256 * GBK * sizeof(__bf1
 // the 16 lanes of every ds_read_b128 service group then hit 16 distinct 16-byte slots.
 constexpr int HBK = 64;
 
-template <bool T, bool PERM = false>
+template <bool PERM = false>
 __device__ __forceinline__ void glds_tile64(const __bf16* __restrict__ base, int64_t ld, int tile0, int k0, __bf16* img, int wave, int lane,
                                             int rmax = 0x7FFFFFFF) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int inst = wave * 4 + u;                         // 32 wave-instructions of 1 KB per 256 x 64 operand tile
-        const __bf16* g;
-        if (!T) {
-            const int r = inst * 8 + (lane >> 3), c = (lane & 7) ^ (PERM ? swz_mk64p(r) : swz_mk64(r));
-            g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
-        } else {
-            const int f = inst * 64 + lane, kr = f >> 5, c = (f & 31) ^ swz_km(kr);     // 32 chunks per 512-byte k-row
-            g = base + (int64_t)(k0 + kr) * ld + tile0 + c * 8;
-        }
+        const int r = inst * 8 + (lane >> 3), c = (lane & 7) ^ (PERM ? swz_mk64p(r) : swz_mk64(r));
+        const __bf16* g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
         __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)(img + inst * 512), 16, 0, 0);
     }
 }
 
 // one 1-KB piece (wave-instruction) of a 256 x 64 operand tile: piece index u = 0..3 of this wave
-template <bool T, bool PERM = false>
+template <bool PERM = false>
 __device__ __forceinline__ void glds_piece64(const __bf16* __restrict__ base, int64_t ld, int tile0, int k0, __bf16* img, int wave, int lane, int u,
                                              int rmax = 0x7FFFFFFF) {
     const int inst = wave * 4 + u;
-    const __bf16* g;
-    if (!T) {
-        const int r = inst * 8 + (lane >> 3), c = (lane & 7) ^ (PERM ? swz_mk64p(r) : swz_mk64(r));
-        g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
-    } else {
-        const int f = inst * 64 + lane, kr = f >> 5, c = (f & 31) ^ swz_km(kr);
-        g = base + (int64_t)(k0 + kr) * ld + tile0 + c * 8;
-    }
+    const int r = inst * 8 + (lane >> 3), c = (lane & 7) ^ (PERM ? swz_mk64p(r) : swz_mk64(r));
+    const __bf16* g = base + (int64_t)min(tile0 + r, rmax) * ld + k0 + c * 8;
     __builtin_amdgcn_global_load_lds((glb_void*)g, (lds_void*)(img + inst * 512), 16, 0, 0);
 }
 
@@ -1061,26 +1028,17 @@ __device__ __forceinline__ bf16x8 gfrag64p(const __bf16* img, int n0, int j, int
     return *reinterpret_cast<const bf16x8*>(img + row * HBK + (((ks * 4 + lg) ^ swz_mk64p(row)) << 3));
 }
 
-template <bool T>
 __device__ __forceinline__ bf16x8 gfrag64(const __bf16* img, int m0, int ks, int lane) {
     const int lr = lane & 15, lg = lane >> 4;
-    if (!T) {
-        return *reinterpret_cast<const bf16x8*>(img + (m0 + lr) * HBK + (((ks * 4 + lg) ^ swz_mk64(lr)) << 3));
-    } else {
-        const int q = lr >> 2, pp = lane & 3;
-        const int chunk = ((m0 >> 3) + (pp >> 1)) ^ (2 * q + 8 * (lg & 1));
-        const __bf16* a = img + (ks * 32 + 8 * lg + q) * 256 + (chunk << 3) + 4 * (pp & 1);
-        const bf16x4 lo = tr_read(a), hi = tr_read(a + 4 * 256);
-        return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
+    return *reinterpret_cast<const bf16x8*>(img + (m0 + lr) * HBK + (((ks * 4 + lg) ^ swz_mk64(lr)) << 3));
 }
 
-// EPI: -1 = the general epilogue (every option a run-time test); 0..3 = the lean one, bit 0 dropout, bit 1 gate (forward layout, no
-// split-K accumulation, no row scale: the launcher chooses)
-template <bool TA, bool TB, int EPI = -1>
+// EPI: -1 = the general epilogue (every option a run-time test); 0..3 = the lean one, bit 0 dropout, bit 1 gate (no split-K accumulation,
+// no row scale: the launcher chooses).  The B image is always the permuted one (swz_mk64p / gfrag64p): a lane's accumulators pair up
+// into 8 consecutive columns.  (Soft-max partials in this kernel's epilogue measured slower than the 128 x 128 kernel on the decode-time
+// generator: launches with statistics never come here.)
+template <int EPI = -1>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_dma256_kernel(ortk_gemm_args p, int tilesM, int tilesN, int kchunk) {
-    constexpr bool PERM = !TB && EPI < 4;            // (EPI 4: soft-max partials per natural 64-column block, then the lean store — measured slower
-                                                     //  than the 128 x 128 kernel on the decode-time generator, not dispatched)
     constexpr int IMG = 256 * HBK;                  // elements per operand image (32 KB)
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1101,8 +1059,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma256_kernel(ortk_gemm_args
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
     auto issue = [&](int t) {
         __bf16* st = smem16 + (size_t)(t & 1) * 2 * IMG;
-        glds_tile64<TA>(Ap, p.lda, mb, k_begin + t * HBK, st, wave, lane, TA ? 0x7FFFFFFF : p.M - 1);
-        glds_tile64<TB, PERM>(Bp, p.ldb, nb, k_begin + t * HBK, st + IMG, wave, lane);
+        glds_tile64(Ap, p.lda, mb, k_begin + t * HBK, st, wave, lane, p.M - 1);
+        glds_tile64<true>(Bp, p.ldb, nb, k_begin + t * HBK, st + IMG, wave, lane);
     };
     if (T > 0) issue(0);
     for (int t = 0; t < T; ++t) {
@@ -1121,15 +1079,15 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma256_kernel(ortk_gemm_args
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[8], b[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = PERM ? gfrag64p(sB, wn * 64, j, ks, lane) : gfrag64<TB>(sB, wn * 64 + 16 * j, ks, lane);
+            for (int j = 0; j < 4; ++j) b[j] = gfrag64p(sB, wn * 64, j, ks, lane);
 #pragma unroll
-            for (int i = 0; i < 8; ++i) a[i] = gfrag64<TA>(sA, wm * 128 + 16 * i, ks, lane);
+            for (int i = 0; i < 8; ++i) a[i] = gfrag64(sA, wm * 128 + 16 * i, ks, lane);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 if (next && (i & 1) == 0) {
                     const int u = ks * 4 + (i >> 1);               // 0..7: pieces 0-3 of A, then 0-3 of B
-                    if (u < 4) glds_piece64<TA>(Ap, p.lda, mb, nk0, nst, wave, lane, u, TA ? 0x7FFFFFFF : p.M - 1);
-                    else       glds_piece64<TB, PERM>(Bp, p.ldb, nb, nk0, nst + IMG, wave, lane, u - 4);
+                    if (u < 4) glds_piece64(Ap, p.lda, mb, nk0, nst, wave, lane, u, p.M - 1);
+                    else       glds_piece64<true>(Bp, p.ldb, nb, nk0, nst + IMG, wave, lane, u - 4);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
@@ -1137,34 +1095,31 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma256_kernel(ortk_gemm_args
             }
         }
     }
+    const int ncol0 = nb + wn * 64 + 8 * (lane >> 4);
     if constexpr (EPI >= 0) {
-        if (EPI == 4 && p.tile_stats) stats_partials<8>(p, mb + wm * 128, nb + wn * 64, lane, acc);
-        epilogue_lean<8, PERM, (EPI & 1) != 0 && EPI < 4, (EPI & 2) != 0 && EPI < 4>(p, mb + wm * 128 + (lane & 15), nb + wn * 64 + (PERM ? 8 : 4) * (lane >> 4), acc);
+        epilogue_lean<8, true, (EPI & 1) != 0, (EPI & 2) != 0>(p, mb + wm * 128 + (lane & 15), ncol0, acc);
         return;
     }
     Epi e{p.C, p.ldc, p.c_dtype, p.bias, p.rowscale, p.resid, p.ldr, p.gate, p.ldg, p.gate_dtype, p.gate_scale,
           p.relu, p.drop_p, p.drop_seed, p.accumulate, ks_ == 0, p.M, p.N, p.drop_row_stride > 0 ? p.drop_row_stride : 1, p.drop_row_off, p.drop_rows};
-    // (forward-layout B: the permuted column order, a lane's accumulators pair up into 8 consecutive columns)
-    const int ncol0 = nb + wn * 64 + (PERM ? 8 : 4) * (lane >> 4);
     if (mb + 256 <= p.M) {
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh)
-            epilogue_tile<true, 4, 4, 16, 16, PERM>(e, mb + wm * 128 + 64 * hh + (lane & 15), ncol0, *reinterpret_cast<f32x4(*)[4][4]>(&acc[4 * hh]));
+            epilogue_tile<true, 4, 4, 16, 16, true>(e, mb + wm * 128 + 64 * hh + (lane & 15), ncol0, *reinterpret_cast<f32x4(*)[4][4]>(&acc[4 * hh]));
     } else {              // partial last row tile (ragged M)
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh)
-            epilogue_tile<false, 4, 4, 16, 16, PERM>(e, mb + wm * 128 + 64 * hh + (lane & 15), ncol0, *reinterpret_cast<f32x4(*)[4][4]>(&acc[4 * hh]));
+            epilogue_tile<false, 4, 4, 16, 16, true>(e, mb + wm * 128 + 64 * hh + (lane & 15), ncol0, *reinterpret_cast<f32x4(*)[4][4]>(&acc[4 * hh]));
     }
 }
 constexpr size_t DMA256_LDS_BYTES = (size_t)2 * 2 * 256 * HBK * sizeof(__bf16);   // 128 KB
 
 
 // ------------------------------------------------------------------------------------------------
-// 128 x 512 "row panel" tile (forward operand layout, N = 512 = d_model): the workgroup owns WHOLE rows of the output, so
-// the LayerNorm that follows the projection in the residual stream (forward: x' = x + dropout(proj), y = LN(x')) or that
-// the product is the output gradient of (backward: dy = dY W, dx = dLN/dx(dy) + residual gradient) runs in the epilogue,
-// on the accumulators, instead of as a second kernel that reads the (rows, 512) fp32 matrix back: 30 + 32 launches of an
-// XE step and the 44 + 34 MB round trip of each.  Same pipeline as the 256 x 256 kernel above: two stages of 64 columns
+// 128 x 512 "row panel" tile (forward operand layout, N = 512 = d_model; ln_mode = 1): the workgroup owns WHOLE rows of the output,
+// so the LayerNorm that follows the projection in the residual stream (x' = x + dropout(proj), y = LN(x')) runs in the epilogue,
+// on the accumulators, instead of as a second kernel that reads the (rows, 512) fp32 matrix back: 30 launches of an
+// XE step and the 44 MB round trip of each.  (The backward counterpart is the short-panel kernel below.)  Same pipeline as the 256 x 256 kernel above: two stages of 64 columns
 // (A 16 KB + B 64 KB each: the whole 160 KB of LDS), 8 waves as 2 x 4, each 64 rows x 128 columns = 4 x 8 MFMA tiles; the
 // 10 DMA pieces a wave moves per stage are issued between the MFMA groups.  Row reductions: in-lane over the lane's 32
 // values of a row, two shuffles over the four lane groups, one LDS exchange over the four column waves.
@@ -1172,18 +1127,6 @@ constexpr int RP_M = 128, RP_N = 512;
 constexpr int RP_IMG_A = RP_M * HBK, RP_IMG_B = RP_N * HBK;
 constexpr size_t RP_LDS_BYTES = (size_t)2 * (RP_IMG_A + RP_IMG_B) * sizeof(__bf16);   // 163 840
 
-// sum over the 16 lanes of a DPP row (the lanes that hold the same columns of 16 different rows); every lane gets the total
-__device__ __forceinline__ float row16_sum(float v) {
-#define ORTK_DPP_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, true))
-    ORTK_DPP_ADD(0xB1);     // quad_perm [1,0,3,2]
-    ORTK_DPP_ADD(0x4E);     // quad_perm [2,3,0,1]
-    ORTK_DPP_ADD(0x141);    // row_half_mirror: the other quad of the half row
-    ORTK_DPP_ADD(0x140);    // row_mirror: the other half row
-#undef ORTK_DPP_ADD
-    return v;
-}
-
-template <int MODE>     // 1: LayerNorm forward of the epilogue's result; 2: LayerNorm backward of the product
 __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args p, int, int, int) {
     extern __shared__ __attribute__((aligned(16))) __bf16 smem16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1223,9 +1166,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[4], b[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) b[j] = gfrag64<false>(sB, wn * 128 + 16 * j, ks, lane);
+            for (int j = 0; j < 8; ++j) b[j] = gfrag64(sB, wn * 128 + 16 * j, ks, lane);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) a[i] = gfrag64<false>(sA, wm * 64 + 16 * i, ks, lane);
+            for (int i = 0; i < 4; ++i) a[i] = gfrag64(sA, wm * 64 + 16 * i, ks, lane);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (next) {
@@ -1245,10 +1188,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
     const int lr = lane_e & 15, lg = lane_e >> 4;
-    const int tid_e = wave * 64 + lane_e;
     float* red0 = reinterpret_cast<float*>(smem16);    // [128 rows][4 column waves]
     float* red1 = red0 + RP_M * 4;
-    float* colr = red1 + RP_M * 4;                     // [2 (da, db)][2 row waves][512]
     const int row0 = mb + wm * 64 + lr;                // + 16 i
     const int col0 = wn * 128 + 4 * lg;                // + 16 j (+ r)
     // sum over the row's 512 columns of one value per (lane, i): lane groups by two shuffles, column waves through LDS
@@ -1266,176 +1207,79 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args
             s[i] = (q[0] + q[1]) + (q[2] + q[3]);
         }
     };
-    if (MODE == 1) {
-        const float inv_keep = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
-        const int drs = p.drop_row_stride > 0 ? p.drop_row_stride : 1;
-        f32x4 bias4[8];
+    const float inv_keep = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
+    const int drs = p.drop_row_stride > 0 ? p.drop_row_stride : 1;
+    f32x4 bias4[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        // (optional operands: an unconditional load from memory that is readable in any case + a select — a uniform branch
+        // around the load makes the compiler wait for every load right after issuing it)
+        const f32x4 t_ = *reinterpret_cast<const f32x4*>((p.bias ? p.bias : p.ln_a) + col0 + 16 * j);
+        bias4[j] = p.bias ? t_ : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    float s[4], q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = row0 + 16 * i, rowc = min(row, p.M - 1);
+        const uint64_t drow = (p.drop_p > 0.f && p.drop_rows) ? (uint64_t)p.drop_rows[rowc] : (uint64_t)rowc;
+        f32x4 res[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            // (optional operands: an unconditional load from memory that is readable in any case + a select — a uniform branch
-            // around the load makes the compiler wait for every load right after issuing it)
-            const f32x4 t_ = *reinterpret_cast<const f32x4*>((p.bias ? p.bias : p.ln_a) + col0 + 16 * j);
-            bias4[j] = p.bias ? t_ : (f32x4){0.f, 0.f, 0.f, 0.f};
+            const f32x4 t_ = *reinterpret_cast<const f32x4*>((p.resid ? p.resid + (int64_t)rowc * p.ldr : reinterpret_cast<const float*>(p.C) + (int64_t)rowc * p.ldc) + col0 + 16 * j);
+            res[j] = p.resid ? t_ : (f32x4){0.f, 0.f, 0.f, 0.f};
         }
-        float s[4], q[4];
+        float si = 0.f;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = row0 + 16 * i, rowc = min(row, p.M - 1);
-            const uint64_t drow = (p.drop_p > 0.f && p.drop_rows) ? (uint64_t)p.drop_rows[rowc] : (uint64_t)rowc;
-            f32x4 res[8];
+        for (int j = 0; j < 8; ++j) {
+            bool kp[4] = {true, true, true, true};
+            if (p.drop_p > 0.f)
+                ortk_keep4(p.drop_seed, (drow * (uint64_t)drs + (uint64_t)p.drop_row_off) * (uint64_t)RP_N + (col0 + 16 * j), p.drop_p, kp);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const f32x4 t_ = *reinterpret_cast<const f32x4*>((p.resid ? p.resid + (int64_t)rowc * p.ldr : reinterpret_cast<const float*>(p.C) + (int64_t)rowc * p.ldc) + col0 + 16 * j);
-                res[j] = p.resid ? t_ : (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int r = 0; r < 4; ++r) {
+                float x = acc[i][j][r] + bias4[j][r];
+                if (p.drop_p > 0.f) x = kp[r] ? x * inv_keep : 0.f;
+                x += res[j][r];
+                acc[i][j][r] = x;
+                si += x;
             }
-            float si = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                bool kp[4] = {true, true, true, true};
-                if (p.drop_p > 0.f)
-                    ortk_keep4(p.drop_seed, (drow * (uint64_t)drs + (uint64_t)p.drop_row_off) * (uint64_t)RP_N + (col0 + 16 * j), p.drop_p, kp);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float x = acc[i][j][r] + bias4[j][r];
-                    if (p.drop_p > 0.f) x = kp[r] ? x * inv_keep : 0.f;
-                    x += res[j][r];
-                    acc[i][j][r] = x;
-                    si += x;
-                }
-                if (row < p.M) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)row * p.ldc + col0 + 16 * j) = acc[i][j];
-            }
-            s[i] = si;
+            if (row < p.M) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)row * p.ldc + col0 + 16 * j) = acc[i][j];
         }
-        row_total(s, red0);
+        s[i] = si;
+    }
+    row_total(s, red0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        s[i] *= (1.f / RP_N);                      // mean
+        float qi = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { const float t_ = acc[i][j][r] - s[i]; qi += t_ * t_; }
+        q[i] = qi;
+    }
+    row_total(q, red1);
+    float rinv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float sd = sqrtf(q[i] / (float)(RP_N - 1));
+        rinv[i] = 1.f / (sd + p.ln_eps);
+        const int row = row0 + 16 * i;
+        if (p.ln_stats && wn == 0 && lg == 0 && row < p.M) { p.ln_stats[(int64_t)row * 2] = s[i]; p.ln_stats[(int64_t)row * 2 + 1] = sd; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const f32x4 ga = *reinterpret_cast<const f32x4*>(p.ln_a + col0 + 16 * j);
+        const f32x4 gb = *reinterpret_cast<const f32x4*>(p.ln_b + col0 + 16 * j);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            s[i] *= (1.f / RP_N);                      // mean
-            float qi = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { const float t_ = acc[i][j][r] - s[i]; qi += t_ * t_; }
-            q[i] = qi;
-        }
-        row_total(q, red1);
-        float rinv[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float sd = sqrtf(q[i] / (float)(RP_N - 1));
-            rinv[i] = 1.f / (sd + p.ln_eps);
             const int row = row0 + 16 * i;
-            if (p.ln_stats && wn == 0 && lg == 0 && row < p.M) { p.ln_stats[(int64_t)row * 2] = s[i]; p.ln_stats[(int64_t)row * 2 + 1] = sd; }
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const f32x4 ga = *reinterpret_cast<const f32x4*>(p.ln_a + col0 + 16 * j);
-            const f32x4 gb = *reinterpret_cast<const f32x4*>(p.ln_b + col0 + 16 * j);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = row0 + 16 * i;
-                if (row >= p.M) continue;
-                float4 o;
-                o.x = ga[0] * (acc[i][j][0] - s[i]) * rinv[i] + gb[0];
-                o.y = ga[1] * (acc[i][j][1] - s[i]) * rinv[i] + gb[1];
-                o.z = ga[2] * (acc[i][j][2] - s[i]) * rinv[i] + gb[2];
-                o.w = ga[3] * (acc[i][j][3] - s[i]) * rinv[i] + gb[3];
-                st_elem4(p.ln_y, (int64_t)row * RP_N + col0 + 16 * j, p.ln_y_dtype, o);
-            }
-        }
-    } else {
-        // dy = acc.  With xc = x - mean, rr = 1 / (sd + eps), g = dy * a:  dx = rr (g - mean(g)) - rr^2 sum(g xc) xc / (511 sd) + dres;
-        // da += sum_rows dy xc rr, db += sum_rows dy  (ortk_norm.hip: ln_bwd_kernel, the same formulas)
-        float mean[4], sd[4], rr[4], vf[4], sg[4], sgx[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int rowc = min(row0 + 16 * i, p.M - 1);
-            mean[i] = p.ln_stats[(int64_t)rowc * 2]; sd[i] = p.ln_stats[(int64_t)rowc * 2 + 1];
-            rr[i] = 1.f / (sd[i] + p.ln_eps);
-            vf[i] = row0 + 16 * i < p.M ? 1.f : 0.f;
-        }
-        // four partial row sums per row (one per r): the same shape as the packed column sums, so that the compiler's pairing
-        // of the r's does not leave a scalar chain behind that keeps every product alive (148 spilled registers)
-        f32x4 sg4[4], sgx4[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { sg4[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; sgx4[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        // pass 1, two column tiles at a time: row sums of g and g xc (g replaces dy in the accumulators), column sums of the
-        // parameter gradients over the lane's 4 rows, then over the 16 rows of the wave's lane row by DPP
-#pragma unroll
-        for (int jp = 0; jp < 4; ++jp) {
-            f32x4 xv[4][2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj)
-                    xv[i][jj] = *reinterpret_cast<const f32x4*>(p.ln_x + (int64_t)min(row0 + 16 * i, p.M - 1) * RP_N + col0 + 16 * (2 * jp + jj));
-#pragma unroll
-            for (int jj = 0; jj < 2; ++jj) {
-                const int j = 2 * jp + jj;
-                const f32x4 ga = *reinterpret_cast<const f32x4*>(p.ln_a + col0 + 16 * j);
-                float pa[4] = {0.f, 0.f, 0.f, 0.f}, pb[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        // (rows past M only have to stay out of the column sums: vf = 0; their own results are never stored)
-                        const float dyv = acc[i][j][r];
-                        const float t_ = dyv * (xv[i][jj][r] - mean[i]);        // dy xc
-                        pa[r] += t_ * (rr[i] * vf[i]); pb[r] += dyv * vf[i];
-                        const float g = dyv * ga[r];
-                        acc[i][j][r] = g; sg4[i][r] += g; sgx4[i][r] += t_ * ga[r];
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { pa[r] = row16_sum(pa[r]); pb[r] = row16_sum(pb[r]); }
-                if (lr == 0) {
-                    *reinterpret_cast<f32x4*>(colr + wm * RP_N + col0 + 16 * j) = (f32x4){pa[0], pa[1], pa[2], pa[3]};
-                    *reinterpret_cast<f32x4*>(colr + 2 * RP_N + wm * RP_N + col0 + 16 * j) = (f32x4){pb[0], pb[1], pb[2], pb[3]};
-                }
-            }
-            // keep the batches apart: hoisting all 32 row loads of the pass to its top costs 131 spilled registers
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            sg[i] = (sg4[i][0] + sg4[i][1]) + (sg4[i][2] + sg4[i][3]);
-            sgx[i] = (sgx4[i][0] + sgx4[i][1]) + (sgx4[i][2] + sgx4[i][3]);
-        }
-        row_total(sg, red0);
-        row_total(sgx, red1);          // (its barrier also publishes the column sums)
-        {
-            atomicAdd(p.ln_da + tid_e, colr[tid_e] + colr[RP_N + tid_e]);
-            atomicAdd(p.ln_db + tid_e, colr[2 * RP_N + tid_e] + colr[3 * RP_N + tid_e]);
-        }
-        const float ik = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = row0 + 16 * i, rowc = min(row, p.M - 1);
-            const float mg = sg[i] * (1.f / RP_N);
-            const float coef = rr[i] * rr[i] * sgx[i] / ((float)(RP_N - 1) * sd[i]);
-            f32x4 xv[8], dr[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                xv[j] = *reinterpret_cast<const f32x4*>(p.ln_x + (int64_t)rowc * RP_N + col0 + 16 * j);
-                const f32x4 t_ = *reinterpret_cast<const f32x4*>((p.ln_dres ? p.ln_dres : p.ln_x) + (int64_t)rowc * RP_N + col0 + 16 * j);
-                dr[j] = p.ln_dres ? t_ : (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-            if (row < p.M)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                f32x4 o;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = rr[i] * (acc[i][j][r] - mg) - coef * (xv[j][r] - mean[i]) + dr[j][r];
-                const int64_t i0 = (int64_t)row * RP_N + col0 + 16 * j;
-                *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + i0) = o;
-                if (p.ln_y) {
-                    bool kp[4] = {true, true, true, true};
-                    if (p.drop_p > 0.f) ortk_keep4(p.drop_seed, p.drop_rows ? (uint64_t)p.drop_rows[row] * RP_N + (uint64_t)(col0 + 16 * j) : (uint64_t)i0, p.drop_p, kp);
-                    st_elem4(p.ln_y, i0, p.ln_y_dtype, make_float4(kp[0] ? o[0] * ik : 0.f, kp[1] ? o[1] * ik : 0.f, kp[2] ? o[2] * ik : 0.f, kp[3] ? o[3] * ik : 0.f));
-                }
-            }
-            asm volatile("" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
+            if (row >= p.M) continue;
+            float4 o;
+            o.x = ga[0] * (acc[i][j][0] - s[i]) * rinv[i] + gb[0];
+            o.y = ga[1] * (acc[i][j][1] - s[i]) * rinv[i] + gb[1];
+            o.z = ga[2] * (acc[i][j][2] - s[i]) * rinv[i] + gb[2];
+            o.w = ga[3] * (acc[i][j][3] - s[i]) * rinv[i] + gb[3];
+            st_elem4(p.ln_y, (int64_t)row * RP_N + col0 + 16 * j, p.ln_y_dtype, o);
         }
     }
 }
@@ -1443,7 +1287,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args
 // ------------------------------------------------------------------------------------------------
 // Data-gradient product + LayerNorm backward on SHORT row panels (ln_mode = 2, round 6): (16 MT rows) x 512 columns per workgroup,
 // MT = 2 .. 5 chosen so that the grid is about one workgroup per compute unit (16 640 rows -> 80-row panels, 208 workgroups;
-// 9 216 -> 48-row panels, 192).  The 128-row form above owns whole rows as well, but its 130 workgroups moved the epilogue's
+// 9 216 -> 48-row panels, 192).  A 128-row form (round 3, removed) owned whole rows as well, but its 130 workgroups moved the epilogue's
 // 0.6-1.1 MB each through half of the chip's load/store paths and lost to the separate kernels (section 7c of DESIGN.md); here
 // every unit streams its share of x / dres / dx / dz, the LayerNorm input stays in registers between the two passes (the small
 // accumulator tile leaves room), and the weight panel — 512 KB, re-read by every workgroup — comes out of L2 in two 64-column stages
@@ -1453,6 +1297,17 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_row512_kernel(ortk_gemm_args
 constexpr int LB_BK = 64, LB_N = 512;
 constexpr int LB_IMG_B = LB_N * LB_BK;                          // bf16 elements of a weight stage (64 KB)
 template <int MT> constexpr size_t lb_lds_bytes() { return (size_t)2 * (LB_IMG_B + 16 * MT * LB_BK) * sizeof(__bf16); }
+
+// sum over the 16 lanes of a DPP row (the lanes that hold the same columns of 16 different rows); every lane gets the total
+__device__ __forceinline__ float row16_sum(float v) {
+#define ORTK_DPP_ADD(ctrl) v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, 0xF, 0xF, true))
+    ORTK_DPP_ADD(0xB1);     // quad_perm [1,0,3,2]
+    ORTK_DPP_ADD(0x4E);     // quad_perm [2,3,0,1]
+    ORTK_DPP_ADD(0x141);    // row_half_mirror: the other quad of the half row
+    ORTK_DPP_ADD(0x140);    // row_mirror: the other half row
+#undef ORTK_DPP_ADD
+    return v;
+}
 
 template <int MT>
 __global__ __launch_bounds__(512, 1) void gemm_bf16_rowln_bwd_kernel(ortk_gemm_args p) {
@@ -1499,9 +1354,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_rowln_bwd_kernel(ortk_gemm_a
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[MT], b[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) b[j] = gfrag64<false>(sB, wave * 64 + 16 * j, ks, lane);
+            for (int j = 0; j < 4; ++j) b[j] = gfrag64(sB, wave * 64 + 16 * j, ks, lane);
 #pragma unroll
-            for (int i = 0; i < MT; ++i) a[i] = gfrag64<false>(sA, 16 * i, ks, lane);
+            for (int i = 0; i < MT; ++i) a[i] = gfrag64(sA, 16 * i, ks, lane);
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 if (next) {
@@ -1607,11 +1462,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_rowln_bwd_kernel(ortk_gemm_a
         }
     }
 }
-template <int MT> static int launch_rowln_bwd(const ortk_gemm_args& p, hipStream_t s) {
-    if (ortk::lds_attr(reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<MT>), lb_lds_bytes<MT>())) return ORTK_EINVAL;
-    hipLaunchKernelGGL(gemm_bf16_rowln_bwd_kernel<MT>, dim3((unsigned)ortk_cdiv(p.M, 16 * MT)), dim3(512), lb_lds_bytes<MT>(), s, p);
-    return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // 64 x 64 tile, 64-column K-steps, forward layout only, for SHORT grids: the decode-time projections (rows = images x
@@ -1689,9 +1539,9 @@ __global__ __launch_bounds__(256, NS > 4 ? 1 : NS == 4 ? 2 : 3) void gemm_bf16_d
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 a[2], b[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) b[j] = gfrag64<false>(sB, wn * 32 + 16 * j, ks, lane);
+            for (int j = 0; j < 2; ++j) b[j] = gfrag64(sB, wn * 32 + 16 * j, ks, lane);
 #pragma unroll
-            for (int i = 0; i < 2; ++i) a[i] = gfrag64<false>(sA, wm * 32 + 16 * i, ks, lane);
+            for (int i = 0; i < 2; ++i) a[i] = gfrag64(sA, wm * 32 + 16 * i, ks, lane);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2020,14 +1870,6 @@ __global__ __launch_bounds__(64 * GM * GN, MINB) void gemm_f32x3p_kernel(ortk_ge
           p.relu, p.drop_p, p.drop_seed, 0, true, p.M, p.N, p.drop_row_stride > 0 ? p.drop_row_stride : 1, p.drop_row_off, p.drop_rows};
     epilogue_tile<false, WM, 4 * WN, 32, 8>(e, mb + wm * 32 * WM + l32, nb + wn * 32 * WN + 4 * lh, acc4);
 }
-template <int WM, int WN, int GM, int GN, int MINB>
-int launch_f32x3p(const ortk_gemm_args& p, hipStream_t s) {
-    constexpr size_t lds = (size_t)2 * 3 * (32 * WM * GM + 32 * WN * GN) * 32 * sizeof(__bf16);
-    ortk::lds_attr(reinterpret_cast<const void*>(gemm_f32x3p_kernel<WM, WN, GM, GN, MINB>), lds);
-    const int tm = (int)ortk_cdiv(p.M, 32 * WM * GM), tn = (int)ortk_cdiv(p.N, 32 * WN * GN);
-    hipLaunchKernelGGL((gemm_f32x3p_kernel<WM, WN, GM, GN, MINB>), dim3((unsigned)(tm * tn)), dim3(64 * GM * GN), lds, s, p, tm, tn, 0);
-    return 0;
-}
 
 // The transposed-operand layouts of the same split product (fp32 parity mode: data gradients dX = dY W with W stored (K, N), weight
 // gradients dW = dY^T X with both operands stored k-major and K = the batch's rows split over workgroups that accumulate with
@@ -2202,121 +2044,69 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void gemm_f32x3t_kernel(ortk_gemm
     epilogue_tile<false, 2, 8, 32, 8>(e, mb + wm * 64 + l32, nb + wn * 64 + 4 * lh, acc4);
 }
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------ profiling hook
-// Opt-in, measurement only (bench.py's roofline leg): HIP events around every GEMM launch on the launch stream,
-// accumulated per kernel instance (precision, transA, transB).  Disabled by default; the timed region of bench.py
-// never runs with it on.  This is the only process-global state in the library.
-namespace {
-struct ProfRec { hipEvent_t a, b; int key; double flops, bytes; int slot; double per_count; double units; };
-constexpr int PROF_SLOTS = 1 << 16;
-unsigned long long* g_prof_slots = nullptr;      // device counters (ortk::prof_slot)
-int g_prof_slot_next = 0;
-bool g_prof_on = false;
-bool g_prof_serial = false;    // level 1: the executor keeps every launch on the caller's stream (kernels timed in isolation)
-std::mutex g_prof_mu;          // decode chunks may be driven by several host threads
-std::vector<ProfRec>* g_prof = nullptr;
-}  // namespace
-
-namespace ortk {
-// hipFuncAttributeMaxDynamicSharedMemorySize is a property of (device, function): set once per pair, from any host thread
-// (a process-wide `static bool` per call site left the second device of a process without it, and raced)
-int lds_attr(const void* fn, size_t bytes) {
-    struct Key { int dev; const void* fn; size_t bytes; };
-    static std::mutex mu;
-    static std::vector<Key>* seen = new std::vector<Key>();
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return ORTK_EINVAL;
-    std::lock_guard<std::mutex> lk(mu);
-    for (const Key& k : *seen) if (k.dev == dev && k.fn == fn && k.bytes >= bytes) return 0;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return ORTK_EINVAL;
-    seen->push_back(Key{dev, fn, bytes});
-    return 0;
-}
-bool ortk_prof_active() { return g_prof_on; }
-bool ortk_prof_serial() { return g_prof_serial; }
-// the same hook for launches that are not ortk_gemm (key >= 16): begin records the first event, end the second
-bool prof_begin(int key, double flops, double bytes, hipStream_t s, ProfMark& m) {
-    m.live = false;
-    if (!g_prof_on) return false;
-    if (hipEventCreate(&m.a) != hipSuccess || hipEventCreate(&m.b) != hipSuccess) return false;
-    m.key = key; m.flops = flops; m.bytes = bytes; m.live = true;
-    (void)hipEventRecord(m.a, s);
-    return true;
-}
-void prof_end(const ProfMark& m, hipStream_t s) {
-    if (!m.live) return;
-    (void)hipEventRecord(m.b, s);
-    ProfRec rec{m.a, m.b, m.key, m.flops, m.bytes, m.slot, m.per_count, m.units};
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof->push_back(rec);
-}
-unsigned long long* prof_slot(int* index) {
-    if (index) *index = -1;
-    if (!g_prof_on || !g_prof_slots || !index) return nullptr;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (g_prof_slot_next >= PROF_SLOTS) return nullptr;
-    *index = g_prof_slot_next++;
-    return g_prof_slots + *index;
-}
-}  // namespace ortk
-
-extern "C" int ortk_prof_enable(int32_t on) {
-    if (!g_prof) g_prof = new std::vector<ProfRec>();
-    for (auto& r : *g_prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    g_prof->clear();
-    if (on && !g_prof_slots && hipMalloc(reinterpret_cast<void**>(&g_prof_slots), PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess) g_prof_slots = nullptr;
-    if (on && g_prof_slots && hipMemset(g_prof_slots, 0, PROF_SLOTS * sizeof(unsigned long long)) != hipSuccess) return ORTK_EINVAL;
-    g_prof_slot_next = 0;
-    g_prof_on = on != 0;
-    g_prof_serial = on == 1;
-    return 0;
-}
-// key = precision*4 + transA*2 + transB.  Waits for the recorded events (host sync: measurement only).
-extern "C" int ortk_prof_collect(int32_t key, int64_t* launches, double* total_ms, double* total_flops) {
-    if (!g_prof || !launches || !total_ms || !total_flops) return ORTK_EINVAL;
-    *launches = 0; *total_ms = 0; *total_flops = 0;
-    for (auto& r : *g_prof) {
-        if (r.key != key) continue;
-        if (hipEventSynchronize(r.b) != hipSuccess) return ORTK_EINVAL;
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, r.a, r.b) != hipSuccess) return ORTK_EINVAL;
-        *launches += 1; *total_ms += ms; *total_flops += r.flops;
+// ------------------------------------------------------------------------------------------------ host side: validate -> plan -> launch
+// A plan is what the launch tail needs and nothing else.  Every kernel of this file but the short-panel one takes
+// (ortk_gemm_args, int, int, int); the tail hands all four to hipLaunchKernel, which reads as many as the kernel has parameters.
+struct Launch { const void* fn; unsigned grid, block; size_t lds; int a0, a1, a2; };
+struct Plan {
+    Launch l[2]; int n = 0;      // the second launch: the 128-column remainder of a 256 n + 128 column count (plan_dma)
+    int key = 0; double bytes = 0.0;   // profiling: precision * 4 + transA * 2 + transB; algorithmic bytes
+    void add(gemm16_fn fn, int64_t grid, int block, size_t lds, int a0, int a1, int a2) {
+        l[n++] = Launch{reinterpret_cast<const void*>(fn), (unsigned)grid, (unsigned)block, lds, a0, a1, a2};
     }
-    return 0;
-}
+};
+// 128 x 128 output tiles and the K range of a workgroup (split-K only when accumulating)
+struct Tiling { int tilesM, tilesN, splitk, kchunk; int64_t grid() const { return (int64_t)tilesM * tilesN * splitk; } };
 
-// sum over the launches of `key` of the workgroups each one started (recorded by the launchers that size their grids themselves:
-// the grouped weight gradients) — launches / this = the average share of the chip such a launch holds
-extern "C" int ortk_prof_collect_units(int32_t key, double* total_workgroups) {
-    if (!g_prof || !total_workgroups) return ORTK_EINVAL;
-    *total_workgroups = 0;
-    for (auto& r : *g_prof) if (r.key == key) *total_workgroups += r.units;
-    return 0;
-}
+bool al(const void* q, size_t a_) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) % a_) == 0; }
+int layout_key(const ortk_gemm_args& p) { return (p.precision ? 4 : 0) | (p.transA ? 2 : 0) | (p.transB ? 1 : 0); }
 
-extern "C" int ortk_prof_collect_bytes(int32_t key, double* total_bytes) {
-    if (!g_prof || !total_bytes) return ORTK_EINVAL;
-    *total_bytes = 0;
-    // (the counters of the slots: the caller has synchronised — ortk_prof_collect waits for every event — and this copy waits as well)
-    std::vector<unsigned long long> slots;
-    if (g_prof_slots && g_prof_slot_next > 0) {
-        slots.resize((size_t)g_prof_slot_next);
-        if (hipMemcpy(slots.data(), g_prof_slots, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return ORTK_EINVAL;
+Tiling gemm_tiling(const ortk_gemm_args& p) {
+    Tiling t{(int)ortk_cdiv(p.M, BM), (int)ortk_cdiv(p.N, BN), 1, 0};
+    // (fp32 transposed layouts on the split kernels consume K 32 at a time: K-split chunks are made multiples of 32 for them)
+    const int bk = p.precision ? BK16 : (ortk::tuning().f32_split && (p.transA || p.transB)) ? 32 : 16;
+    t.splitk = p.accumulate ? (p.splitk > 0 ? p.splitk : 1) : 1;
+    t.kchunk = bk;
+    if (p.K <= 0) {
+        t.splitk = 1;  // empty reduction: C = epilogue(0), bias / residual still applied
+    } else {
+        const int ksteps = (int)ortk_cdiv(p.K, bk);
+        if (t.splitk > ksteps) t.splitk = ksteps;
+        t.kchunk = (int)ortk_cdiv(ksteps, t.splitk) * bk;
+        t.splitk = (int)ortk_cdiv(p.K, t.kchunk);
     }
-    for (auto& r : *g_prof) {
-        if (r.key != key) continue;
-        *total_bytes += r.bytes;
-        if (r.slot >= 0 && (size_t)r.slot < slots.size()) *total_bytes += r.per_count * (double)slots[(size_t)r.slot];
-    }
-    return 0;
+    return t;
 }
 
-extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
-    if (!a || !a->A || !a->B || !a->C || a->M < 0 || a->N < 0 || a->K < 0) return ORTK_EINVAL;
-    if (a->M == 0 || a->N == 0) return 0;
-    ortk_gemm_args p = *a;
+// everything the unguarded bf16-MFMA kernels assume, except the row count: full column / K tiles and vector alignment
+bool bf16_fast_nk(const ortk_gemm_args& p, const Tiling& t) {
+    const size_t ea = ortk_esize(p.a_dtype), eb = ortk_esize(p.b_dtype), ec = ortk_esize(p.c_dtype), eg = ortk_esize(p.gate_dtype);
+    return p.N % BN == 0 && p.K > 0 && p.K % BK16 == 0 && t.kchunk % BK16 == 0 &&
+           al(p.A, 16) && al(p.B, 16) && (p.lda * ea) % 16 == 0 && (p.ldb * eb) % 16 == 0 &&
+           al(p.C, 4 * ec) && (p.ldc % 4) == 0 && al(p.bias, 16) && al(p.resid, 16) && (p.ldr % 4) == 0 &&
+           al(p.gate, 4 * eg) && (p.ldg % 4) == 0;
+}
+// The forward-layout LDS-DMA kernels also take a RAGGED row count (M = images x regions, captions x positions, images x
+// beams: whatever the batch is): the operand rows of the partial last row tile are clamped to M - 1 and only that tile
+// runs the bounds-checked epilogue.  (Without this every batch size that is not a multiple of 128 images fell back to
+// the guarded register-staged kernel: 13.4 ms per XE step at 127 images against 9.0 ms at 128.)
+bool bf16_fast4(const ortk_gemm_args& p, const Tiling& t) { return bf16_fast_nk(p, t) && layout_key(p) == 4 && !p.accumulate; }
+bool both_bf16(const ortk_gemm_args& p) { return p.a_dtype == ORTK_BF16 && p.b_dtype == ORTK_BF16; }
+
+// Does a fused-LayerNorm kernel serve the call?  (ln_mode 1: the 128-row panel kernel; 2: the short-panel kernel, whose 32-bit
+// operand offsets also bound the matrices.)  Otherwise ortk_gemm runs the separate kernels.
+bool ln_fused(const ortk_gemm_args& p) {
+    const bool fused = p.precision && !p.transB && both_bf16(p) && p.N == RP_N && p.K > 0 &&
+                       p.K % HBK == 0 && !p.relu && al(p.A, 16) && al(p.B, 16) && (p.lda % 8) == 0 && (p.ldb % 8) == 0 && al(p.C, 16) &&
+                       al(p.bias, 16) && al(p.resid, 16) && (p.ldr % 4) == 0 && al(p.ln_a, 16) && al(p.ln_b, 16) && al(p.ln_y, 16) &&
+                       al(p.ln_x, 16) && al(p.ln_dres, 16);
+    if (p.ln_mode == 1) return fused;
+    static_assert(LB_BK == HBK && LB_N == RP_N, "one shape test for both fused-LayerNorm kernels");
+    return fused && p.lda < (1 << 30) / 2 && p.ldb < (1 << 30) / 2 && (int64_t)p.M * p.lda < (1ll << 30);
+}
+
+// Every argument check of ortk_gemm, before anything is created or launched.
+int gemm_validate(const ortk_gemm_args& p) {
     auto dt_ok = [](int d) { return d == ORTK_F32 || d == ORTK_BF16; };
     if (!dt_ok(p.a_dtype) || !dt_ok(p.b_dtype) || !dt_ok(p.c_dtype) || !dt_ok(p.gate_dtype)) return ORTK_EINVAL;
     if (!p.precision && (p.a_dtype || p.b_dtype)) return ORTK_EINVAL;   // fp32 MFMA path takes fp32 operands only
@@ -2329,251 +2119,231 @@ extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
             p.N < 2 || p.N > 2048 || !p.ln_a || !p.ln_stats) return ORTK_EINVAL;
         if (p.ln_mode == 1 && (!p.ln_b || !p.ln_y)) return ORTK_EINVAL;
         if (p.ln_mode == 2 && (!p.ln_x || !p.ln_da || !p.ln_db || p.bias || p.resid || p.relu)) return ORTK_EINVAL;
-        auto al = [](const void* q, size_t a_) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) % a_) == 0; };
-        const bool fused = p.precision && !p.transB && p.a_dtype == ORTK_BF16 && p.b_dtype == ORTK_BF16 && p.N == RP_N && p.K > 0 &&
-                           p.K % HBK == 0 && !p.relu && al(p.A, 16) && al(p.B, 16) && (p.lda % 8) == 0 && (p.ldb % 8) == 0 && al(p.C, 16) &&
-                           al(p.bias, 16) && al(p.resid, 16) && (p.ldr % 4) == 0 && al(p.ln_a, 16) && al(p.ln_b, 16) && al(p.ln_y, 16) &&
-                           al(p.ln_x, 16) && al(p.ln_dres, 16);
-        if (!fused) {
-            // any other shape / precision: the same result from the separate kernels
-            ortk_gemm_args q = p; q.ln_mode = 0;
-            if (p.ln_mode == 2) q.drop_p = 0.f;
-            if (int e = ortk_gemm(&q, stream)) return e;
-            float* Cf = reinterpret_cast<float*>(p.C);
-            if (p.ln_mode == 1) return ortk_layernorm_fwd(Cf, p.ln_a, p.ln_b, p.ln_y, p.ln_y_dtype, p.ln_stats, p.M, p.N, p.ln_eps, stream);
-            return ortk_layernorm_bwd_drop_rows(Cf, p.ln_x, p.ln_a, p.ln_stats, p.ln_dres, Cf, p.ln_da, p.ln_db, p.M, p.N, p.ln_eps,
-                                                p.ln_y, p.ln_y_dtype, p.drop_p, p.drop_seed, p.drop_rows, stream);
-        }
-        if (p.ln_mode == 2 && p.K % LB_BK == 0 && p.lda < (1 << 30) / 2 && p.ldb < (1 << 30) / 2 && (int64_t)p.M * p.lda < (1ll << 30) && !(ortk::tuning().ln_fuse & 2)) {
-            // short row panels, about one workgroup per compute unit
-            const int mt = (int)std::min<int64_t>(5, std::max<int64_t>(2, ortk_cdiv(p.M, 16 * 256)));      // (96-row panels spill)
-            hipStream_t s = ortk_s(stream);
-            ProfRec rec{};
-            if (g_prof_on) {
-                if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess) return ORTK_EINVAL;
-                rec.key = 4; rec.flops = 2.0 * p.M * p.N * p.K;
-                rec.bytes = (double)p.M * p.K * 2 + (double)p.N * p.K * 2 + (double)p.M * p.N * (4 + 4 + 4 + 2);
-                (void)hipEventRecord(rec.a, s);
-            }
-            int e = 0;
-            switch (mt) {
-                case 2: e = launch_rowln_bwd<2>(p, s); break;
-                case 3: e = launch_rowln_bwd<3>(p, s); break;
-                case 4: e = launch_rowln_bwd<4>(p, s); break;
-                default: e = launch_rowln_bwd<5>(p, s); break;
-            }
-            if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-            if (e) return e;
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
-        gemm16_fn g = p.ln_mode == 1 ? gemm_bf16_row512_kernel<1> : gemm_bf16_row512_kernel<2>;
-        ortk::lds_attr(reinterpret_cast<const void*>(g), RP_LDS_BYTES);
-        hipStream_t s = ortk_s(stream);
-        ProfRec rec{};
-        if (g_prof_on) {
-            if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess) return ORTK_EINVAL;
-            rec.key = 4; rec.flops = 2.0 * p.M * p.N * p.K;
-            rec.bytes = (double)p.M * p.K * 2 + (double)p.N * p.K * 2 + (double)p.M * p.N * (4 + 4 + 2 + (p.ln_mode == 2 ? 8 : 0));
-            (void)hipEventRecord(rec.a, s);
-        }
-        hipLaunchKernelGGL(g, dim3((unsigned)ortk_cdiv(p.M, RP_M)), dim3(512), RP_LDS_BYTES, s, p, 0, 0, 0);
-        if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-        ORTK_CHECK_LAUNCH();
-        return 0;
+        return 0;      // (the fused kernels read no statistics arguments; the separate-kernels form comes back here with ln_mode = 0)
     }
-    const int tilesM = (int)ortk_cdiv(p.M, BM), tilesN = (int)ortk_cdiv(p.N, BN);
-    // (fp32 transposed layouts on the split kernels consume K 32 at a time: K-split chunks are made multiples of 32 for them)
-    const int bk = p.precision ? BK16 : (ortk::tuning().f32_split && (p.transA || p.transB)) ? 32 : 16;
-    int splitk = p.accumulate ? (p.splitk > 0 ? p.splitk : 1) : 1;
-    int kchunk = bk;
-    if (p.K <= 0) {
-        splitk = 1;  // empty reduction: C = epilogue(0), bias / residual still applied
-    } else {
-        const int ksteps = (int)ortk_cdiv(p.K, bk);
-        if (splitk > ksteps) splitk = ksteps;
-        kchunk = (int)ortk_cdiv(ksteps, splitk) * bk;
-        splitk = (int)ortk_cdiv(p.K, kchunk);
-    }
-    dim3 grid((unsigned)(tilesM * tilesN * splitk)), block(256);
-    hipStream_t s = ortk_s(stream);
-    const int key = (p.precision ? 4 : 0) | (p.transA ? 2 : 0) | (p.transB ? 1 : 0);
-    ProfRec rec{};
-    if (g_prof_on) {
-        if (hipEventCreate(&rec.a) != hipSuccess || hipEventCreate(&rec.b) != hipSuccess) return ORTK_EINVAL;
-        rec.key = key; rec.flops = 2.0 * p.M * p.N * p.K;
-        rec.bytes = (double)p.M * p.K * ortk_esize(p.a_dtype) + (double)p.N * p.K * ortk_esize(p.b_dtype) +
-                    (double)p.M * p.N * (ortk_esize(p.c_dtype) + (p.resid ? 4 : 0) + (p.gate ? ortk_esize(p.gate_dtype) : 0));
-        (void)hipEventRecord(rec.a, s);
-    }
-    if (!p.precision) {
-        if (p.tile_stats || p.tile_samp) return ORTK_EINVAL;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        if (key == 0 && ortk::tuning().f32_split && !p.accumulate && p.K > 0 && p.K % 32 == 0 && (p.lda & 3) == 0 && (p.ldb & 3) == 0 &&
-            al16(p.A) && al16(p.B)) {
-            // three-way bf16 split on the bf16 matrix cores (gemm_f32x3_kernel); tile size by how many workgroups it gives the chip
-            // Instance by how the grid fills the 256 compute units (measured on the shapes of the fp32 parity decode:
-            // scratch/f32x3_bench.py, profiles/r05_f32_split_gemm.txt): the 256 x 128 pipelined tile wherever its grid fills at least
-            // 3/4 of its last round of workgroups; short grids (at most 1.25 workgroups of 128 x 128 per unit) the 64 x 64 pipelined
-            // tile; in between 128 x 64, three workgroups per unit.
-            const int64_t t128 = (int64_t)tilesM * tilesN, big = ortk_cdiv(p.M, 256) * (int64_t)tilesN;
-            const int force = ortk::tuning().f32_split;     // 1 automatic | 2..7 a fixed kernel instance
-            const int shape = force > 1 ? force : big * 4 >= ortk_cdiv(big, 256) * 256 * 3 ? 7 : t128 < 320 ? 5 : 3;
-#define ORTK_X3(WM_, WN_, GM_, GN_, MB_) do { const int tm = (int)ortk_cdiv(p.M, 32 * WM_ * GM_), tn = (int)ortk_cdiv(p.N, 32 * WN_ * GN_); \
-            hipLaunchKernelGGL((gemm_f32x3_kernel<WM_, WN_, GM_, GN_, MB_>), dim3((unsigned)(tm * tn)), dim3(64 * GM_ * GN_), 0, s, p, tm, tn, 0); } while (0)
-            switch (shape) {
-                case 2:  ORTK_X3(1, 1, 2, 2, 2); break;               // single-buffered: 64 x 64 (24 KB)
-                case 3:  ORTK_X3(2, 1, 2, 2, 3); break;               //                  128 x 64 (36 KB), three workgroups per unit
-                case 4:  ORTK_X3(2, 2, 2, 2, 3); break;               //                  128 x 128 (48 KB), three
-                case 5:  launch_f32x3p<1, 1, 2, 2, 3>(p, s); break;   // pipelined:       64 x 64 (48 KB)
-                case 6:  launch_f32x3p<2, 1, 2, 2, 2>(p, s); break;   //                  128 x 64 (72 KB)
-                default: launch_f32x3p<2, 2, 4, 2, 1>(p, s); break;   //                  256 x 128, 8 waves (144 KB)
-            }
-#undef ORTK_X3
-            if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
-        // transposed-operand layouts of the split product (gemm_f32x3t_kernel): dgrad without accumulation, wgrad with or without
-        if (key != 0 && ortk::tuning().f32_split && p.K > 0 && (p.ldb & 3) == 0 && al16(p.B) && (p.N & 3) == 0 && p.N >= 4 && kchunk % 32 == 0 &&
-            (key == 1 ? !p.accumulate && p.K % 32 == 0 && (p.lda & 3) == 0 && al16(p.A)
-                      : (p.lda & 3) == 0 && al16(p.A) && (p.M & 3) == 0 && p.M >= 4)) {
-            typedef void (*x3t_fn)(ortk_gemm_args, int, int, int);
-            const x3t_fn fn = key == 1 ? gemm_f32x3t_kernel<false, false> : p.accumulate ? gemm_f32x3t_kernel<true, true> : gemm_f32x3t_kernel<true, false>;
-            const size_t lds = p.accumulate ? BF16_LDS_BYTES_C : (size_t)6 * 128 * 32 * sizeof(__bf16);
-            ortk::lds_attr(reinterpret_cast<const void*>(gemm_f32x3t_kernel<true, true>), BF16_LDS_BYTES_C);
-            hipLaunchKernelGGL(fn, grid, block, lds, s, p, tilesM, tilesN, kchunk);
-            if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
-        // (the fp32 MFMA kernel has no fused column sums: the same sums from their own launch)
-        if (p.colsum) { if (int e = ortk_colsum(p.A, ORTK_F32, p.lda, p.colsum, p.K, p.M, stream)) return e; }
-        switch (key) {
-            case 0: hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, block, 0, s, p, tilesM, tilesN, kchunk); break;
-            case 1: hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, block, 0, s, p, tilesM, tilesN, kchunk); break;
-            case 3: hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, block, 0, s, p, tilesM, tilesN, kchunk); break;
-            default: return ORTK_EINVAL;
-        }
-    } else {
-        auto al = [](const void* q, size_t a_) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) % a_) == 0; };
-        const size_t ea = ortk_esize(p.a_dtype), eb = ortk_esize(p.b_dtype), ec = ortk_esize(p.c_dtype), eg = ortk_esize(p.gate_dtype);
-        // everything the unguarded kernels assume, except the row count: full column / K tiles and vector alignment
-        const bool fast_nk = p.N % BN == 0 && p.K > 0 && p.K % BK16 == 0 && kchunk % BK16 == 0 &&
-                             al(p.A, 16) && al(p.B, 16) && (p.lda * ea) % 16 == 0 && (p.ldb * eb) % 16 == 0 &&
-                             al(p.C, 4 * ec) && (p.ldc % 4) == 0 && al(p.bias, 16) && al(p.resid, 16) && (p.ldr % 4) == 0 &&
-                             al(p.gate, 4 * eg) && (p.ldg % 4) == 0;
-        const bool fast = fast_nk && p.M % BM == 0;
-        // The forward-layout LDS-DMA kernels also take a RAGGED row count (M = images x regions, captions x positions, images x
-        // beams: whatever the batch is): the operand rows of the partial last row tile are clamped to M - 1 and only that tile
-        // runs the bounds-checked epilogue.  (Without this every batch size that is not a multiple of 128 images fell back to
-        // the guarded register-staged kernel: 13.4 ms per XE step at 127 images against 9.0 ms at 128.)
-        const bool fast4 = fast_nk && key == 4 && !p.accumulate;
-        if (p.tile_samp && !p.tile_stats) return ORTK_EINVAL;      // (the combine step needs the partials beside the candidates)
-        const bool want_stats = p.tile_stats != nullptr;      // soft-max partials (+ sampling candidates): the 128 x 128 LDS-DMA kernel's epilogue
-        if (want_stats && !(fast4 && p.a_dtype == ORTK_BF16 && p.b_dtype == ORTK_BF16 && kchunk % GBK == 0 && p.K % HBK == 0 && !p.relu &&
-                            p.drop_p == 0.f && !p.gate && !p.rowscale && !p.resid && p.stat_ncols > 0 && p.stat_ncols <= p.N))
+    // soft-max partials (+ sampling candidates): the 128 x 128 LDS-DMA kernel's epilogue and nothing else
+    if (!p.precision && (p.tile_stats || p.tile_samp)) return ORTK_EINVAL;
+    if (p.tile_samp && !p.tile_stats) return ORTK_EINVAL;      // (the combine step needs the partials beside the candidates)
+    if (p.tile_stats) {
+        const Tiling t = gemm_tiling(p);
+        if (!(bf16_fast4(p, t) && both_bf16(p) && t.kchunk % GBK == 0 && p.K % HBK == 0 && !p.relu &&
+              p.drop_p == 0.f && !p.gate && !p.rowscale && !p.resid && p.stat_ncols > 0 && p.stat_ncols <= p.N))
             return ORTK_EINVAL;
-        const int impl = ortk::tuning().gemm_impl;   // experiments: 1 = register-staged kernel only, 2 = 128^2 DMA tiles only, 3 = 256^2 whenever legal
-        // Measured in the XE step (bench.py, ms/step): register-staged kernel everywhere 17.9; DMA kernels everywhere
-        // 21.3 (the k-major layouts lose: dgrad 4.1 vs 3.3 ms, wgrad 4.1 vs 3.4 ms per step in isolation); the DMA kernels
-        // therefore serve the forward layout only unless ORTK_GEMM_IMPL >= 2 asks for them everywhere.
-        const bool dma_layout = key == 4 || impl >= 2;
-        // short forward grids (decode-time projections): 64 x 64 tiles
-        // Measured with bias + residual epilogues (scratch/gemm_t64.py, us, 128^2/256^2 kernels -> 64^2): 1536x512x512 16.4 -> 7.9,
-        // 1536x512x2048 33.3 -> 15.6, 5120x512x512 16.8 -> 10.5, 5120x512x2048 35.9 -> 23.4, 5120x2048x512 31.4 -> 29.1,
-        // 9216x512x512 23.3 -> 17.6; past ~640 big tiles or with the generator's N = 10240 the small tiles lose (5120x10240x512
-        // 163 -> 178, 21760x1536x512 87 -> 106).  Decode-sized row counts only (M <= 6 144): inside the training step, beside
-        // the side stream's weight gradients, the 9 216- and 16 640-row projections are faster on the big tiles (XE step
-        // 12.67 ms with them on the 64 x 64 tiles, 12.51 without).
-        const int t64 = ortk::tuning().gemm_t64;     // use them while the 128 x 128 grid has at most this many workgroups (-1 = never)
-        if (fast4 && impl != 1 && !want_stats && p.a_dtype == ORTK_BF16 && p.b_dtype == ORTK_BF16 && p.K % HBK == 0 &&
-            p.drop_p == 0.f && !p.gate && !p.rowscale && (int64_t)tilesM * tilesN <= t64 && p.N <= 2048 && p.M <= 6144) {
-            const int tm = (int)ortk_cdiv(p.M, 64), tn = p.N / 64;
-            const bool one = (int64_t)tm * tn <= 256 + 64;          // one workgroup per CU: the whole K = 512 panel in flight
-            gemm16_fn g = one ? gemm_bf16_dma64_kernel<8> : gemm_bf16_dma64_kernel<3>;    // else three per CU
-            const size_t lds = (one ? 8 : 3) * DMA64_STAGE_BYTES;
-            ortk::lds_attr(reinterpret_cast<const void*>(g), lds);
-            hipLaunchKernelGGL(g, dim3((unsigned)(tm * tn)), dim3(256), lds, s, p, tm, tn, kchunk);
-            if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
-        if (want_stats && tilesN > 0xFFFF) return ORTK_EINVAL;       // (the 128 x 128 kernel's column-tile argument is 16 bits wide: 8.3 M columns)
-        if ((fast || fast4) && (impl != 1 || want_stats) && dma_layout && p.a_dtype == ORTK_BF16 && p.b_dtype == ORTK_BF16 && kchunk % GBK == 0 && tilesN <= 0xFFFF) {
-            // 256 x 256 tiles when they still give enough workgroups (and no split-K accumulation, which needs the
-            // staged 128 x 128 epilogue); impl 2 = small tiles only, impl 3 = big tiles whenever legal
-            const int64_t big_blocks = (int64_t)ortk_cdiv(p.M, 256) * (p.N / 256);
-            // measured (scratch/gemm_shapes.py): the big tile wins whenever its grid fills >= 60 % of the CU slots of its
-            // last round (170 blocks: 29.6 vs 33.7 us; 510: 58 vs 72 us) and loses on short grids (72 blocks: 26 vs 17 us;
-            // 288 blocks = 1.1 rounds: 50 vs 44 us)
-            const int64_t rounds = (big_blocks + 255) / 256;
-            // In the training step the threshold is 50 %: the 130-tile launches of the valid-position decoder (16 640 x 512) leave
-            // the other half of the chip to the weight-gradient GEMM of the side stream (XE step 12.47 -> 12.10 ms; 40 % and
-            // 30 % measure the same)
-            const bool fills = big_blocks * 10 >= rounds * 256 * 5;
-            const bool lean = key == 4 && !p.accumulate && !p.rowscale && !(ortk::tuning().gemm_epilogue & 1);
-            // Round 6: a column count of 256 n + 128 (the padded vocabulary: 10 112 = 39 x 256 + 128) runs its first 256 n columns on the
-            // 256 x 256 tiles and the last 128 as a second launch of the 128 x 128 kernel on the same stream: the training-time generator
-            // (16 640 / 21 760 rows; XE step 10.03 -> 10.00 ms, SCST step 23.06 -> 22.94).  NOT the launches that carry soft-max
-            // partials: the decode-time generator (5 120 rows) is slower that way — 18.00 vs 17.65 ms per 1 024-image decode,
-            // scratch/decode_tuning_ab.py — as it was in round 5 (the statistics epilogue has nothing to overlap with at one workgroup per
-            // unit), so launches with statistics never take the big tile.
-            // (ortk_tuning.gemm_epilogue & 2: never split.)
-            const bool nsplit = lean && !want_stats && !(ortk::tuning().gemm_epilogue & 2) && p.N % 256 == 128 && p.N > 256 && p.K % HBK == 0;
-            const bool big = !p.accumulate && !want_stats && (p.M % 256 == 0 || fast4) &&
-                             (p.N % 256 == 0 || nsplit) && impl != 2 && (impl == 3 || fills);
-            // 8-deep ring for grids of at most one workgroup per CU (decode-time projections): measured SLOWER in the
-            // 1024-image decode (36.9 vs 35.8 ms) -> experiment only (ORTK_GEMM_IMPL=5)
-            const bool deep = !big && (int64_t)tilesM * tilesN * splitk <= 256 && impl == 5;
-            gemm16_fn gf;
-            if (big)       gf = key == 4 ? gemm_bf16_glds_kernel<false, false, true, 4> : key == 5 ? gemm_bf16_glds_kernel<false, true, true, 4> : gemm_bf16_glds_kernel<true, true, true, 4>;
-            else if (deep) gf = key == 4 ? gemm_bf16_glds_kernel<false, false, false, 8> : key == 5 ? gemm_bf16_glds_kernel<false, true, false, 8> : gemm_bf16_glds_kernel<true, true, false, 8>;
-            else           gf = key == 4 ? gemm_bf16_glds_kernel<false, false, false, 4> : key == 5 ? gemm_bf16_glds_kernel<false, true, false, 4> : gemm_bf16_glds_kernel<true, true, false, 4>;
-            // (the remainder launch of a split takes the small kernel's lean instance too)
-            if (big && nsplit) gf = gemm_bf16_glds_kernel<false, false, false, 4>;
-            if (lean && (!big || nsplit) && !deep) {
-                if (want_stats) gf = p.tile_samp ? gemm_bf16_glds_kernel<false, false, false, 4, 5> : gemm_bf16_glds_kernel<false, false, false, 4, 4>;
-                else switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
-                    case 0:  gf = gemm_bf16_glds_kernel<false, false, false, 4, 0>; break;
-                    case 1:  gf = gemm_bf16_glds_kernel<false, false, false, 4, 1>; break;
-                    case 2:  gf = gemm_bf16_glds_kernel<false, false, false, 4, 2>; break;
-                    default: gf = gemm_bf16_glds_kernel<false, false, false, 4, 3>; break;
-                }
-            }
-            const size_t lds = (big && !nsplit) ? GLDS_LDS_BYTES_BIG : deep ? 2 * GLDS_RING_BYTES : GLDS_LDS_BYTES;
-            ortk::lds_attr(reinterpret_cast<const void*>(gf), lds);
-            if (big && impl != 6 && p.K % HBK == 0) {
-                // 64-column stages (full cache lines); impl 6 = the 32-column 4-stage ring for comparison
-                gemm16_fn g2 = key == 4 ? gemm_bf16_dma256_kernel<false, false> : key == 5 ? gemm_bf16_dma256_kernel<false, true>
-                                                                                              : gemm_bf16_dma256_kernel<true, true>;
-                if (lean) {
-                    switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
-                        case 0:  g2 = gemm_bf16_dma256_kernel<false, false, 0>; break;
-                        case 1:  g2 = gemm_bf16_dma256_kernel<false, false, 1>; break;
-                        case 2:  g2 = gemm_bf16_dma256_kernel<false, false, 2>; break;
-                        default: g2 = gemm_bf16_dma256_kernel<false, false, 3>; break;
-                    }
-                }
-                ortk::lds_attr(reinterpret_cast<const void*>(g2), DMA256_LDS_BYTES);
-                hipLaunchKernelGGL(g2, dim3((unsigned)big_blocks), dim3(512), DMA256_LDS_BYTES, s, p, (int)ortk_cdiv(p.M, 256), p.N / 256, kchunk);
-                if (nsplit)      // the last 128 columns: one column tile of the 128 x 128 kernel, starting at tile (N / 128 - 1)
-                    hipLaunchKernelGGL(gf, dim3((unsigned)tilesM), block, lds, s, p, tilesM, 1 | ((tilesN - 1) << 16), kchunk);
-            }
-            else if (big) hipLaunchKernelGGL(gf, dim3((unsigned)big_blocks), dim3(512), lds, s, p, (int)ortk_cdiv(p.M, 256), p.N / 256, kchunk);
-            else          hipLaunchKernelGGL(gf, grid, block, lds, s, p, tilesM, tilesN, kchunk);
-            if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
-        gemm16_fn fn = key == 4 ? pick16<false, false>(p.a_dtype, p.b_dtype, fast)
-                     : key == 5 ? pick16<false, true>(p.a_dtype, p.b_dtype, fast)
-                                : pick16<true, true>(p.a_dtype, p.b_dtype, fast);
-        // > 64 KB of dynamic LDS needs the attribute once per kernel instance and device
-        ortk::lds_attr(reinterpret_cast<const void*>(fn), BF16_LDS_BYTES);
-        hipLaunchKernelGGL(fn, grid, block, BF16_LDS_BYTES, s, p, tilesM, tilesN, kchunk);
+        if (t.tilesN > 0xFFFF) return ORTK_EINVAL;       // (the 128 x 128 kernel's column-tile argument is 16 bits wide: 8.3 M columns)
     }
-    if (g_prof_on) { (void)hipEventRecord(rec.b, s); std::lock_guard<std::mutex> lk(g_prof_mu); g_prof->push_back(rec); }
+    return 0;
+}
+
+// ---- fused LayerNorm (ln_fused calls only)
+void plan_ln(const ortk_gemm_args& p, Plan& pl) {
+    pl.key = 4;
+    const double ab = (double)p.M * p.K * 2 + (double)p.N * p.K * 2;
+    if (p.ln_mode == 1) {
+        pl.bytes = ab + (double)p.M * p.N * (4 + 4 + 2);
+        pl.add(gemm_bf16_row512_kernel, ortk_cdiv(p.M, RP_M), 512, RP_LDS_BYTES, 0, 0, 0);
+        return;
+    }
+    // short row panels, about one workgroup per compute unit
+    pl.bytes = ab + (double)p.M * p.N * (4 + 4 + 4 + 2);
+    const int mt = (int)std::min<int64_t>(5, std::max<int64_t>(2, ortk_cdiv(p.M, 16 * 256)));      // (96-row panels spill)
+    const void* fn; size_t lds;
+    switch (mt) {
+        case 2:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<2>); lds = lb_lds_bytes<2>(); break;
+        case 3:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<3>); lds = lb_lds_bytes<3>(); break;
+        case 4:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<4>); lds = lb_lds_bytes<4>(); break;
+        default: fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<5>); lds = lb_lds_bytes<5>(); break;
+    }
+    pl.l[pl.n++] = Launch{fn, (unsigned)ortk_cdiv(p.M, 16 * mt), 512, lds, 0, 0, 0};
+}
+
+// ---- fp32, forward layout: three-way bf16 split on the bf16 matrix cores (gemm_f32x3_kernel / gemm_f32x3p_kernel)
+template <int WM, int WN, int GM, int GN, int MINB>
+void add_f32x3(const ortk_gemm_args& p, Plan& pl) {
+    const int tm = (int)ortk_cdiv(p.M, 32 * WM * GM), tn = (int)ortk_cdiv(p.N, 32 * WN * GN);
+    pl.add(gemm_f32x3_kernel<WM, WN, GM, GN, MINB>, (int64_t)tm * tn, 64 * GM * GN, 0, tm, tn, 0);
+}
+template <int WM, int WN, int GM, int GN, int MINB>
+void add_f32x3p(const ortk_gemm_args& p, Plan& pl) {
+    const int tm = (int)ortk_cdiv(p.M, 32 * WM * GM), tn = (int)ortk_cdiv(p.N, 32 * WN * GN);
+    pl.add(gemm_f32x3p_kernel<WM, WN, GM, GN, MINB>, (int64_t)tm * tn, 64 * GM * GN,
+           (size_t)2 * 3 * (32 * WM * GM + 32 * WN * GN) * 32 * sizeof(__bf16), tm, tn, 0);
+}
+bool plan_f32x3(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    if (!(layout_key(p) == 0 && ortk::tuning().f32_split && !p.accumulate && p.K > 0 && p.K % 32 == 0 && (p.lda & 3) == 0 && (p.ldb & 3) == 0 &&
+          al(p.A, 16) && al(p.B, 16))) return false;
+    // Instance by how the grid fills the 256 compute units (measured on the shapes of the fp32 parity decode:
+    // scratch/f32x3_bench.py, profiles/r05_f32_split_gemm.txt): the 256 x 128 pipelined tile wherever its grid fills at least
+    // 3/4 of its last round of workgroups; short grids (at most 1.25 workgroups of 128 x 128 per unit) the 64 x 64 pipelined
+    // tile; in between 128 x 64, three workgroups per unit.
+    const int64_t t128 = (int64_t)t.tilesM * t.tilesN, big = ortk_cdiv(p.M, 256) * (int64_t)t.tilesN;
+    const int force = ortk::tuning().f32_split;     // 1 automatic | 2..7 a fixed kernel instance
+    const int shape = force > 1 ? force : big * 4 >= ortk_cdiv(big, 256) * 256 * 3 ? 7 : t128 < 320 ? 5 : 3;
+    switch (shape) {
+        case 2:  add_f32x3<1, 1, 2, 2, 2>(p, pl); break;    // single-buffered: 64 x 64 (24 KB)
+        case 3:  add_f32x3<2, 1, 2, 2, 3>(p, pl); break;    //                  128 x 64 (36 KB), three workgroups per unit
+        case 4:  add_f32x3<2, 2, 2, 2, 3>(p, pl); break;    //                  128 x 128 (48 KB), three
+        case 5:  add_f32x3p<1, 1, 2, 2, 3>(p, pl); break;   // pipelined:       64 x 64 (48 KB)
+        case 6:  add_f32x3p<2, 1, 2, 2, 2>(p, pl); break;   //                  128 x 64 (72 KB)
+        default: add_f32x3p<2, 2, 4, 2, 1>(p, pl); break;   //                  256 x 128, 8 waves (144 KB)
+    }
+    return true;
+}
+// ---- fp32, transposed-operand layouts of the split product (gemm_f32x3t_kernel): dgrad without accumulation, wgrad with or without
+bool plan_f32x3t(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    const int key = layout_key(p);
+    if (!(key != 0 && ortk::tuning().f32_split && p.K > 0 && (p.ldb & 3) == 0 && al(p.B, 16) && (p.N & 3) == 0 && p.N >= 4 && t.kchunk % 32 == 0 &&
+          (key == 1 ? !p.accumulate && p.K % 32 == 0 && (p.lda & 3) == 0 && al(p.A, 16)
+                    : (p.lda & 3) == 0 && al(p.A, 16) && (p.M & 3) == 0 && p.M >= 4))) return false;
+    const gemm16_fn fn = key == 1 ? gemm_f32x3t_kernel<false, false> : p.accumulate ? gemm_f32x3t_kernel<true, true> : gemm_f32x3t_kernel<true, false>;
+    // (the accumulating instance stages its C tile over the six images)
+    pl.add(fn, t.grid(), 256, p.accumulate ? BF16_LDS_BYTES_C : (size_t)6 * 128 * 32 * sizeof(__bf16), t.tilesM, t.tilesN, t.kchunk);
+    return true;
+}
+// ---- fp32 MFMA: every fp32 call the split kernels do not take (f32_split = 0, odd K, unaligned operands).  No fused column sums:
+// ortk_gemm launches ortk_colsum ahead of it.
+void plan_f32(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    const int key = layout_key(p);
+    pl.add(key == 0 ? gemm_f32_kernel<false, false> : key == 1 ? gemm_f32_kernel<false, true> : gemm_f32_kernel<true, true>,
+           t.grid(), 256, 0, t.tilesM, t.tilesN, t.kchunk);
+}
+
+// ---- bf16, forward layout, short grids (decode-time projections): 64 x 64 tiles
+// Measured with bias + residual epilogues (scratch/gemm_t64.py, us, 128^2/256^2 kernels -> 64^2): 1536x512x512 16.4 -> 7.9,
+// 1536x512x2048 33.3 -> 15.6, 5120x512x512 16.8 -> 10.5, 5120x512x2048 35.9 -> 23.4, 5120x2048x512 31.4 -> 29.1,
+// 9216x512x512 23.3 -> 17.6; past ~640 big tiles or with the generator's N = 10240 the small tiles lose (5120x10240x512
+// 163 -> 178, 21760x1536x512 87 -> 106).  Decode-sized row counts only (M <= 6 144): inside the training step, beside
+// the side stream's weight gradients, the 9 216- and 16 640-row projections are faster on the big tiles (XE step
+// 12.67 ms with them on the 64 x 64 tiles, 12.51 without).
+bool plan_dma64(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    const int t64 = ortk::tuning().gemm_t64;     // use them while the 128 x 128 grid has at most this many workgroups (-1 = never)
+    if (!(bf16_fast4(p, t) && !p.tile_stats && both_bf16(p) && p.K % HBK == 0 &&
+          p.drop_p == 0.f && !p.gate && !p.rowscale && (int64_t)t.tilesM * t.tilesN <= t64 && p.N <= 2048 && p.M <= 6144)) return false;
+    const int tm = (int)ortk_cdiv(p.M, 64), tn = p.N / 64;
+    const bool one = (int64_t)tm * tn <= 256 + 64;          // one workgroup per CU: the whole K = 512 panel in flight; else three per CU
+    pl.add(one ? gemm_bf16_dma64_kernel<8> : gemm_bf16_dma64_kernel<3>, (int64_t)tm * tn, 256, (one ? 8 : 3) * DMA64_STAGE_BYTES, tm, tn, t.kchunk);
+    return true;
+}
+
+// ---- bf16, forward layout, full column / K tiles: the 128 x 128 and 256 x 256 LDS-DMA kernels
+// Forward layout only.  Measured in the XE step (bench.py, ms/step): register-staged kernel everywhere 17.9; DMA kernels
+// everywhere 21.3 (the k-major layouts lose: dgrad 4.1 vs 3.3 ms, wgrad 4.1 vs 3.4 ms per step in isolation,
+// profiles/r03_wgrad_impl.txt); the k-major instances of these kernels are gone, the weight gradients have moved to
+// ortk_wgrad_group and the data gradients come here in the forward layout through the transposed weight copy.
+gemm16_fn lean_glds(const ortk_gemm_args& p) {
+    if (p.tile_stats) return p.tile_samp ? gemm_bf16_glds_kernel<false, 5> : gemm_bf16_glds_kernel<false, 4>;
+    switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
+        case 0:  return gemm_bf16_glds_kernel<false, 0>;
+        case 1:  return gemm_bf16_glds_kernel<false, 1>;
+        case 2:  return gemm_bf16_glds_kernel<false, 2>;
+        default: return gemm_bf16_glds_kernel<false, 3>;
+    }
+}
+gemm16_fn lean_dma256(const ortk_gemm_args& p) {
+    switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
+        case 0:  return gemm_bf16_dma256_kernel<0>;
+        case 1:  return gemm_bf16_dma256_kernel<1>;
+        case 2:  return gemm_bf16_dma256_kernel<2>;
+        default: return gemm_bf16_dma256_kernel<3>;
+    }
+}
+bool plan_dma(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    const bool fast_nk = bf16_fast_nk(p, t), fast4 = bf16_fast4(p, t);
+    const bool want_stats = p.tile_stats != nullptr;
+    if (!(layout_key(p) == 4 && (fast4 || (fast_nk && p.M % BM == 0)) && both_bf16(p) && t.kchunk % GBK == 0 && t.tilesN <= 0xFFFF)) return false;
+    // 256 x 256 tiles when they still give enough workgroups (and no split-K accumulation, which needs the
+    // staged 128 x 128 epilogue)
+    const int64_t big_blocks = (int64_t)ortk_cdiv(p.M, 256) * (p.N / 256);
+    // measured (scratch/gemm_shapes.py): the big tile wins whenever its grid fills >= 60 % of the CU slots of its
+    // last round (170 blocks: 29.6 vs 33.7 us; 510: 58 vs 72 us) and loses on short grids (72 blocks: 26 vs 17 us;
+    // 288 blocks = 1.1 rounds: 50 vs 44 us)
+    const int64_t rounds = (big_blocks + 255) / 256;
+    // In the training step the threshold is 50 %: the 130-tile launches of the valid-position decoder (16 640 x 512) leave
+    // the other half of the chip to the weight-gradient GEMM of the side stream (XE step 12.47 -> 12.10 ms; 40 % and
+    // 30 % measure the same)
+    const bool fills = big_blocks * 10 >= rounds * 256 * 5;
+    const bool lean = !p.accumulate && !p.rowscale && !(ortk::tuning().gemm_epilogue & 1);
+    // Round 6: a column count of 256 n + 128 (the padded vocabulary: 10 112 = 39 x 256 + 128) runs its first 256 n columns on the
+    // 256 x 256 tiles and the last 128 as a second launch of the 128 x 128 kernel on the same stream: the training-time generator
+    // (16 640 / 21 760 rows; XE step 10.03 -> 10.00 ms, SCST step 23.06 -> 22.94).  NOT the launches that carry soft-max
+    // partials: the decode-time generator (5 120 rows) is slower that way — 18.00 vs 17.65 ms per 1 024-image decode,
+    // scratch/decode_tuning_ab.py — as it was in round 5 (the statistics epilogue has nothing to overlap with at one workgroup per
+    // unit), so launches with statistics never take the big tile.
+    // (ortk_tuning.gemm_epilogue & 2: never split.)
+    const bool nsplit = lean && !want_stats && !(ortk::tuning().gemm_epilogue & 2) && p.N % 256 == 128 && p.N > 256 && p.K % HBK == 0;
+    const bool big = !p.accumulate && !want_stats && (p.M % 256 == 0 || fast4) && (p.N % 256 == 0 || nsplit) && fills;
+    const gemm16_fn small = lean ? lean_glds(p) : gemm_bf16_glds_kernel<false>;
+    if (!big) {
+        pl.add(small, t.grid(), 256, GLDS_LDS_BYTES, t.tilesM, t.tilesN, t.kchunk);
+    } else if (p.K % HBK == 0) {
+        // 64-column stages (full cache lines)
+        pl.add(lean ? lean_dma256(p) : gemm_bf16_dma256_kernel<>, big_blocks, 512, DMA256_LDS_BYTES, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
+        if (nsplit)      // the last 128 columns: one column tile of the 128 x 128 kernel, starting at tile (N / 128 - 1)
+            pl.add(small, t.tilesM, 256, GLDS_LDS_BYTES, t.tilesM, 1 | ((t.tilesN - 1) << 16), t.kchunk);
+    } else {
+        // K = 32 (mod 64): the 32-column ring on the big tile
+        pl.add(gemm_bf16_glds_kernel<true>, big_blocks, 512, GLDS_LDS_BYTES_BIG, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
+    }
+    return true;
+}
+
+// ---- bf16 MFMA, register-staged: every layout, fp32 or bf16 operands, ragged shapes, split-K accumulation, fused column sums
+void plan_bf16(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
+    const int key = layout_key(p);
+    const bool fast = bf16_fast_nk(p, t) && p.M % BM == 0;
+    pl.add(key == 4 ? pick16<false, false>(p.a_dtype, p.b_dtype, fast)
+         : key == 5 ? pick16<false, true>(p.a_dtype, p.b_dtype, fast)
+                    : pick16<true, true>(p.a_dtype, p.b_dtype, fast),
+           t.grid(), 256, BF16_LDS_BYTES, t.tilesM, t.tilesN, t.kchunk);
+}
+
+// The one launch tail.  (> 64 KB of dynamic LDS needs the attribute once per kernel instance and device; it is set before the
+// profiling events exist so that no error leaves the function with events in hand.)
+int gemm_launch(ortk_gemm_args& p, Plan& pl, hipStream_t s) {
+    for (int i = 0; i < pl.n; ++i)
+        if (pl.l[i].lds > 0 && ortk::lds_attr(pl.l[i].fn, pl.l[i].lds)) return ORTK_EINVAL;
+    ortk::ProfMark mark;
+    ortk::prof_begin(pl.key, 2.0 * p.M * p.N * p.K, pl.bytes, s, mark);
+    for (int i = 0; i < pl.n; ++i) {
+        Launch& l = pl.l[i];
+        void* args[] = {&p, &l.a0, &l.a1, &l.a2};
+        (void)hipLaunchKernel(l.fn, dim3(l.grid), dim3(l.block), args, l.lds, s);     // (its error: ORTK_CHECK_LAUNCH below)
+    }
+    ortk::prof_end(mark, s);
     ORTK_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
+    if (!a || !a->A || !a->B || !a->C || a->M < 0 || a->N < 0 || a->K < 0) return ORTK_EINVAL;
+    if (a->M == 0 || a->N == 0) return 0;
+    ortk_gemm_args p = *a;
+    if (int e = gemm_validate(p)) return e;
+    if (p.ln_mode && !ln_fused(p)) {
+        // any other shape / precision: the same result from the separate kernels
+        ortk_gemm_args q = p; q.ln_mode = 0;
+        if (p.ln_mode == 2) q.drop_p = 0.f;
+        if (int e = ortk_gemm(&q, stream)) return e;
+        float* Cf = reinterpret_cast<float*>(p.C);
+        if (p.ln_mode == 1) return ortk_layernorm_fwd(Cf, p.ln_a, p.ln_b, p.ln_y, p.ln_y_dtype, p.ln_stats, p.M, p.N, p.ln_eps, stream);
+        return ortk_layernorm_bwd_drop_rows(Cf, p.ln_x, p.ln_a, p.ln_stats, p.ln_dres, Cf, p.ln_da, p.ln_db, p.M, p.N, p.ln_eps,
+                                            p.ln_y, p.ln_y_dtype, p.drop_p, p.drop_seed, p.drop_rows, stream);
+    }
+    Plan pl;
+    if (p.ln_mode) {
+        plan_ln(p, pl);
+    } else {
+        const Tiling t = gemm_tiling(p);
+        pl.key = layout_key(p);
+        pl.bytes = (double)p.M * p.K * ortk_esize(p.a_dtype) + (double)p.N * p.K * ortk_esize(p.b_dtype) +
+                   (double)p.M * p.N * (ortk_esize(p.c_dtype) + (p.resid ? 4 : 0) + (p.gate ? ortk_esize(p.gate_dtype) : 0));
+        if (p.precision) {
+            if (!plan_dma64(p, t, pl) && !plan_dma(p, t, pl)) plan_bf16(p, t, pl);
+        } else if (!plan_f32x3(p, t, pl) && !plan_f32x3t(p, t, pl)) {
+            if (p.colsum) { if (int e = ortk_colsum(p.A, ORTK_F32, p.lda, p.colsum, p.K, p.M, stream)) return e; }
+            plan_f32(p, t, pl);
+        }
+    }
+    return gemm_launch(p, pl, ortk_s(stream));
 }

@@ -891,20 +891,7 @@ using namespace ortk;
 // ================================================================================================ C ABI
 extern "C" int ortk_version(void) { return ORTK_VERSION; }
 
-// ------------------------------------------------------------------------------------------------ tuning switches
-namespace ortk {
-static ortk_tuning g_tuning = {0, 640, 0, 33, 1, 1, 1, 1, 1, 384, 3, 0, 80, 1, 1, 0, 1, 0};
-const ortk_tuning& tuning() { return g_tuning; }
-}
-extern "C" void ortk_get_tuning(ortk_tuning* out) { if (out) *out = ortk::g_tuning; }
-extern "C" int ortk_set_tuning(const ortk_tuning* t) {
-    if (!t || t->gemm_impl < 0 || t->gemm_impl > 3 || t->attn_impl < 0 || t->attn_impl > 4 || t->attn16_min_lq < 1 || t->f32_split < 0 || t->f32_split > 7 || t->wgrad_wgs < 1 ||
-        t->wgrad_group < 0 || t->wgrad_group > 15 || t->wgrad_group_splitk < 0 || t->wgrad_group_splitk > 8 || t->wgrad_group_wgs < 1 || t->wgrad_group_tail < 0 || t->wgrad_group_tail > 1 ||
-        t->feats_bf16 < 0 || t->feats_bf16 > 1 || t->ln_fuse < 0 || t->ln_fuse > 15 || t->samp_epilogue < 0 || t->samp_epilogue > 1 || t->gemm_epilogue < 0 || t->gemm_epilogue > 3) return ORTK_EINVAL;
-    ortk::g_tuning = *t;
-    return 0;
-}
-
+// (the tuning switches and the profiling registry: ortk_runtime.hip)
 extern "C" int ortk_device_ok(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return 0;

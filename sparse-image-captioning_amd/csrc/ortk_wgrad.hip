@@ -16,7 +16,7 @@
 // Kernel: 256 x 256 tile, 8 waves (2 x 4, each 128 x 64 = 8 x 4 MFMA 16x16x32), a ring of four 32-row stages filled by
 // LDS-DMA (global_load_lds_dwordx4: a k-row of a tile is 512 contiguous bytes), one raw s_barrier per stage, counted vmcnt;
 // [k][m] images XOR-swizzled on the source address, fragments by ds_read_b64_tr_b16 (the images and reads of
-// gemm_bf16_glds_kernel<true, true, true, 4>, ortk_gemm.hip).  Rows past a multiple of 32 go through one guarded,
+// gemm_bf16_glds_kernel's former k-major instance, ortk_gemm.hip).  Rows past a multiple of 32 go through one guarded,
 // register-staged step (any row count: the valid-position decoder layout has one row per caption token).  The bias gradient
 // is one more MFMA per A fragment against a vector of ones (first column tile only).  Epilogue: the fp32 tile is staged
 // through the (free) ring in two halves and added to the arena as 256 contiguous bytes per atomic wave-instruction
