@@ -136,7 +136,8 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
     }
     stage_rows<DK>(sK, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, 16 * NJT, tid, blockDim.x);
     stage_rows<DK>(sV, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, KJ, tid, blockDim.x);
-    if (tid < 128) sMask[tid] = (tid < Lkg) ? (a.kmask ? a.kmask[krow0 + tid] : 1.f) : -1.f;   // -1: padded key
+    for (int j = tid; j < 128; j += blockDim.x)     // all 128 entries whatever the workgroup size (one wave when Lq <= 16)
+        sMask[j] = (j < Lkg) ? (a.kmask ? a.kmask[krow0 + j] : 1.f) : -1.f;                    // -1: padded key
     // key columns 16*NJT .. KJ-1 of the P image are never written below: zero the image once
     for (int idx = lane; idx < 16 * (KJ / 4); idx += 64)
         *reinterpret_cast<bf16x4*>(sP + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));

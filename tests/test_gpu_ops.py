@@ -660,7 +660,7 @@ def test_attention_dropout_is_consistent_between_fwd_and_bwd(L, nkv, H, Lq, Lk, 
     a.nkv, a.H, a.Lq, a.Lk, a.dk = nkv, H, Lq, Lk, dk
     a.drop_p, a.drop_seed = 0.3, 77
     L.check(L.lib().ortk_attention_fwd(C.byref(a), L.stream_ptr()), "attn_fwd")
-    # recover the mask from O = (P*m/keep) V by solving with the saved P: compare against a torch replay of the hash
+    # (the mask itself is compared with the hash in test_gpu_attention.py: test_dropout_is_the_hash_on_every_default_family)
     dq, dk_, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
     a.d_o, a.dq, a.d_k, a.dv = do.data_ptr(), dq.data_ptr(), dk_.data_ptr(), dv.data_ptr()
     a.lddo = a.lddq = a.lddk = a.lddv = d
