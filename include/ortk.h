@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 4      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 5      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -743,6 +743,31 @@ int ortk_mask_bwd_draws(const float* dw_eff, const float* w, const float* m, con
 int ortk_linear_block(const ortk_config* cfg, int32_t i, int64_t* offset, int32_t* N, int32_t* K);
 /* count_dev[0] += number of kept entries (round(sigmoid(m)) for mode 0/1, m != 0 for mode 2) in m[0..n). */
 int ortk_mask_count(const float* m, int64_t n, int32_t mode, float* count_dev, ortk_stream stream);
+
+/* Magnitude-pruning mask selection on the device (pruning/prune.py:271-283,330-365: cat + topk + scatter), no sort, no index array,
+ * no host synchronisation; every launch is on `stream`.  Segment s is the arena range [seg_offset[s], seg_offset[s] + seg_numel[s])
+ * of `w` and of `mask` (same offsets) and is ranked with the other segments of group seg_group[s] (0 .. n_groups-1).  In every
+ * group the n_drop[g] positions with the smallest criterion get mask 0.0 and the group's other positions 1.0; nothing outside the
+ * listed segments is read or written.
+ *   kind 0: c = |w|                                       (mag_blind: one group; mag_uniform: one group per segment)
+ *   kind 1: c = |(w - mean_s) / std_s| per segment s      (mag_dist; population std; mean and std accumulated in fp64 in a fixed
+ *           order, rounded to fp32, c formed in fp32 with a true division)
+ * The key is the fp32 bit pattern of c: -0.0 ties with +0.0, denormals are not flushed, NaN ranks above +inf and is dropped last.
+ * Tie rule: among equal keys at the threshold, the entries with the LOWEST position in group order are dropped — group order is
+ * the order of the chunk table among the chunks of the group.  Two calls on the same inputs give the same bits.
+ * Chunk c is the range [chunk_start[c], chunk_start[c] + chunk_len[c]) INSIDE segment chunk_seg[c]; one workgroup walks it.  The
+ * chunks partition every segment, segments in the order listed and ascending starts inside a segment.  Ranges whose arena start is a
+ * multiple of 4 elements move 16 bytes per lane.  All seven tables are device arrays of int64.
+ * The table CONTENTS are the caller's responsibility (ranges inside the arenas, a partition, 0 <= n_drop[g] <= size of group g, a
+ * group below 2^32 elements): only the arguments themselves are checked.  ORTK_EINVAL before the first launch for a null pointer,
+ * a count <= 0, kind outside {0, 1}, more than 4096 segments, or a workspace (16-byte aligned device memory) smaller than
+ * ortk_mask_select_workspace_bytes(): 8 B of state and a 1 KB histogram per group, 16 B per chunk, and for kind 1 another 8 B per
+ * chunk and 16 B per segment.  Passes over the listed weights: 6 reads + 1 mask write (kind 1: 8 reads). */
+size_t ortk_mask_select_workspace_bytes(int32_t n_segments, int32_t n_groups, int32_t n_chunks, int32_t kind);
+int ortk_mask_select(const float* w, float* mask, const int64_t* seg_offset, const int64_t* seg_numel, const int64_t* seg_group,
+                     const int64_t* chunk_seg, const int64_t* chunk_start, const int64_t* chunk_len, const int64_t* n_drop,
+                     int32_t n_segments, int32_t n_groups, int32_t n_chunks, int32_t kind, void* workspace, size_t workspace_bytes,
+                     ortk_stream stream);
 
 #ifdef __cplusplus
 }

@@ -234,6 +234,8 @@ SIGNATURES = {
     "ortk_mask_bwd": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _U32, _P, _P]),
     "ortk_masked_adam_step": (_I32, [C.POINTER(MaskedAdamArgs), _P]),
     "ortk_mask_count": (_I32, [_P, _I64, _I32, _P, _P]),
+    "ortk_mask_select_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "ortk_mask_select": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P]),
     "ortk_mask_apply_draws": (_I32, [_P, _P, _P, _P, _I64, _P]),
     "ortk_mask_bwd_draws": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "ortk_decode_step_workspace_bytes": (_SZ, [_CFG, _I32]),
@@ -246,7 +248,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 4      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 5      # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -168,6 +168,48 @@ class RelationTransformerModel(PruningMixin, _Dense):
             n += m.numel()
         return n, cnt[0]
 
+    # ---- mask selection on the device (PruningMixin.update_masks_once(select="device"))
+    SELECT_CHUNK = 32768        # elements one workgroup of ortk_mask_select walks (a multiple of 4: entries start on multiples of 64)
+
+    def _select_plan(self):
+        """Segment / chunk tables of the active maskable weights, in `active_pruning_masks()` order, on the arenas' device, with the
+        workspace: built once, rebuilt when the arenas are rebound (`.cuda()`), the frozen scope or the mask type changes."""
+        key = (self._flat.data_ptr(), self._mask_flat.data_ptr(), tuple(self.mask_freeze_scope or ()), self.mask_type)
+        plan = getattr(self, "_select_cache", None)
+        if plan is not None and plan["key"] == key:
+            return plan
+        how = prune._KIND[self.mask_type][1]
+        entry = {e["name"] + "_pruning_mask": e for e in self.named_weight_entries() if e["kind"] == 1}
+        segs = [entry[n] for n, _ in self.active_pruning_masks()]
+        if not segs:
+            raise ValueError("select='device': no active pruning mask (every maskable weight is inside the frozen scope)")
+        per_layer = how == "uniform"
+        group = [i if per_layer else 0 for i in range(len(segs))]
+        group_numel = [e["numel"] for e in segs] if per_layer else [sum(e["numel"] for e in segs)]
+        chunks = [(i, start, min(self.SELECT_CHUNK, e["numel"] - start))
+                  for i, e in enumerate(segs) for start in range(0, e["numel"], self.SELECT_CHUNK)]
+        rows = [[e["offset"] for e in segs], [e["numel"] for e in segs], group] + [list(col) for col in zip(*chunks)]
+        dev = self._flat.device
+        counts = (len(segs), len(group_numel), len(chunks), 1 if how == "dist" else 0)
+        plan = {"key": key, "counts": counts, "group_numel": group_numel,
+                "tables": [torch.tensor(r, dtype=torch.int64, device=dev) for r in rows],
+                "ws": torch.empty(L.lib().ortk_mask_select_workspace_bytes(*counts), dtype=torch.uint8, device=dev)}
+        self._select_cache = plan
+        return plan
+
+    def _select_masks_device(self, sparsity_target):
+        """`compute_mask` for every group of the active weights in ONE call: the host works out how many entries each group loses
+        (the same arithmetic and assertions as `compute_mask`), the device decides which."""
+        if not (self._flat.is_cuda and self._mask_flat.is_cuda):
+            raise ValueError("select='device' needs the arenas on the GPU (model.cuda()); there is no CPU route")
+        assert isinstance(sparsity_target, float) and 0 <= sparsity_target < 1.0
+        plan = self._select_plan()
+        n_drop = [int(sparsity_target * n) for n in plan["group_numel"]]
+        assert all(0 <= d < n for d, n in zip(n_drop, plan["group_numel"]))
+        n_drop = torch.tensor(n_drop, dtype=torch.int64).to(self._flat.device)
+        L.check(L.lib().ortk_mask_select(L.ptr(self._flat), L.ptr(self._mask_flat), *[L.ptr(t) for t in plan["tables"]], L.ptr(n_drop),
+                                         *plan["counts"], L.ptr(plan["ws"]), plan["ws"].numel(), L.stream_ptr()), "ortk_mask_select")
+
     @staticmethod
     def add_argparse_args(parser):
         _Dense.add_argparse_args(parser)

@@ -7,7 +7,8 @@ Where the work happens here:
 * every training step — materialising ``w * mask``, the straight-through backward, counting kept entries — is HIP
   (``ortk_mask_apply`` / ``ortk_mask_bwd`` / ``ortk_mask_count`` over the flat arenas, see ``relation_transformer_prune.py``);
 * the occasional mask UPDATES (one-shot / gradual magnitude pruning, SNIP), the statistics and the checkpoint views are a few
-  tensor expressions on the device arenas below: off the per-step path.
+  tensor expressions on the device arenas below: off the per-step path.  ``select="device"`` hands the
+  magnitude updates to ``ortk_mask_select`` (a radix select over the arenas: no cat, no topk, a defined tie rule).
 
 Mask kinds are described by one table (``_KIND``) instead of the reference's parallel lists; the module-level names the
 callers use (``REGULAR``, ``SNIP``, ``MAG_HARD`` ...) are derived from it.
@@ -238,8 +239,21 @@ class PruningMixin:
         return mask
 
     @torch.no_grad()
-    def update_masks_once(self, sparsity_target):
+    def update_masks_once(self, sparsity_target, select="torch"):
+        """``select="torch"``: the reference's route below (cat + topk + scatter; the order among equal criteria is whatever the
+        sort leaves).  ``select="device"``: the arena model's one-call radix select (``ortk_mask_select``; among equal criteria at
+        the threshold the lowest positions go) for the blind / uniform / dist criteria; SNIP keeps the torch route."""
         assert self.mask_type in MAG_PRUNE_MASKS, f"Invalid mask_type: {self.mask_type}. Must be one of {MAG_PRUNE_MASKS}"
+        if select not in ("torch", "device"):
+            raise ValueError(f"`select` must be 'torch' or 'device', saw `{select}`")
+        if select == "device" and _KIND[self.mask_type][1] in ("blind", "uniform", "dist"):
+            hook = getattr(self, "_select_masks_device", None)
+            if hook is None:
+                raise ValueError("select='device' needs a model whose weights and masks live in device arenas")
+            hook(sparsity_target)
+            self.sparsity_target = sparsity_target
+            self.sparsity_check()
+            return True
         masks = self.active_pruning_masks(named=False)
         weights = self.active_pruned_weights(named=False)
         assert len(weights) == len(masks)
@@ -255,7 +269,7 @@ class PruningMixin:
 
     @torch.no_grad()
     def update_masks_gradual(self, sparsity_target, current_step, start_step, prune_steps, initial_sparsity=0.0,
-                             prune_frequency=1000):
+                             prune_frequency=1000, select="torch"):
         """Cubic schedule of Zhu & Gupta, applied every `prune_frequency` steps from `start_step` (prune.py:383-433)."""
         assert self.mask_type in MAG_ANNEAL
         end_step = start_step + prune_frequency * prune_steps
@@ -263,7 +277,8 @@ class PruningMixin:
         due = current_step >= start_step and (current_step <= end_step or end_step < 0)
         if due and (current_step - start_step) % prune_frequency == 0:
             done = min(1.0, max(0.0, (current_step - start_step) / (end_step - start_step)))
-            self.update_masks_once(sparsity_target=sparsity_target + (initial_sparsity - sparsity_target) * (1.0 - done) ** 3)
+            self.update_masks_once(sparsity_target=sparsity_target + (initial_sparsity - sparsity_target) * (1.0 - done) ** 3,
+                                   select=select)
         return False
 
     @staticmethod
