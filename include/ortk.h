@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 5      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 6      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -153,6 +153,13 @@ void* ortk_train_workspace_memory(const ortk_config* cfg, int32_t B, int32_t S, 
  * Writes the scalar loss to *loss_dev and leaves dLoss/dlogits in `ws`. */
 int ortk_loss(const ortk_config* cfg, const ortk_batch* batch, void* ws, size_t ws_bytes,
               const float* norm_dev, float* loss_dev, ortk_stream stream);
+
+/* The label-smoothed criterion (LabelSmoothing, utils/losses.py:46-77; scripts/train_transformer.py:33-34 when --label_smoothing > 0)
+ * in place of ortk_loss, on the same workspace and batch (valid-position layout included):
+ *   loss = sum_{r,t} KL(q || p)[r,t]*tok_weight[r,t] / norm,  q = 1 - smoothing on the target, smoothing / (V - 1) elsewhere,
+ *   V = cfg->vocab; dLoss/dlogits = (p - q)*tok_weight/norm is left in `ws`.  0 <= smoothing < 1 (0: the plain criterion). */
+int ortk_loss_smooth(const ortk_config* cfg, const ortk_batch* batch, void* ws, size_t ws_bytes,
+                     const float* norm_dev, float* loss_dev, float smoothing, ortk_stream stream);
 
 /* Alternative to ortk_loss for an external criterion: dlogp (R,T,ldv) -> dLoss/dlogits in `ws`. */
 int ortk_loss_external(const ortk_config* cfg, const ortk_batch* batch, void* ws, size_t ws_bytes,
@@ -674,6 +681,13 @@ int64_t ortk_xent_scratch_floats(int64_t rows);
 int ortk_xent_fwd_bwd(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight,
                       const float* norm_dev, float* loss_dev, float* row_loss, int64_t rows, int32_t V, int64_t ld,
                       void* dlogits, int32_t dl_dtype, int64_t ld_dl, ortk_stream stream);
+/* The same for the label-smoothed criterion (LabelSmoothing, utils/losses.py:46-77): per row
+ *   KL = K0 - c*lp[t] - s*(sum_v lp[v] - lp[t]),  c = 1 - smoothing, s = smoothing / (V - 1), K0 = c ln c + (V - 1) s ln s,
+ * times w/norm; dlogits = (p - q)*w/norm with q[t] = c, q[v != t] = s.  Same scratch, aliasing rule and fixed-order sum;
+ * ORTK_EINVAL unless 0 <= smoothing < 1 (finite) and V >= 2.  smoothing = 0 is the plain cross-entropy. */
+int ortk_xent_smooth_fwd_bwd(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight,
+                             const float* norm_dev, float* loss_dev, float* row_loss, int64_t rows, int32_t V, int64_t ld,
+                             void* dlogits, int32_t dl_dtype, int64_t ld_dl, float smoothing, ortk_stream stream);
 /* log_softmax backward: dlogits = dlogp - exp(logp) * sum_v dlogp, written over (rows, ld_out). */
 int ortk_log_softmax_bwd(const float* logp, const float* dlogp, int64_t ld_in, void* dlogits, int32_t dl_dtype,
                          int64_t ld_out, int64_t rows, int32_t V, ortk_stream stream);

@@ -181,6 +181,7 @@ SIGNATURES = {
     "ortk_forward_phase": (_I32, [_CFG, _P, C.POINTER(Batch), _P, _SZ, _P, _I64, _I32, _U64, _I32, _P]),
     "ortk_train_workspace_memory": (_P, [_CFG, _I32, _I32, _I32, _I32, _P, C.POINTER(C.c_int32)]),
     "ortk_loss": (_I32, [_CFG, C.POINTER(Batch), _P, _SZ, _P, _P, _P]),
+    "ortk_loss_smooth": (_I32, [_CFG, C.POINTER(Batch), _P, _SZ, _P, _P, _F, _P]),
     "ortk_loss_external": (_I32, [_CFG, C.POINTER(Batch), _P, _SZ, _P, _P, _I64, _P]),
     "ortk_backward": (_I32, [_CFG, _P, _P, C.POINTER(Batch), _P, _SZ, _I32, _U64, _P]),
     "ortk_backward_phase": (_I32, [_CFG, _P, _P, C.POINTER(Batch), _P, _SZ, _I32, _U64, _I32, _P]),
@@ -218,6 +219,7 @@ SIGNATURES = {
     "ortk_log_softmax": (_I32, [_P, _I64, _I32, _I64, _F, _P]),
     "ortk_xent_scratch_floats": (_I64, [_I64]),
     "ortk_xent_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _P]),
+    "ortk_xent_smooth_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _F, _P]),
     "ortk_log_softmax_bwd": (_I32, [_P, _P, _I64, _P, _I32, _I64, _I64, _I32, _P]),
     "ortk_colsum": (_I32, [_P, _I32, _I64, _P, _I64, _I32, _P]),
     "ortk_gate_apply": (_I32, [_P, _P, _P, _I32, _I64, _F, _P]),
@@ -248,7 +250,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 5      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 6      # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -164,6 +164,102 @@ __global__ __launch_bounds__(256) void xent_reg_kernel(const float* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------- label-smoothed CE
+// LabelSmoothing (utils/losses.py:46-77): per row KL(q || p), q[tgt] = conf = 1 - eps, q[v != tgt] = sm = eps / (V - 1):
+//     KL = K0 - conf * lp[tgt] - sm * (sum_v lp[v] - lp[tgt]),   K0 = conf ln conf + (V - 1) sm ln sm  (host, double; 0 ln 0 = 0)
+//     sum_v lp[v] = sum_v (z[v] - max) - V * lse,                 dKL/dz = p - q.
+// The three forms of the plain criterion above, with one more block reduction (sum_v (z - max), per thread in element order, then
+// block_sum: no atomics) and q instead of the one-hot in the gradient; eps = 0 is the plain criterion.  One read of the logits, one
+// write of the gradient.
+__device__ __forceinline__ float smooth_row_term(float w, float k0, float conf, float sm, float lp_t, float sum_zm, float lse, int V) {
+    const float sum_lp = sum_zm - (float)V * lse;
+    return w != 0.f ? w * (k0 - conf * lp_t - sm * (sum_lp - lp_t)) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void xent_smooth_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                          int64_t target_stride, int T, const float* __restrict__ weight,
+                                                          const float* __restrict__ norm_dev, float* __restrict__ row_loss, int V,
+                                                          int64_t ld, void* dlogits, int dl_dt, int64_t ld_dl, const int32_t* __restrict__ row_pos,
+                                                          float k0, float conf, float sm) {
+    __shared__ float sh[4];
+    const int64_t r = blockIdx.x;
+    const float* row = logits + r * ld;
+    const int64_t pr = row_pos ? (int64_t)row_pos[r] : r;
+    const int64_t tgt = targets[(pr / T) * target_stride + (pr % T)];
+    const float w = weight[pr] / norm_dev[0];
+    float mx = -INFINITY;
+    for (int c = threadIdx.x; c < V; c += 256) mx = fmaxf(mx, row[c]);
+    mx = block_max(mx, sh);
+    float s = 0.f, zm = 0.f;
+    for (int c = threadIdx.x; c < V; c += 256) { const float d = row[c] - mx; zm += d; s += expf(d); }
+    s = block_sum(s, sh);
+    zm = block_sum(zm, sh);
+    const float lse = logf(s);
+    if (threadIdx.x == 0) row_loss[r] = smooth_row_term(w, k0, conf, sm, (row[tgt] - mx) - lse, zm, lse, V);
+    __syncthreads();
+    // dlogits may alias logits (fp32, same ld): every element is read before it is overwritten by the same thread
+    for (int c = threadIdx.x; c < (int)ld_dl; c += 256) {
+        float g = 0.f;
+        if (c < V && w != 0.f) g = (expf((row[c] - mx) - lse) - (c == tgt ? conf : sm)) * w;
+        st_elem(dlogits, r * ld_dl + c, dl_dt, g);
+    }
+}
+
+// Register-resident form, as xent_reg_kernel: the row is read once.  FAST: e = exp(z - max) replaces z in its register, so z - max is
+// added to the row's sum before that.
+template <int NPT, bool FAST>
+__global__ __launch_bounds__(256) void xent_smooth_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                              int64_t target_stride, int T, const float* __restrict__ weight,
+                                                              const float* __restrict__ norm_dev, float* __restrict__ row_loss, int V,
+                                                              int64_t ld, void* dlogits, int dl_dt, int64_t ld_dl, const int32_t* __restrict__ row_pos,
+                                                              float k0, float conf, float sm) {
+    __shared__ float sh[4];
+    const int64_t r = blockIdx.x;
+    const float* row = logits + r * ld;
+    const int tid = threadIdx.x;
+    float z[NPT];
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) { const int c = tid + 256 * u; z[u] = c < V ? row[c] : 0.f; }
+    const int64_t pr = row_pos ? (int64_t)row_pos[r] : r;
+    const int64_t tgt = targets[(pr / T) * target_stride + (pr % T)];
+    const float w = weight[pr] / norm_dev[0];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) mx = fmaxf(mx, z[u]);
+    mx = block_max(mx, sh);
+    float s = 0.f, zm = 0.f;
+    if (FAST) {
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) {
+            const bool in = tid + 256 * u < V;
+            z[u] -= mx;
+            zm += in ? z[u] : 0.f;
+            z[u] = in ? __expf(z[u]) : 0.f;
+            s += z[u];
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) { zm += z[u] - mx; s += expf(z[u] - mx); }
+    }
+    s = block_sum(s, sh);
+    zm = block_sum(zm, sh);
+    const float lse = logf(s);
+    if (tid == 0) row_loss[r] = smooth_row_term(w, k0, conf, sm, (row[tgt] - mx) - lse, zm, lse, V);
+    __syncthreads();     // dlogits may alias logits (fp32 mode): the whole row is in registers and row[tgt] has been read
+    const float ws_ = FAST ? w / s : 0.f;
+    const float wc = w * conf, wsm = w * sm;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+        const int c = tid + 256 * u;
+        if (c < (int)ld_dl) {
+            float g = 0.f;
+            if (FAST) { if (c < V && w != 0.f) g = z[u] * ws_ - (c == tgt ? wc : wsm); }
+            else if (c < V && w != 0.f) g = (expf((z[u] - mx) - lse) - (c == tgt ? conf : sm)) * w;
+            st_elem(dlogits, r * ld_dl + c, dl_dt, g);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __restrict__ logp, const float* __restrict__ dlogp,
                                                               int64_t ld_in, void* __restrict__ dlogits, int dl_dt, int64_t ld_out, int V) {
     __shared__ float sh[4];
@@ -423,6 +519,30 @@ int xent_rows(const float* logits, const int64_t* targets, int64_t target_stride
     ORTK_CHECK_LAUNCH();
     return sum_fixed(row_loss, rows, row_loss + rows, loss_dev, s);
 }
+// the label-smoothed criterion: xent_rows' arguments, scratch and kernel selection; V is the width the reference's criterion sees
+int xent_smooth_rows(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight, const float* norm_dev,
+                     float* loss_dev, float* row_loss, int64_t rows, const int32_t* row_pos, int32_t V, int64_t ld, void* dlogits,
+                     int32_t dl_dtype, int64_t ld_dl, float smoothing, hipStream_t s) {
+    if (!logits || !targets || !weight || !norm_dev || !loss_dev || !row_loss || !dlogits || rows < 0 || V < 2 || ld < V || ld_dl < V || T < 1)
+        return ORTK_EINVAL;
+    if (dl_dtype != ORTK_F32 && dl_dtype != ORTK_BF16) return ORTK_EINVAL;
+    if (!std::isfinite(smoothing) || smoothing < 0.f || smoothing >= 1.f) return ORTK_EINVAL;
+    if (rows == 0) return ortk_fill(loss_dev, 1, 0.f, (ortk_stream)s);
+    const double cd = 1.0 - (double)smoothing, sd = (double)smoothing / (double)(V - 1);
+    const double k0d = (cd > 0.0 ? cd * log(cd) : 0.0) + (sd > 0.0 ? (double)(V - 1) * sd * log(sd) : 0.0);
+    const float k0 = (float)k0d, conf = (float)cd, sm = (float)sd;
+    if (V <= 256 * 40 && ld_dl <= 256 * 40 && V > 256 * 8 && dl_dtype == ORTK_BF16)
+        hipLaunchKernelGGL((xent_smooth_reg_kernel<40, true>), dim3((unsigned)rows), dim3(256), 0, s, logits, targets, target_stride, T,
+                           weight, norm_dev, row_loss, V, ld, dlogits, (int)dl_dtype, ld_dl, row_pos, k0, conf, sm);
+    else if (V <= 256 * 40 && ld_dl <= 256 * 40 && V > 256 * 8)
+        hipLaunchKernelGGL((xent_smooth_reg_kernel<40, false>), dim3((unsigned)rows), dim3(256), 0, s, logits, targets, target_stride, T,
+                           weight, norm_dev, row_loss, V, ld, dlogits, (int)dl_dtype, ld_dl, row_pos, k0, conf, sm);
+    else
+        hipLaunchKernelGGL(xent_smooth_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, targets, target_stride, T, weight,
+                           norm_dev, row_loss, V, ld, dlogits, (int)dl_dtype, ld_dl, row_pos, k0, conf, sm);
+    ORTK_CHECK_LAUNCH();
+    return sum_fixed(row_loss, rows, row_loss + rows, loss_dev, s);
+}
 }  // namespace ortk
 
 extern "C" int64_t ortk_xent_scratch_floats(int64_t rows) { return ortk::xent_scratch_floats(rows); }
@@ -431,6 +551,13 @@ extern "C" int ortk_xent_fwd_bwd(const float* logits, const int64_t* targets, in
                                  int32_t dl_dtype, int64_t ld_dl, ortk_stream stream) {
     return ortk::xent_rows(logits, targets, target_stride, T, weight, norm_dev, loss_dev, row_loss, rows, nullptr, V, ld, dlogits, dl_dtype,
                            ld_dl, ortk_s(stream));
+}
+
+extern "C" int ortk_xent_smooth_fwd_bwd(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight,
+                                        const float* norm_dev, float* loss_dev, float* row_loss, int64_t rows, int32_t V, int64_t ld,
+                                        void* dlogits, int32_t dl_dtype, int64_t ld_dl, float smoothing, ortk_stream stream) {
+    return ortk::xent_smooth_rows(logits, targets, target_stride, T, weight, norm_dev, loss_dev, row_loss, rows, nullptr, V, ld, dlogits,
+                                  dl_dtype, ld_dl, smoothing, ortk_s(stream));
 }
 
 extern "C" int ortk_log_softmax_bwd(const float* logp, const float* dlogp, int64_t ld_in, void* dlogits, int32_t dl_dtype,

@@ -173,6 +173,9 @@ int embed_bwd_rows(const int64_t* seq, int64_t seq_stride, const float* dout, fl
 int xent_rows(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight, const float* norm_dev,
               float* loss_dev, float* row_loss, int64_t rows, const int32_t* row_pos, int32_t V, int64_t ld, void* dlogits, int32_t dl_dtype,
               int64_t ld_dl, hipStream_t s);
+int xent_smooth_rows(const float* logits, const int64_t* targets, int64_t target_stride, int32_t T, const float* weight, const float* norm_dev,
+                     float* loss_dev, float* row_loss, int64_t rows, const int32_t* row_pos, int32_t V, int64_t ld, void* dlogits,
+                     int32_t dl_dtype, int64_t ld_dl, float smoothing, hipStream_t s);
 int64_t xent_scratch_floats(int64_t rows);
 int64_t sum_partials(int64_t n);
 int sum_fixed(const float* x, int64_t n, float* part, float* out_dev, hipStream_t s);

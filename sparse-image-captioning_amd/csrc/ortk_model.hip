@@ -1207,6 +1207,19 @@ extern "C" int ortk_loss(const ortk_config* cfg, const ortk_batch* bt, void* ws,
                      compact ? bt->row_pos : nullptr, cfg->vocab, w.ldv, w.dlogits, w.adt, w.ldv, ortk_s(stream));
 }
 
+extern "C" int ortk_loss_smooth(const ortk_config* cfg, const ortk_batch* bt, void* ws, size_t ws_bytes, const float* norm_dev,
+                                float* loss_dev, float smoothing, ortk_stream stream) {
+    if (int e = check_cfg(cfg)) return e;
+    if (int e = check_batch(cfg, bt, true)) return e;
+    if (!ws || !norm_dev || !loss_dev || !bt->tok_weight) return ORTK_EINVAL;
+    TrainWS w; carve_train(*cfg, bt->B, bt->S, bt->R, bt->T, ws, w);
+    if (w.bytes > ws_bytes) return ORTK_ENOSPC;
+    const bool compact = batch_compact(bt);
+    return xent_smooth_rows(w.logits, bt->seqs + 1, bt->seq_stride, bt->T, bt->tok_weight, norm_dev, loss_dev, w.row_loss,
+                            compact ? bt->Mc : w.Md, compact ? bt->row_pos : nullptr, cfg->vocab, w.ldv, w.dlogits, w.adt, w.ldv, smoothing,
+                            ortk_s(stream));
+}
+
 extern "C" int ortk_loss_external(const ortk_config* cfg, const ortk_batch* bt, void* ws, size_t ws_bytes, const float* logp,
                                   const float* dlogp, int64_t ldv, ortk_stream stream) {
     if (int e = check_cfg(cfg)) return e;

@@ -5,7 +5,7 @@
     zero_grad -> forward -> criterion -> backward -> clip_grad_value_(0.1) -> Adam(lr = Noam)       [one step]
 
 Everything between the batch and the updated parameters is HIP on flat arenas: ``ortk_forward`` (activations kept
-in the workspace), the fused criterion ``ortk_loss`` (log-probs are never materialised), ``ortk_backward`` into
+in the workspace), the fused criterion ``ortk_loss`` (``ortk_loss_smooth`` with label smoothing; log-probs are never materialised), ``ortk_backward`` into
 the flat gradient arena, ONE RCCL all-reduce of that arena when ``torch.distributed`` is initialised (one process
 per GPU, minibatch split by image; loss normalised by the GLOBAL mask sum), and ``ortk_adam_clip``.
 """
@@ -28,8 +28,14 @@ def noam_rate(step, d_model, factor, warmup):
 class NativeTrainer:
     def __init__(self, model, noamopt_factor=1.0, noamopt_warmup=20000, grad_clip=0.1, betas=(0.9, 0.98), eps=1e-9,
                  prune_supermask_lr=100.0, mask_eps=1e-2, sparsity_target=None, sparsity_weight=None, max_train_step=1,
-                 overlap_allreduce=None, keep_grads=False, allreduce_dtype=None):
+                 overlap_allreduce=None, keep_grads=False, allreduce_dtype=None, label_smoothing=0.0):
         L.require_gpu()
+        # XE criterion: 0 = LanguageModelCriterion, > 0 = LabelSmoothing(smoothing=...) (scripts/train_transformer.py:33-34); the SCST
+        # step keeps RewardCriterion either way
+        label_smoothing = float(label_smoothing)
+        if not (math.isfinite(label_smoothing) and 0.0 <= label_smoothing < 1.0):
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.label_smoothing = label_smoothing
         self.model = model
         self.dev = model._flat.device
         assert self.dev.type == "cuda", "move the model to the GPU first"
@@ -132,7 +138,7 @@ class NativeTrainer:
         self._enc_geom = (b.B, b.S, b.R, b.T, bool(train), int(seed))
         return int(mem)
 
-    def _fwd_bwd(self, batch, norm, train=True, seed=None, after_decoder_half=None, encoded=False):
+    def _fwd_bwd(self, batch, norm, train=True, seed=None, after_decoder_half=None, encoded=False, smoothing=0.0):
         """forward + fused criterion + backward into self.grads; returns the seed the dropout / mask draws used.
         `after_decoder_half()`: called between the two backward phases (every gradient at offsets >= _dec_off is final)."""
         m, lib = self.model, L.lib()
@@ -152,8 +158,12 @@ class NativeTrainer:
         # encoded: encode_for_update() has run phase 1 of this forward on this workspace (same parameters, mode and seed)
         L.check(lib.ortk_forward_phase(C.byref(m._ccfg), pptr, C.byref(batch), L.ptr(ws), ws.numel(), None, 0, int(train), seed,
                                        2 if encoded else 0, L.stream_ptr()), "ortk_forward")
-        L.check(lib.ortk_loss(C.byref(m._ccfg), C.byref(batch), L.ptr(ws), ws.numel(), L.ptr(norm), L.ptr(self.loss_dev),
-                              L.stream_ptr()), "ortk_loss")
+        if smoothing > 0.0:
+            L.check(lib.ortk_loss_smooth(C.byref(m._ccfg), C.byref(batch), L.ptr(ws), ws.numel(), L.ptr(norm), L.ptr(self.loss_dev),
+                                         smoothing, L.stream_ptr()), "ortk_loss_smooth")
+        else:
+            L.check(lib.ortk_loss(C.byref(m._ccfg), C.byref(batch), L.ptr(ws), ws.numel(), L.ptr(norm), L.ptr(self.loss_dev),
+                                  L.stream_ptr()), "ortk_loss")
         if self.overlap or after_decoder_half is not None:
             for phase in (1, 2):
                 L.check(lib.ortk_backward_phase(C.byref(m._ccfg), pptr, L.ptr(self.grads), C.byref(batch), L.ptr(ws), ws.numel(),
@@ -191,9 +201,10 @@ class NativeTrainer:
     # ------------------------------------------------------------------ steps
     def xe_step(self, data, train=True):
         """One XE step on ``data`` = {att_feats, boxes, att_masks, seqs, masks}; returns the loss (device scalar).
-        Loss = LanguageModelCriterion(model(**data), seqs[:,1:], masks[:,1:]) (train_transformer.py:70)."""
+        Loss = LanguageModelCriterion(model(**data), seqs[:,1:], masks[:,1:]) (train_transformer.py:70), or LabelSmoothing(...) of the
+        same arguments when the trainer was built with ``label_smoothing`` > 0 (the smoothed loss is what is returned)."""
         tok_w = data["masks"][:, 1:].contiguous().float()
-        return self._step(data, tok_w, tok_w, train)
+        return self._step(data, tok_w, tok_w, train, smoothing=self.label_smoothing)
 
     def scst_step(self, data, reward_fn, num_samples=5, baseline="greedy", train=True, sample="random", update_dropout=False,
                   sample_dropout=None, rollout_opt=None):
@@ -378,7 +389,7 @@ class NativeTrainer:
             return torch.from_numpy(sc_sample - sc_baseline).float()
         return fn
 
-    def _step(self, data, tok_weight, norm_mask, train, seed=None, encoded=False, rollouts=False):
+    def _step(self, data, tok_weight, norm_mask, train, seed=None, encoded=False, rollouts=False, smoothing=0.0):
         m = self.model
         self.step_count += 1
         if not self._grads_clean:
@@ -405,7 +416,7 @@ class NativeTrainer:
                 with torch.cuda.stream(self._opt_stream):
                     self._adam(m._flat[d0:m._n_train], self.grads[d0:], self.m[d0:], self.v[d0:], lr, self.eps, zero=not self.keep_grads)
         try:
-            seed = self._fwd_bwd(batch, self.norm_dev, train, seed, after_decoder_half=early, encoded=encoded)
+            seed = self._fwd_bwd(batch, self.norm_dev, train, seed, after_decoder_half=early, encoded=encoded, smoothing=smoothing)
         except BaseException:
             if self._opt_stream is not None:       # a decoder-half update may already be queued: never leave it racing the caller
                 torch.cuda.current_stream().wait_stream(self._opt_stream)
