@@ -596,10 +596,13 @@ int ortk_layernorm_bwd_dt(const void* dy, int32_t dy_dtype, const float* x, cons
 /* Geometry bias of BoxMultiHeadedAttention (relation_transformer.py:196-256,177-183,286):
  * out[l,b,h,i,j] = log(max(relu(WG[l,h].e_ij + bG[l,h]), 1e-6)).  wg[l]/bg[l] are per-layer device pointers
  * laid out (h,64)/(h).  dim_mat = the 8 fp32 wavelengths 1/1000^(k/8) as torch computes them; dim_mat = NULL selects the
- * non-trigonometric mode (embedding = the 4 log-ratios, WG laid out (h,4); ortk_box_embedding then writes (B,S,S,4)). */
+ * non-trigonometric mode (embedding = the 4 log-ratios, WG laid out (h,4); ortk_box_embedding then writes (B,S,S,4)).
+ * Limits: 0 <= L <= 16, H >= 1, S >= 1, B >= 0, no null pointer (else ORTK_EINVAL); B = 0 or L = 0 returns 0 and writes nothing. */
 int ortk_box_logbias_fwd(const float* boxes, const float* const* wg, const float* const* bg, const float* dim_mat,
                          float* out, int32_t L, int32_t B, int32_t S, int32_t H, ortk_stream stream);
-/* dscore (L,B,H,S,S) -> dwg[l] (H,64) += , dbg[l] (H) += . */
+/* dscore (L,B,H,S,S) -> dwg[l] (H,64) += , dbg[l] (H) += ((H,4) in the non-trigonometric mode).  The sums are added with float
+ * atomics: two calls agree to rounding, not bit for bit.  Limits: 0 <= L <= 16, 1 <= H <= 8 (the backward keeps one 8-head tile per
+ * pair), S >= 1, B >= 0, no null pointer (else ORTK_EINVAL); B = 0 or L = 0 returns 0 and writes nothing. */
 int ortk_box_logbias_bwd(const float* boxes, const float* const* wg, const float* const* bg, const float* dim_mat,
                          const float* dscore, float* const* dwg, float* const* dbg,
                          int32_t L, int32_t B, int32_t S, int32_t H, ortk_stream stream);
