@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 6      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 7      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -376,6 +376,7 @@ int ortk_set_tuning(const ortk_tuning* t);
 #define ORTK_DEC_STACK_SPLIT 16
 #define ORTK_DEC_SPLIT_SMALL 32
 #define ORTK_DEC_SPARSE_GATHER 64
+#define ORTK_DEC_STACK_FP8 128
 typedef struct ortk_decode_opts {
     int32_t beam_size;            /* 1 = greedy; >1 = beam search; <1 with num_random_sample > 0 = multinomial */
     int32_t num_random_sample;
@@ -419,6 +420,21 @@ typedef struct ortk_decode_opts {
      *                           that XCD's L2; any other placement takes write-through (sc1) stores — same results, ~1 us more per
      *                           exchange.  Set the flag when this decode has the GPU to itself (the Python model does unless told
      *                           otherwise);
+     *   ORTK_DEC_STACK_FP8      the plain (32-row) stack kernel on an FP8 weight stream: the decoder weights of this call are
+     *                           quantised on the device to OCP e4m3 bytes with one power-of-two scale per weight row and block of 512
+     *                           input columns (ortk_fp8_rows: the slice of a row one unit of the kernel consumes), streamed at half
+     *                           the bytes and converted to bf16 in registers (v_cvt_scalef32_pk_bf16_fp8) in front of the same
+     *                           MFMAs.  An e4m3 value times a power of two is a bf16 value, so the decode is BIT-IDENTICAL to
+     *                           ORTK_DEC_STACK on the dequantised weights (ortk_fp8_rows' `deq`).  Quantised: the six weight families
+     *                           of every decoder layer — packed self-attention Q|K|V, its output projection, the cross-attention
+     *                           query and output projections, both FFN matrices — shared layers (share_dec, ACORT) included.  NOT
+     *                           quantised: the encoder, the cross-attention K|V projection of the memory, embeddings, generator, all
+     *                           biases and LayerNorm parameters; activations and caches stay bf16.  Implies ORTK_DEC_STACK and is
+     *                           served wherever that flag is, at any row count; opt-in only — never chosen automatically.
+     *                           ORTK_EINVAL (ortk_decode_workspace_bytes: 0) in fp32 precision, with ORTK_DEC_UNFUSED,
+     *                           ORTK_DEC_SPARSE_STREAM, ORTK_DEC_SPARSE_GATHER, ORTK_DEC_STACK_SPLIT, ORTK_DEC_SPLIT_SMALL or
+     *                           ORTK_DEC_STACK_RB20, with a sparse plan, with `train`, and for a configuration the stack kernel does
+     *                           not serve;
      *   bits 8-15               measurement / tests only: skip self-attention (1) / cross-attention (2) / the FFN (4), no L2
      *                           prefetchers (8); column-split form: deal the members of a group over different XCDs (16), one member
      *                           of group 0 never arrives (32). */
@@ -706,6 +722,15 @@ int ortk_dropout_apply_rows(const float* x, void* y, int32_t y_dtype, int64_t ro
                             const int32_t* drop_rows, ortk_stream stream);
 /* fp32 -> bf16 copy (the working copy of the weight arena in precision 1). */
 int ortk_cast_bf16(const float* x, void* y, int64_t n, ortk_stream stream);
+/* Weight-only FP8 quantiser of a bf16 weight image (rows = output features, leading dimension ld elements, n_cols a multiple of 512):
+ * a scale group is one row x one block of 512 input columns.  Per group: amax = max |w|; e = the smallest integer with
+ * amax * 2^-e <= 448, found exactly on the bit pattern (0 for an all-zero group); q = e4m3fn(w * 2^-e), round to nearest even (the
+ * scaling is exact and nothing overflows; +-0 and values that round to zero keep their sign).  Outputs: the bytes q (rows, ldq), the
+ * scales 2^e as floats (rows, n_cols / 512) and, unless `deq` is NULL, the dequantised fp32 image q * 2^e (rows, ldd) — exactly what
+ * ORTK_DEC_STACK_FP8 multiplies by.  Finite weights assumed.  Deterministic (no atomics): two runs give the same bytes.
+ * Alignment: w16 and q 8 bytes, deq 16 bytes; ld and ldd multiples of 4, ldq of 8. */
+int ortk_fp8_rows(const void* w16, int64_t ld, int64_t rows, int64_t n_cols, uint8_t* q, int64_t ldq, float* scale, float* deq, int64_t ldd,
+                  ortk_stream stream);
 int ortk_fill(float* x, int64_t n, float value, ortk_stream stream);
 /* y[r, 0..cols) += x[r, 0..cols): x and y are column blocks of (rows, ld) matrices of `dtype` (0 fp32, 1 bf16) */
 int ortk_axpy_cols(const void* x, void* y, int32_t dtype, int64_t ld, int64_t rows, int32_t cols, ortk_stream stream);

@@ -105,7 +105,7 @@ class Tuning(C.Structure):
                 ("wgrad_group", C.c_int32), ("wgrad_group_splitk", C.c_int32), ("wgrad_group_wgs", C.c_int32), ("wgrad_group_tail", C.c_int32), ("feats_bf16", C.c_int32), ("ln_fuse", C.c_int32), ("samp_epilogue", C.c_int32), ("gemm_epilogue", C.c_int32)]
 
 
-DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_SPLIT_SMALL, DEC_SPARSE_GATHER = 1, 2, 4, 8, 16, 32, 64      # ortk_decode_opts.exec_flags
+DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_SPLIT_SMALL, DEC_SPARSE_GATHER, DEC_STACK_FP8 = 1, 2, 4, 8, 16, 32, 64, 128      # ortk_decode_opts.exec_flags
 
 
 class DecodeOpts(C.Structure):
@@ -227,6 +227,7 @@ SIGNATURES = {
     "ortk_dropout_apply_rows": (_I32, [_P, _P, _I32, _I64, _I32, _F, _U32, _P, _P]),
     "ortk_dropout_site_seed": (_U32, [_U64, _I32, _I32, _I32]),
     "ortk_cast_bf16": (_I32, [_P, _P, _I64, _P]),
+    "ortk_fp8_rows": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P, _P, _I64, _P]),
     "ortk_fill": (_I32, [_P, _I64, _F, _P]),
     "ortk_sum_scratch_floats": (_I64, [_I64]),
     "ortk_sum": (_I32, [_P, _I64, _P, _P, _P]),
@@ -250,7 +251,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 6      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 7      # include/ortk.h: ORTK_VERSION
 
 
 def lib():

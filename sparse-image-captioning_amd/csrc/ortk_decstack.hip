@@ -125,6 +125,77 @@ __device__ __forceinline__ void unit_gemm(f32x4 (&acc)[2][4], const char* A, con
     wp += 16 * KSTEP;
 }
 
+// ------------------------------------------------------------------------------------------------ fp8 weight stream
+// The same unit product with HALF the bytes per weight (ORTK_DEC_STACK_FP8): the stream holds OCP e4m3 bytes, one power-of-two
+// scale per weight row and unit (the slice of a row one unit consumes: ortk_fp8_rows), and a fragment becomes bf16 in registers —
+// v_cvt_scalef32_pk_bf16_fp8 turns two bytes into two bf16 values times the scale, four of them per fragment.  An e4m3 value times
+// a power of two is a bf16 value, so the MFMAs get exactly the operands the bf16 stream of the dequantised weights would give
+// them, in the same order: the executor is bit-identical to the dense stream on those weights.
+//
+// Stream of wave w: per unit 16 k-steps of 2 x 64 uint4; lane's uint4 p of k-step ks = its 8 bytes of column tile 2 p (.x .y)
+// and of column tile 2 p + 1 (.z .w), byte j = W_u[64 w + 16 nt + (lane & 15)][32 ks + 8 (lane >> 4) + j] — the fragment order of
+// stack_pack_kernel, 8 bytes per lane and fragment, two fragments per 16-byte load.  Behind all streams: per (wave, unit) 64 floats,
+// [lane & 15][nt] = the scale of that weight row (a lane's 8 weights of a fragment share one row: one scale per column tile).
+#ifndef SPD8_
+#define SPD8_ 8
+#endif
+constexpr int SPD8 = SPD8_;        // k-steps of fp8 fragments in flight per wave: the bytes in flight (and the registers) of the bf16 ring
+constexpr int KSTEP8 = 2 * FRAG;   // uint4 per k-step of one wave
+static_assert(16 % SPD8 == 0, "the ring turns a whole number of times per unit");
+__host__ __device__ inline int64_t fp8_stream_uint4(int L, int U) { return (int64_t)8 * L * U * 16 * KSTEP8 + (int64_t)SPD8 * KSTEP8; }   // + the ring's read-ahead
+struct Ring8 { uint4 f[SPD8][2]; f32x4 sc; };
+
+__device__ __forceinline__ void ring8_start(Ring8& r, const uint4* wp, const float* scp, int lane) {
+#pragma unroll
+    for (int s = 0; s < SPD8; ++s)
+#pragma unroll
+        for (int p = 0; p < 2; ++p) r.f[s][p] = wp[s * KSTEP8 + p * FRAG + lane];
+    r.sc = *reinterpret_cast<const f32x4*>(scp + 4 * (lane & 15));
+}
+// 8 e4m3 bytes x scale -> the bf16 MFMA fragment (exact)
+__device__ __forceinline__ bf16x8 fp8_frag(unsigned int lo, unsigned int hi, float scale) {
+    const bf16x2 v0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, false), v1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, scale, true);
+    const bf16x2 v2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, false), v3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, scale, true);
+    const uint4 u = make_uint4(__builtin_bit_cast(unsigned int, v0), __builtin_bit_cast(unsigned int, v1), __builtin_bit_cast(unsigned int, v2),
+                               __builtin_bit_cast(unsigned int, v3));
+    return __builtin_bit_cast(bf16x8, u);
+}
+__device__ __forceinline__ int fresh_lane_id() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+// unit_gemm on the fp8 stream: the same MFMAs in the same order.  scp = the scales of this (wave, unit); the next unit's are requested
+// at the top (NEXT) and arrive behind a whole unit of fragments.
+template <bool NEXT>
+__device__ __forceinline__ void unit_gemm_fp8(f32x4 (&acc)[2][4], const char* A, const uint4*& wp, const float*& scp, Ring8& r, int lane) {
+    const int m = lane & 15, kg = lane >> 4;
+    const f32x4 sc = r.sc;
+    if (NEXT) r.sc = *reinterpret_cast<const f32x4*>(scp + 64 + 4 * m);
+#pragma unroll 1
+    for (int it = 0; it < 16 / SPD8; ++it) {
+#pragma unroll
+        for (int s = 0; s < SPD8; ++s) {
+            const int ks = it * SPD8 + s;
+            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(A + img_off(m, 4 * ks + kg));
+            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(A + img_off(16 + m, 4 * ks + kg));
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                const uint4 v = r.f[s][nt >> 1];
+                const bf16x8 b = (nt & 1) ? fp8_frag(v.z, v.w, sc[nt]) : fp8_frag(v.x, v.y, sc[nt]);
+                acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a0, acc[0][nt], 0, 0, 0);
+                acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a1, acc[1][nt], 0, 0, 0);
+            }
+            if (NEXT || it < 16 / SPD8 - 1) {
+#pragma unroll
+                for (int p = 0; p < 2; ++p) r.f[s][p] = wp[(ks + SPD8) * KSTEP8 + p * FRAG + lane];
+            }
+        }
+    }
+    wp += 16 * KSTEP8;
+    scp += 64;
+}
+
 
 // ------------------------------------------------------------------------------------------------ sparse weight stream
 // The same unit product when the decoder weights are mostly zeros (the reference evaluates pruned checkpoints as dense
@@ -356,13 +427,16 @@ __device__ __forceinline__ void store_img(char* img, const f32x4 (&acc)[2][4], c
 
 // LayerNorm of the register-resident rows (transformer.py:338-341: a (x - mean) / (std_unbiased + eps) + b), two exchanges
 // of per-wave partial sums through LDS.  The caller puts a barrier between the result and its consumers.
-template <bool RAW>
+// LATE: gain and bias are requested behind the first exchange instead of up front (32 registers less while the row sums form).
+template <bool RAW, bool LATE = false>
 __device__ __forceinline__ void layer_norm(const f32x4 (&x)[2][4], const float* ga, const float* be, float eps, float* red1, float* red2,
                                            int wave, int lane, f32x4 (&y)[2][4]) {
 #pragma clang fp contract(off)
     f32x4 a4[4], b4[4];
-    load_cols(ga, wave, lane, a4);
-    load_cols(be, wave, lane, b4);
+    if constexpr (!LATE) {
+        load_cols(ga, wave, lane, a4);
+        load_cols(be, wave, lane, b4);
+    }
     const int m = lane & 15;
     float mean[2], rinv[2];
 #pragma unroll
@@ -376,6 +450,10 @@ __device__ __forceinline__ void layer_norm(const f32x4 (&x)[2][4], const float* 
         if (lane < 16) red1[(16 * mt + m) * 8 + wave] = s;
     }
     if constexpr (RAW) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); } else __syncthreads();
+    if constexpr (LATE) {
+        load_cols(ga, wave, lane, a4);
+        load_cols(be, wave, lane, b4);
+    }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const f32x4 p0 = *reinterpret_cast<const f32x4*>(red1 + (16 * mt + m) * 8), p1 = *reinterpret_cast<const f32x4*>(red1 + (16 * mt + m) * 8 + 4);
@@ -499,9 +577,12 @@ struct AttState {
 // workgroups only shorten the attention phases).  Rows RB .. 31 of the two MFMA row tiles do not exist: their operand reads
 // land in whatever follows the image in LDS, their accumulators are never stored.
 // GATHER (with SPARSE, RB <= 24): the units as per-column gather lists over transposed A images (above) instead of the scatter stream.
-template <bool SPARSE, int RB, bool GATHER = false>
+// FP8 (dense stream only): a.wpk is the stack_pack_fp8() image — e4m3 fragments and their scales — converted in registers.
+template <bool SPARSE, int RB, bool GATHER = false, bool FP8 = false>
 __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
     static_assert(!GATHER || (SPARSE && RB <= 24), "gather form: sparse stream, at most 24 rows");
+    static_assert(!FP8 || !SPARSE, "fp8 fragments: the dense stream");
+    constexpr int KSU = FP8 ? KSTEP8 : KSTEP;      // uint4 per k-step of one wave's stream
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int IMG = RB * SD * 2;  // bytes of one bf16 A image
     char* A0 = smem;                  // LayerNorm output / attention output: the A operand of the next projection
@@ -527,9 +608,9 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
             for (; spin < 4096 && __hip_atomic_load(a.progress + xcd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < base + u + 1 - STACK_AHEAD; ++spin)
                 __builtin_amdgcn_s_sleep(8);
             spin = spin >= 4096 ? 4096 : 0;
-            const unsigned int* src = reinterpret_cast<const unsigned int*>(a.wpk + ((int64_t)wave * a.L * U + u) * 16 * KSTEP) + lane * 32;
+            const unsigned int* src = reinterpret_cast<const unsigned int*>(a.wpk + ((int64_t)wave * a.L * U + u) * 16 * KSU) + lane * 32;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) sink += src[i * 64 * 32];          // 8 x (64 lanes x 128 B) = this wave's 64 KB of the unit
+            for (int i = 0; i < (FP8 ? 4 : 8); ++i) sink += src[i * 64 * 32];          // 8 x (64 lanes x 128 B) = this wave's 64 KB of the unit (fp8: 32 KB)
         }
         if (sink == 0x9E3779B1u) a.progress[8] = 1;                          // (keeps the loads)
         return;
@@ -538,7 +619,9 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
     int unit_no = a.t * a.L * U;
 // a fresh, opaque copy of the lane id per phase: without it the compiler hoists every lane-derived address of every phase
     // out of the layer loop and keeps ~60 of them alive (spilled) through the whole kernel
-#define STACK_FRESH_LANE() do { lane = lane0; asm volatile("" : "+v"(lane)); } while (0)
+    // (fp8 instance: the lane id is read afresh instead — its copy would be one more register alive through every phase, and that
+    // instance has none to spare: it must not spill)
+#define STACK_FRESH_LANE() do { if constexpr (FP8) lane = fresh_lane_id(); else { lane = lane0; asm volatile("" : "+v"(lane)); } } while (0)
 #define STACK_UNIT_BEGIN() do { ++unit_no; if (pace) __hip_atomic_store(a.progress + blockIdx.x, unit_no, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while (0)
     const int r0 = blockIdx.x * RB;
     const int m = lane & 15, q4 = lane >> 4;
@@ -564,8 +647,11 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         }
     }
     // dense stream state
-    const uint4* wp = a.wpk + (int64_t)wave * a.L * U * 16 * KSTEP;
+    const uint4* wp = a.wpk + (int64_t)wave * a.L * U * 16 * KSU;
     Ring ring;
+    // fp8 stream state: the ring and the scales of the wave's next unit
+    Ring8 ring8;
+    const float* scp = nullptr;
     // sparse stream state
     const uint2* sp = nullptr;
     cint_ptr nstp = nullptr;
@@ -592,6 +678,9 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(D + i * 1024 + lane * 16) = z4;
         if (lane < 16) *reinterpret_cast<uint4*>(D + 4096 + lane * 16) = z4;
         s_unit_cold(D, E, F, lane);
+    } else if constexpr (FP8) {
+        scp = reinterpret_cast<const float*>(a.wpk + fp8_stream_uint4(a.L, U)) + (int64_t)wave * a.L * U * 64;
+        ring8_start(ring8, wp, scp, lane);
     } else {
         ring_start(ring, wp, lane);
     }
@@ -601,21 +690,28 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         STACK_UNIT_BEGIN();                                                                            \
         if constexpr (GATHER) { const int np_ = *nstp++; unit_gather(ACC, (AIMG) == A0 ? PA : PH, GT, sp, np_, GE, lane); } \
         else if constexpr (SPARSE) { const int nst_ = *nstp++; unit_sparse<NEXT>(ACC, AIMG, D, sp, nst_, E, F, lane); } \
+        else if constexpr (FP8) unit_gemm_fp8<NEXT>(ACC, AIMG, wp, scp, ring8, lane);                   \
         else unit_gemm<NEXT>(ACC, AIMG, wp, ring, lane);                                               \
     } while (0)
 #define STACK_RESTART()                                                                                \
-    do { if constexpr (GATHER) gring_start(GE, sp, lane); else if constexpr (SPARSE) s_unit_cold(D, E, F, lane); else ring_start(ring, wp, lane); } while (0)
+    do { if constexpr (GATHER) gring_start(GE, sp, lane); else if constexpr (SPARSE) s_unit_cold(D, E, F, lane);      \
+         else if constexpr (FP8) ring8_start(ring8, wp, scp, lane); else ring_start(ring, wp, lane); } while (0)
 // gather form: a freshly published A image (behind the barrier that publishes it) gets its transposed planes
 #define STACK_PUBLISH(AIMG)                                                                            \
     do { if constexpr (GATHER) { build_planes<RB>(AIMG, (AIMG) == A0 ? PA : PH, tid); __syncthreads(); } } while (0)
 
 #define STACK_SYNC() __syncthreads()
+    // fp8 instance: a quarter of the residual rows waits in LDS (private 16-byte slots behind the LayerNorm exchange area) while an
+    // attention phase runs — the phases are the register peak of this kernel, and this instance must not spill
+    f32x4* park = reinterpret_cast<f32x4*>(smem + 4 * IMG + 2 * 32 * 8 * 4) + tid;
+#define STACK_PARK()   do { if constexpr (FP8) { park[0] = x[1][2]; park[512] = x[1][3]; } } while (0)
+#define STACK_UNPARK() do { if constexpr (FP8) { x[1][2] = park[0]; x[1][3] = park[512]; } } while (0)
     for (int l = 0; l < a.L; ++l) {
         const StackLayer& P = a.layer[l];
         f32x4 acc[2][4], y[2][4], bias[4];
         // ---- LayerNorm 0 -> A0
         STACK_FRESH_LANE();
-        layer_norm<false>(x, P.n0a, P.n0b, a.eps, red1, red2, wave, lane, y);
+        layer_norm<false, FP8>(x, P.n0a, P.n0b, a.eps, red1, red2, wave, lane, y);
         store_img_plain<RB>(A0, y, wave, lane);
         STACK_SYNC();
         STACK_PUBLISH(A0);
@@ -627,6 +723,7 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         STACK_SYNC();
         // ---- self-attention: wave w serves rows w, w + 8, w + 16, .. of the block over their cache rows + this position; o -> A0
         STACK_FRESH_LANE();
+        STACK_PARK();
         if (!(a.debug & 1)) {
             // The wave's SROWS rows run in lock-step, each with its own K / V registers: SROWS x SKB row loads of K and as
             // many of V are in flight, K of the next batch requested as soon as the scores have consumed this one's, V as
@@ -699,13 +796,14 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         STACK_PUBLISH(A0);
         // ---- output projection + residual, LayerNorm 1 -> A0
         STACK_FRESH_LANE();
+        STACK_UNPARK();
         STACK_RESTART();
         load_cols(P.bo, wave, lane, bias); zero(acc); STACK_UNIT(acc, A0, true);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) x[mt][nt] += acc[mt][nt] + bias[nt];
-        layer_norm<false>(x, P.n1a, P.n1b, a.eps, red1, red2, wave, lane, y);       // (its barriers: every wave is done reading A0)
+        layer_norm<false, FP8>(x, P.n1a, P.n1b, a.eps, red1, red2, wave, lane, y);       // (its barriers: every wave is done reading A0)
         store_img_plain<RB>(A0, y, wave, lane);
         STACK_SYNC();
         STACK_PUBLISH(A0);
@@ -715,6 +813,7 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         STACK_SYNC();
         // ---- cross-attention: chunks of up to XNR rows of one image, dealt round-robin to the waves; o -> A0
         STACK_FRESH_LANE();
+        STACK_PARK();
         if (!(a.debug & 2)) {
             const int last = min(r0 + RB, a.rows) - 1;
             const int img0 = r0 / a.per_img, img1 = last / a.per_img;
@@ -762,13 +861,14 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         STACK_PUBLISH(A0);
         // ---- output projection + residual, LayerNorm 2 -> A0
         STACK_FRESH_LANE();
+        STACK_UNPARK();
         STACK_RESTART();
         load_cols(P.cob, wave, lane, bias); zero(acc); STACK_UNIT(acc, A0, true);
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) x[mt][nt] += acc[mt][nt] + bias[nt];
-        layer_norm<false>(x, P.n2a, P.n2b, a.eps, red1, red2, wave, lane, y);
+        layer_norm<false, FP8>(x, P.n2a, P.n2b, a.eps, red1, red2, wave, lane, y);
         store_img_plain<RB>(A0, y, wave, lane);
         STACK_SYNC();
         STACK_PUBLISH(A0);
@@ -792,7 +892,7 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
     // ---- final LayerNorm -> bf16 rows for the generator
     STACK_FRESH_LANE();
     f32x4 y[2][4];
-    layer_norm<false>(x, a.fa, a.fb, a.eps, red1, red2, wave, lane, y);
+    layer_norm<false, FP8>(x, a.fa, a.fb, a.eps, red1, red2, wave, lane, y);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
         const int row = 16 * mt + (lane & 15), g = r0 + row;
@@ -804,6 +904,8 @@ __global__ __launch_bounds__(512) void decoder_stack_kernel(StackArgs a) {
         }
     }
 #undef STACK_SYNC
+#undef STACK_PARK
+#undef STACK_UNPARK
 #undef STACK_UNIT
 #undef STACK_RESTART
 #undef STACK_PUBLISH
@@ -839,6 +941,118 @@ size_t stack_packed_bytes(int L, int NC) {
 
 int stack_pack(const void* w16, void* wpk, const StackPack& t, hipStream_t s) {
     hipLaunchKernelGGL(stack_pack_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<const __bf16*>(w16), reinterpret_cast<uint4*>(wpk), t);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ fp8 quantiser and stream builder
+// The contract of ortk_fp8_rows (include/ortk.h), one wave per scale group (one weight row x 512 input columns, lane = 8 columns):
+// amax = max |w|; e = the smallest integer with amax 2^-e <= 448 (the largest e4m3 value), read off amax's bit pattern; q =
+// RNE_e4m3fn(w 2^-e), rounded in software on the fp32 bit pattern (the result must not depend on a conversion instruction's
+// treatment of subnormals); scale = 2^e.  Integer max, no atomics: the same bytes on every run.
+namespace {
+// e of a group from max |w| as bf16 bits without the sign
+__device__ __forceinline__ int fp8_group_exp(unsigned int amax) {
+    if (amax == 0) return 0;
+    int ue = (int)(amax >> 7) - 127;
+    unsigned int mant = amax & 0x7Fu;
+    if ((amax >> 7) == 0) {                       // a bf16 subnormal: mant 2^-133
+        const int p = 31 - __clz((int)mant);
+        ue = p - 133;
+        mant = (mant << (7 - p)) & 0x7Fu;
+    }
+    return ue - 8 + (mant > 0x60u ? 1 : 0);        // 448 = 1.75 x 2^8: mantissa 1100000
+}
+// x (|x| <= 448) -> e4m3fn byte, round to nearest even
+__device__ __forceinline__ unsigned int fp8_e4m3_rne(float x) {
+    const unsigned int u = __builtin_bit_cast(unsigned int, x), au = u & 0x7FFFFFFFu;
+    unsigned int q;
+    if (au < 0x3C800000u) q = (unsigned int)__builtin_rintf(__builtin_bit_cast(float, au) * 512.f);      // below 2^-6: multiples of 2^-9 (8 = the smallest normal)
+    else q = ((au + 0x7FFFFu + ((au >> 20) & 1u)) >> 20) - (120u << 3);                                    // 3 mantissa bits, exponent bias 127 -> 7
+    return ((u >> 24) & 0x80u) | q;
+}
+__device__ __forceinline__ float fp8_e4m3_value(unsigned int b) {
+    const int ex = (int)((b >> 3) & 15u), m = (int)(b & 7u);
+    const float v = ex ? ldexpf((float)(8 + m), ex - 10) : ldexpf((float)m, -9);
+    return (b & 0x80u) ? -v : v;
+}
+// the lane's 8 weights (bf16 pairs d[0..3]) of a group -> its 8 bytes; e = the group's exponent (the whole wave calls)
+__device__ __forceinline__ uint2 fp8_quant_group(const unsigned int (&d)[4], int& e) {
+    unsigned int amax = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) amax = max(amax, max(d[i] & 0x7FFFu, (d[i] >> 16) & 0x7FFFu));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = max(amax, (unsigned int)__shfl_xor((int)amax, o, 64));
+    e = fp8_group_exp(amax);
+    unsigned int out[2] = {0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float w = (j & 1) ? hi_f(d[j >> 1]) : lo_f(d[j >> 1]);
+        out[j >> 2] |= fp8_e4m3_rne(ldexpf(w, -e)) << (8 * (j & 3));
+    }
+    return make_uint2(out[0], out[1]);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void fp8_rows_kernel(const unsigned short* __restrict__ w16, int64_t ld, int64_t rows, int nblk, unsigned char* __restrict__ q, int64_t ldq,
+                                                      float* __restrict__ scale, float* __restrict__ deq, int64_t ldd) {
+    const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (item >= rows * nblk) return;
+    const int64_t row = item / nblk;
+    const int col = (int)(item % nblk) * 512 + lane * 8;
+    const uint2* src = reinterpret_cast<const uint2*>(w16 + row * ld + col);
+    const uint2 lo = src[0], hi = src[1];
+    const unsigned int d[4] = {lo.x, lo.y, hi.x, hi.y};
+    int e;
+    const uint2 b = fp8_quant_group(d, e);
+    *reinterpret_cast<uint2*>(q + row * ldq + col) = b;
+    if (lane == 0) scale[item] = ldexpf(1.f, e);
+    if (deq) {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = ldexpf(fp8_e4m3_value(((j < 4 ? b.x : b.y) >> (8 * (j & 3))) & 0xFFu), e);
+        float4* dst = reinterpret_cast<float4*>(deq + row * ldd + col);
+        dst[0] = make_float4(v[0], v[1], v[2], v[3]);
+        dst[1] = make_float4(v[4], v[5], v[6], v[7]);
+    }
+}
+
+// One wave per (layer position, unit, output row r): the row's 512 inputs of that unit are ONE scale group; lane j holds columns
+// 8 j .. 8 j + 7 = k-step j / 4, k-group j % 4 of the fragment order (unit_gemm_fp8).
+__global__ __launch_bounds__(256) void stack_pack_fp8_kernel(const __bf16* __restrict__ w16, uint2* __restrict__ st, float* __restrict__ sc, StackPack t) {
+    const int U = 6 + 2 * t.NC;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (item >= t.L * U * SD) return;
+    const int r = item & (SD - 1), u = (item >> 9) % U, l = (item >> 9) / U;
+    int64_t base; int ld;
+    if (u < 3)       { base = t.off[l][0] + (int64_t)u * SD * SD; ld = SD; }
+    else if (u < 6)  { base = t.off[l][u - 2]; ld = SD; }
+    else {
+        const int c = (u - 6) >> 1;
+        if (((u - 6) & 1) == 0) { base = t.off[l][4] + (int64_t)c * SD * SD; ld = SD; }
+        else                    { base = t.off[l][5] + (int64_t)c * SD; ld = t.NC * SD; }
+    }
+    const uint4 f = *reinterpret_cast<const uint4*>(w16 + base + (int64_t)r * ld + 8 * lane);
+    const unsigned int d[4] = {f.x, f.y, f.z, f.w};
+    int e;
+    const uint2 b = fp8_quant_group(d, e);
+    const int w = r >> 6, nt = (r >> 4) & 3, m = r & 15, ks = lane >> 2, kg = lane & 3;
+    const int64_t wu = ((int64_t)w * t.L + l) * U + u;
+    st[(((wu * 16 + ks) * 2 + (nt >> 1)) * 64 + kg * 16 + m) * 2 + (nt & 1)] = b;
+    if (lane == 0) sc[wu * 64 + m * 4 + nt] = ldexpf(1.f, e);
+}
+
+size_t stack_packed_fp8_bytes(int L, int NC) {
+    const int U = 6 + 2 * NC;
+    return (size_t)fp8_stream_uint4(L, U) * sizeof(uint4) + ((size_t)8 * L * U * 64 + 64) * sizeof(float);     // (+ the next unit's scales past the end)
+}
+
+int stack_pack_fp8(const void* w16, void* wpk8, const StackPack& t, hipStream_t s) {
+    const int U = 6 + 2 * t.NC;
+    float* sc = reinterpret_cast<float*>(reinterpret_cast<uint4*>(wpk8) + fp8_stream_uint4(t.L, U));
+    hipLaunchKernelGGL(stack_pack_fp8_kernel, dim3((unsigned)ortk_cdiv(t.L * U * SD, 4)), dim3(256), 0, s, reinterpret_cast<const __bf16*>(w16),
+                       reinterpret_cast<uint2*>(wpk8), sc, t);
     ORTK_CHECK_LAUNCH();
     return 0;
 }
@@ -1860,9 +2074,9 @@ static int stack_tp_launch(const StackArgs& b, hipStream_t s) {
     return 0;
 }
 
-template <bool SPARSE, int RB, bool GATHER = false>
+template <bool SPARSE, int RB, bool GATHER = false, bool FP8 = false>
 static int stack_launch(const StackArgs& b, bool pf, hipStream_t s) {
-    constexpr size_t lds = (size_t)4 * RB * SD * 2 + 2 * 32 * 8 * sizeof(float) + (GATHER ? 2 * GPL + 8 * GTB : SPARSE ? 8 * SDBUF : 0);
+    constexpr size_t lds = (size_t)4 * RB * SD * 2 + 2 * 32 * 8 * sizeof(float) + (GATHER ? 2 * GPL + 8 * GTB : SPARSE ? 8 * SDBUF : FP8 ? 2 * 512 * 16 : 0);
     static_assert(lds <= 160 * 1024, "LDS budget");
     // (per device: the attribute belongs to the function on ONE device; a process that drives several GPUs sets it on each)
     static std::mutex mu;
@@ -1872,16 +2086,17 @@ static int stack_launch(const StackArgs& b, bool pf, hipStream_t s) {
     {
         std::lock_guard<std::mutex> g(mu);
         if (!done[dev]) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_stack_kernel<SPARSE, RB, GATHER>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decoder_stack_kernel<SPARSE, RB, GATHER, FP8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return (int)e;
             done[dev] = true;
         }
     }
-    hipLaunchKernelGGL((decoder_stack_kernel<SPARSE, RB, GATHER>), dim3((unsigned)(b.nblocks + (pf ? 8 : 0))), dim3(512), lds, s, b);
+    hipLaunchKernelGGL((decoder_stack_kernel<SPARSE, RB, GATHER, FP8>), dim3((unsigned)(b.nblocks + (pf ? 8 : 0))), dim3(512), lds, s, b);
     return 0;
 }
 
-int stack_step(const StackArgs& a, hipStream_t s) {
+int stack_step(const StackArgs& a, hipStream_t s, bool fp8) {
+    if (fp8 && (a.sstream || a.tp || a.rb == 20 || a.drop_p > 0.f || !a.wpk)) return ORTK_EINVAL;      // (the 32-row dense kernel only)
     if (a.rows < 1 || a.S < 1 || a.S > 128 || a.t < 0 || a.t >= 64 || a.per_img < 1 || a.L < 1 || a.L > STACK_MAXL || a.NC < 1) return ORTK_EINVAL;
     const bool sparse = a.sstream != nullptr;
     // (the sparse stream's fragment buffers leave LDS for 20-row images.  Whole-image 30-row blocks — with 5 beams a 32-row block cuts
@@ -1898,7 +2113,7 @@ int stack_step(const StackArgs& a, hipStream_t s) {
     ProfMark pm;
     if (ortk_prof_active()) {
         const double U = 6 + 2 * a.NC, imgs = (double)ortk_cdiv(a.rows, a.per_img);
-        const double wbytes = U * SD * SD * (sparse ? 0.05 * 4.0 : 2.0);       // (sparse: priced at the 95 % of BASELINE configs[4])
+        const double wbytes = U * SD * SD * (sparse ? 0.05 * 4.0 : fp8 ? 1.0 : 2.0);       // (sparse: priced at the 95 % of BASELINE configs[4])
         // cached keys / values: every row's t positions — or, with a counter of the UNIQUE rows the beams of this pass reference
         // (StackArgs.uniq_slot: beams share ancestors through the ancestry table), that count — plus the appended position per row
         const bool uq = a.uniq_slot > 0 && a.kvidx;
@@ -1920,6 +2135,7 @@ int stack_step(const StackArgs& a, hipStream_t s) {
     else if (sparse && a.gather) rc = stack_launch<true, 20, true>(b, pf, s);
     else if (sparse) rc = stack_launch<true, 20>(b, pf, s);
     else if (rb == 20) rc = stack_launch<false, 20>(b, pf, s);
+    else if (fp8) rc = stack_launch<false, 32, false, true>(b, pf, s);
     else rc = stack_launch<false, 32>(b, pf, s);
     prof_end(pm, s);
     if (rc) return rc;
@@ -1928,3 +2144,17 @@ int stack_step(const StackArgs& a, hipStream_t s) {
 }
 
 }  // namespace ortk
+
+// Weight-only fp8 quantiser (include/ortk.h): the scale groups of the decoder stack's fp8 weight stream.
+extern "C" int ortk_fp8_rows(const void* w16, int64_t ld, int64_t rows, int64_t n_cols, uint8_t* q, int64_t ldq, float* scale, float* deq, int64_t ldd,
+                             ortk_stream stream) {
+    if (!w16 || !q || !scale || rows < 1 || n_cols < 512 || n_cols % 512 || ld < n_cols || ldq < n_cols || (deq && ldd < n_cols)) return ORTK_EINVAL;
+    // (8-byte loads of the weights and stores of the bytes, 16-byte stores of the dequantised image)
+    if (ld % 4 || ldq % 8 || (deq && ldd % 4) || ((uintptr_t)w16 & 7) || ((uintptr_t)q & 7) || ((uintptr_t)deq & 15)) return ORTK_EINVAL;
+    const int64_t items = rows * (n_cols / 512);
+    if (items > ((int64_t)1 << 32)) return ORTK_EINVAL;
+    hipLaunchKernelGGL(ortk::fp8_rows_kernel, dim3((unsigned)ortk_cdiv(items, 4)), dim3(256), 0, ortk_s(stream), reinterpret_cast<const unsigned short*>(w16), ld,
+                       rows, (int)(n_cols / 512), q, ldq, scale, deq, ldd);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}

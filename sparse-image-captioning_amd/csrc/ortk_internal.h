@@ -102,7 +102,7 @@ struct StackLayer {
 };
 struct StackArgs {
     StackLayer layer[STACK_MAXL];
-    const uint4* wpk;              // stack_pack() image of the decoder weights (dense stream)
+    const uint4* wpk;              // stack_pack() image of the decoder weights (dense stream; stack_pack_fp8() image with stack_step(fp8))
     const uint2* sstream;          // sparse stream (sstack_pack): per wave, steps of 64 lanes x 2 scatter entries
     int32_t gather;                // the sparse stream holds per-column gather lists (gstack_pack) instead: decoder_stack_kernel<true, 20, true>
     const int32_t* snst;           //   [8][L * U] steps of every (wave, unit) (multiples of 4)
@@ -147,7 +147,11 @@ constexpr int TP_ERR_TIMEOUT = 1;          // a member of an exchange group did 
 struct StackPack { int64_t off[STACK_MAXL][6]; int32_t L, NC; };   // element offsets of wqkv, wo, cqw, cow, w1, w2 per layer
 size_t stack_packed_bytes(int L, int NC);
 int stack_pack(const void* w16, void* wpk, const StackPack& t, hipStream_t s);
-int stack_step(const StackArgs& a, hipStream_t s);
+// fp8: a.wpk is the stack_pack_fp8() image (e4m3 fragments + per-row power-of-two scales, converted to bf16 in registers): the
+// 32-row dense kernel only
+int stack_step(const StackArgs& a, hipStream_t s, bool fp8 = false);
+size_t stack_packed_fp8_bytes(int L, int NC);
+int stack_pack_fp8(const void* w16, void* wpk8, const StackPack& t, hipStream_t s);
 // column-split form: G (0 = not served), weight image bytes, exchange buffer bytes, flag ints for a decode of `rows` rows
 int stack_tp_degree(int64_t rows);
 size_t stack_tp_packed_bytes(int L, int NC, int G);

@@ -1717,7 +1717,7 @@ struct DecodeWS {
                                                                // decode attention kernels take them (kv16), fp32 otherwise
     int64_t* it; int32_t *unfinished, *last_step;
     int32_t *bseq[2], *kvidx[2], *done_seq, *done_len, *done_cnt; float *blp[2], *cum, *done_lp; double* done_p;
-    void* wpk = nullptr;               // decoder weights in the stack kernel's streaming order (stack path, dense stream)
+    void* wpk = nullptr;               // decoder weights in the stack kernel's streaming order (stack path, dense stream: bf16 or fp8 fragments)
     int32_t* progress = nullptr;       // pace-maker counters of the stack kernel's L2 prefetchers
     SStackBufs ss{};                   // the sparse stream and its tables (stack path, sparse stream)
     int tp = 0;                        // column-split stack kernel: workgroups per group (0 = off), its weight image,
@@ -1754,7 +1754,7 @@ static int split_degree(bool dense_stack, int32_t flags, int64_t rows) {
     return ((flags & ORTK_DEC_SPLIT_SMALL) && !(flags & ORTK_DEC_STACK) && G >= 4) ? G : 0;     // the small decodes only (8 or 4 per group)
 }
 static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, void* base, DecodeWS& w, bool stack = false, bool sstream = false,
-                         bool train = false, int tp = 0, bool greedy_rows = false) {
+                         bool train = false, int tp = 0, bool greedy_rows = false, bool fp8 = false) {
     const int64_t d = c.d_model, ff = c.d_ff, H = c.n_heads, L = c.n_layers, T = c.seq_len;
     // bf16 K / V storage: only when both decode attention kernels that understand it will be the ones dispatched
     w.kvdt = (c.precision && H == 8 && d == 512 && S > 8 && S <= 48 && T <= 32 && K <= 16) ? ORTK_BF16 : ORTK_F32;
@@ -1798,7 +1798,10 @@ static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, v
         w.tp_xbuf = reinterpret_cast<char*>(b.take_bytes(stack_tp_xbuf_bytes(rows, (int)(ff / 512))));
         w.tp_flag = b.take<int32_t>((int64_t)stack_tp_groups(rows) * TP_FLAG_STRIDE);
         w.progress = b.take<int32_t>(16);
-    } else if (stack && !sstream) { w.wpk = b.take_bytes(stack_packed_bytes((int)L, (int)(ff / 512))); w.progress = b.take<int32_t>(16); }
+    } else if (stack && !sstream) {
+        w.wpk = b.take_bytes(fp8 ? stack_packed_fp8_bytes((int)L, (int)(ff / 512)) : stack_packed_bytes((int)L, (int)(ff / 512)));
+        w.progress = b.take<int32_t>(16);
+    }
     if (stack && sstream) {
         const size_t nb = sstack_bytes((int)L, (int)(ff / 512), nullptr, nullptr);
         void* p = b.take_bytes(nb);
@@ -1837,10 +1840,18 @@ static int decode_K(const ortk_decode_opts* o) {
 // Which executor serves a decode call.  Train-mode rows (ortk_decode_opts.train) run on the column-split stack kernel with at least 4
 // workgroups per group (its dropout sites, ortk_decstack.hip) or on the unfused executor; eval-mode (greedy) rows beside them
 // (`with_greedy`) only on the former.  ok = false: the option combination is not served (ORTK_EINVAL).
-struct DecodePlan { bool ok, stack, sstream; int split; bool gather = false; };
+struct DecodePlan { bool ok, stack, sstream; int split; bool gather = false; bool fp8 = false; };
 static DecodePlan plan_decode(const ortk_config& cfg, int B, int K, const ortk_decode_opts* o) {
     DecodePlan p{true, false, false, 0};
     const int64_t rows = (int64_t)B * K;
+    if (o->exec_flags & ORTK_DEC_STACK_FP8) {
+        // the fp8 weight stream (ortk.h): the plain dense stack kernel wherever ORTK_DEC_STACK is served, and nothing else — no
+        // other executor stands in for it
+        const int32_t other = ORTK_DEC_UNFUSED | ORTK_DEC_SPARSE_STREAM | ORTK_DEC_SPARSE_GATHER | ORTK_DEC_STACK_SPLIT | ORTK_DEC_SPLIT_SMALL | ORTK_DEC_STACK_RB20;
+        p.ok = !(o->exec_flags & other) && !o->sparse && !o->train && stack_ok(cfg, rows, ORTK_DEC_STACK);
+        p.stack = p.fp8 = p.ok;
+        return p;
+    }
     p.stack = stack_ok(cfg, rows, o->exec_flags) && !o->sparse;
     p.sstream = p.stack && (o->exec_flags & ORTK_DEC_SPARSE_STREAM);
     p.gather = p.sstream && (o->exec_flags & ORTK_DEC_SPARSE_GATHER);
@@ -1860,7 +1871,7 @@ extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B,
     const DecodePlan pl = plan_decode(*cfg, B, K, o);
     if (!pl.ok) return 0;
     DecodeWS w; carve_decode(*cfg, B, S, K, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
-                             pl.split, o->with_greedy != 0);
+                             pl.split, o->with_greedy != 0, pl.fp8);
     return w.bytes;
 }
 
@@ -1997,7 +2008,7 @@ static int decoder_stack_step(const Ctx& c, const Offsets& o, const StepBufs& w,
         a.tp_launch = t;                 // one launch per position: the exchange counters keep running through the decode
         a.tp_xtile = (int64_t)stack_tp_xtile_bytes(cfg->d_ff / 512);
     }
-    TRY(stack_step(a, c.s));
+    TRY(stack_step(a, c.s, (flags & ORTK_DEC_STACK_FP8) != 0));
     return gen_gemm(c, o, w, ORTK_BF16, rows);
 }
 
@@ -2024,7 +2035,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const int split = pl.split;
     const bool greedy_rows = op->train && op->with_greedy;         // (=> stack)
     if (greedy_rows && (!att_feats || (!boxes && !cfg->no_box))) return ORTK_EINVAL;      // their eval-mode encoder pass runs here
-    DecodeWS w; carve_decode(*cfg, B, S, K, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows);
+    DecodeWS w; carve_decode(*cfg, B, S, K, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows, pl.fp8);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
     hipStream_t s = ortk_s(stream);
     TRY(fill_i32(w.status, 64, 0, s));
@@ -2049,7 +2060,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
             TRY(fill_i32(w.tp_flag, (int64_t)stack_tp_groups((int64_t)B * K) * TP_FLAG_STRIDE, 0, s));
             TRY(fill_i32(w.progress, 16, 0, s));
         } else {
-            TRY(stack_pack(w.w16, w.wpk, tp, s));
+            TRY(pl.fp8 ? stack_pack_fp8(w.w16, w.wpk, tp, s) : stack_pack(w.w16, w.wpk, tp, s));
             TRY(fill_i32(w.progress, 16, 0, s));
         }
     }

@@ -572,7 +572,8 @@ class RelationTransformerModel(CaptionModelBase):
             assert o.beam_size >= 1, f"Beam size must be >= 1, saw {o.beam_size}"    # transformer.py:514
             assert o.beam_size <= self.vocab_size                                    # transformer.py:482
             K = o.beam_size
-        # executor choice (ortk_decode_opts.exec_flags): opt["executor"] = "auto" | "unfused" | "stack" | "sparse_stream";
+        # executor choice (ortk_decode_opts.exec_flags): opt["executor"] = "auto" | "unfused" | "stack" | "sparse_stream" | "stack_fp8" ..;
+        # "stack_fp8" (the stack kernel on FP8-quantised decoder weights, fp8_dequantized_decoder_state) is opt-in only: never "auto"
         # ORTK_DEC_STACK=0 / 2 in the environment (read here, on the host side, per call) = "unfused" / "stack"
         ex = opt.get("executor", {"0": "unfused", "2": "stack", "3": "stack_split"}.get(os.environ.get("ORTK_DEC_STACK", ""), "auto"))
         if ex == "auto" and getattr(self, "_sparse_stream", False):
@@ -584,8 +585,72 @@ class RelationTransformerModel(CaptionModelBase):
         o.exec_flags = {"auto": small, "unfused": L.DEC_UNFUSED, "stack": L.DEC_STACK, "sparse_stream": L.DEC_SPARSE_STREAM,
                         "stack_rb20": L.DEC_STACK | L.DEC_STACK_RB20, "stack_split": L.DEC_STACK | L.DEC_STACK_SPLIT,
                         "sparse_stream_rb20": L.DEC_SPARSE_STREAM | L.DEC_STACK_RB20,
-                        "sparse_gather": L.DEC_SPARSE_STREAM | L.DEC_SPARSE_GATHER}[ex] | (int(opt.get("stack_debug", 0)) & 0xFF) << 8
+                        "sparse_gather": L.DEC_SPARSE_STREAM | L.DEC_SPARSE_GATHER,
+                        "stack_fp8": L.DEC_STACK | L.DEC_STACK_FP8}[ex] | (int(opt.get("stack_debug", 0)) & 0xFF) << 8
+        if ex == "stack_fp8":
+            self._check_fp8_executor(o)
         return o, K, ex
+
+    def _check_fp8_executor(self, o):
+        """``executor="stack_fp8"`` is served where the plain stack kernel is and nowhere else (ortk.h: ORTK_DEC_STACK_FP8); every
+        refusal names its reason."""
+        c = self._ccfg
+        why = None
+        if not self.precision:
+            why = "it needs mixed precision (precision='bf16'): the fp32 parity mode has no stack kernel"
+        elif o.train:
+            why = "train-mode sampling runs the column-split stack kernel or the unfused executor"
+        elif getattr(self, "_sparse_min", None) is not None:
+            why = "a sparse plan is enabled (enable_sparse_kernels): the FP8 stream is a dense stream"
+        elif not (c.d_model == 512 and c.n_heads == 8 and c.d_ff % 512 == 0 and c.d_ff // 512 <= 8 and c.share_att_dec == 0
+                  and c.n_layers <= 8 and c.seq_len <= 64):
+            why = ("the decoder stack kernel serves d_model 512, 8 heads, d_ff a multiple of 512 up to 4096, at most 8 layers, "
+                   "captions of at most 64 tokens and no share_att_decoder")
+        if why:
+            raise ValueError(f'executor="stack_fp8" is not served here: {why}')
+
+    @torch.no_grad()
+    def fp8_dequantized_decoder_state(self):
+        """``{state_dict key: fp32 tensor}`` of the weights ``executor="stack_fp8"`` multiplies by: the six weight families of every
+        decoder layer (self-attention Q, K, V and output projection, cross-attention query and output projection, both FFN
+        matrices; shared layers under every position's key) after the bf16 cast of the mixed-precision path and the FP8 round
+        trip of ``ortk_fp8_rows`` (e4m3, one power-of-two scale per row and block of 512 input columns).  Loaded over the model's
+        own state, ``executor="stack"`` then decodes bit-for-bit what ``"stack_fp8"`` decodes on the original one.  Everything else
+        (encoder, cross-attention K / V projections, embeddings, generator, biases, LayerNorm) is not quantised and not listed."""
+        L.require_gpu()
+        lib = L.lib()
+        self._eff_params_ptr(False, 0)
+        eff = self._eff_params_tensor()
+        dev = eff.device
+        w16 = torch.empty(self._n_train, dtype=torch.bfloat16, device=dev)
+        L.check(lib.ortk_cast_bf16(L.ptr(eff), L.ptr(w16), self._n_train, L.stream_ptr()), "ortk_cast_bf16")
+        root = "core." if self.NO_BOX else "model."
+        fams = (".self_attn.linears.0.weight", ".self_attn.linears.1.weight", ".self_attn.linears.2.weight", ".self_attn.linears.3.weight",
+                ".src_attn.linears.0.weight", ".src_attn.linears.3.weight", ".feed_forward.w_1.weight", ".feed_forward.w_2.weight")
+        if self._ccfg.share_att_dec != 0:
+            raise ValueError("fp8_dequantized_decoder_state: share_att_decoder models have no FP8 executor")
+        out = {}
+        for e in self._entries:
+            name = e["name"]
+            if not (name.startswith(root + "decoder.layers.") and name.endswith(fams)):
+                continue
+            n, k = e["shape"]
+            if k % 512:
+                raise ValueError(f"fp8_dequantized_decoder_state: {name} has {k} input columns, not a multiple of 512")
+            q = torch.empty(n, k, dtype=torch.uint8, device=dev)
+            sc = torch.empty(n, k // 512, device=dev)
+            deq = torch.empty(n, k, device=dev)
+            L.check(lib.ortk_fp8_rows(C.c_void_p(w16.data_ptr() + 2 * e["offset"]), k, n, k, L.ptr(q), k, L.ptr(sc), L.ptr(deq), k,
+                                      L.stream_ptr()), "ortk_fp8_rows")
+            out[name] = deq
+        # a shared position is the same module as the position it shares: the same tensor under its own key
+        pre = root + "decoder.layers."
+        for l in range(self.num_layers):
+            src = self._ccfg.share_dec[l]
+            if src > 0:
+                for kname in [k for k in out if k.startswith(f"{pre}{src - 1}.")]:
+                    out[f"{pre}{l}." + kname[len(f"{pre}{src - 1}."):]] = out[kname]
+        return out
 
     def decode_supported(self, B, S, opt, att_max_len=None):
         """Whether ``mode="sample"`` serves this option combination for B images of S regions (e.g. train-mode rollouts with the
