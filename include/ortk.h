@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 7      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 8      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -463,6 +463,26 @@ typedef struct ortk_decode_opts {
      * its own encoder pass (att_feats / boxes may be NULL).  With `train` it must be the TRAIN-mode memory under drop_seed
      * (ortk_forward_phase(train = 1, seed = drop_seed, phase 1)); the eval-mode rows of `with_greedy` still take att_feats / boxes. */
     const void* memory;
+    /* multinomial only (num_random_sample > 0): TRUNCATED sampling, CaptionModel.sample_next_word's "top<k>" / "top<p>" methods
+     * (caption_model.py:228-268).  At most one of the two is set; 0 / 0 = the full distribution, as before.
+     *   top_k >= 1      the draw is taken among the top_k best candidates of the row;
+     *   0 < top_p < 1   ... among the shortest prefix of the candidates whose soft-max(logits / temperature) mass reaches top_p: an
+     *                   entry is kept iff the mass strictly before it is < top_p (at least one is; all are if rounding keeps the
+     *                   total below top_p).
+     * Candidates: every token but the previous one under decoding_constraint (t > 0), which counts towards neither k nor any mass.
+     * Order: larger logit first, the lower token id on equal logits — exact, ties included; the kept set is a prefix of it.  The
+     * token is the arg-max over the kept set of logp / temperature + Gumbel(seed, t, hash row, token), the noise of the plain
+     * multinomial decode: top_k >= vocab reproduces that decode bit for bit (as run with ortk_tuning.samp_epilogue = 0).  The greedy
+     * rows of `with_greedy` are not truncated.
+     * logprob_out holds the log-prob of the token under the FULL distribution at temperature 1, exactly as the plain multinomial
+     * decode stores it — NOT the reference's log-prob under the truncated, tempered distribution (sample_next_word's return value,
+     * which nothing on this path consumes): SCST recomputes its differentiable log-probs in the teacher-forced pass either way.
+     * Served in both precisions, by every executor, with `train`, `with_greedy` and a sparse plan; the generator's logit rows are
+     * stored and read back by the truncating step (the sampling epilogue of ortk_tuning.samp_epilogue is not taken).
+     * ORTK_EINVAL (ortk_decode_workspace_bytes: 0): without num_random_sample > 0, both set, top_k < 0, top_p outside [0, 1),
+     * cfg->vocab > 10 240 (the row is held in registers: ortk_sample_truncate). */
+    int32_t top_k;
+    float   top_p;
 } ortk_decode_opts;
 
 size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o);
@@ -692,6 +712,18 @@ int ortk_embed_bwd(const int64_t* seq, int64_t seq_stride, const float* dout, fl
 /* In-place log_softmax over the first V columns of (rows, ld) (OutputEmbedding, transformer.py:412-413);
  * logits are first multiplied by `scale` (1/temperature). */
 int ortk_log_softmax(float* x, int64_t rows, int32_t V, int64_t ld, float scale, ortk_stream stream);
+/* The cut of truncated sampling (ortk_decode_opts.top_k / top_p), row by row, by the device function of the decode's sampling step:
+ * logits (rows, ld) raw generator logits, columns V..ld never read; banned (rows) int64 or NULL: the column that is no candidate
+ * (-1: none).  Exactly one of top_k >= 1, 0 < top_p < 1.  Candidates ordered by larger logit, then lower column; the kept set is the
+ * prefix described at ortk_decode_opts.  Per row: kept = entries kept, (thr, thr_col) = logit and column of the LAST kept entry —
+ * column v is kept iff v != banned and (z[v] > thr or (z[v] == thr and v <= thr_col)) — and kept_mass = the fp32
+ * soft-max(z / temperature) mass of the kept set over the candidates (both modes).  A row without candidates (V = 1, banned = 0):
+ * kept 0, thr -inf, thr_col -1, kept_mass 0.  fast_exp: 1 = v_exp_f32 (what the decode uses in mixed precision), 0 = libm expf.
+ * Exact and deterministic: integer counts, fp32 sums in a fixed order, no atomics — two runs give the same bytes.
+ * ORTK_EINVAL: V < 1, V > 10 240, ld < V, temperature <= 0, top_k < 0, top_p outside [0, 1), both or neither of top_k / top_p. */
+int ortk_sample_truncate(const float* logits, int64_t rows, int32_t V, int64_t ld, float temperature, int32_t top_k, float top_p,
+                         const int64_t* banned, int32_t fast_exp, int32_t* kept, float* thr, int32_t* thr_col, float* kept_mass,
+                         ortk_stream stream);
 /* Fused cross-entropy on logits (rows, ld): *loss_dev = -sum logp[target]*w/norm (LanguageModelCriterion / RewardCriterion,
  * utils/losses.py:15-43); dlogits (rows, ld_dl; fp32 or bf16; may alias logits when fp32 with ld_dl == ld) <- dLoss/dlogits,
  * zero in the pad columns.  The sum is DETERMINISTIC: every row's term goes to row_loss[row] and one workgroup adds them in a

@@ -565,6 +565,218 @@ __global__ __launch_bounds__(256) void sample_step_fused_kernel(SampleState st, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ truncated sampling (top-k / nucleus)
+// The kept set of a row is a PREFIX of the total order of its candidates (larger logit first, lower column on equal logits; the banned
+// column is no candidate): entry e is kept iff mu{entries strictly better than e} < lambda, with mu = count and lambda = min(top_k,
+// candidates) for top-k, mu = soft-max(z / temperature) mass and lambda = top_p for the nucleus (caption_model.py:252-257).  mu is an
+// integer count or an fp32 sum taken in ONE fixed order whatever the set (thread-sequential over the 40 registers with the entries
+// outside the set as +0, xor tree over the wave, the four waves in order), so it is monotone along the order — fl(a + b) is monotone in
+// both arguments — and two runs give the same bits.  The cut is found without a sort: a bit-wise descent over the order-preserving
+// uint32 image of the logit (32 block-wide measures: the largest key T with mu{key >= T} >= lambda), then, only where several
+// candidates share that logit, 14 more over the column.  No atomics, no global scratch.
+struct TruncCut { uint32_t key; int col; int kept; float mass; };       // last kept entry (key, col); entries kept; their mass
+
+// order-preserving image of a float (-0 counts as +0, as in the float compare)
+__device__ __forceinline__ uint32_t trunc_key(float x) {
+    const uint32_t b = __float_as_uint(x + 0.f);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float trunc_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+__device__ __forceinline__ bool trunc_in(uint32_t key, int v, const TruncCut& c) { return key > c.key || (key == c.key && v <= c.col); }
+
+// block-wide reduction that leaves the result in every thread; the two halves of `sh` alternate (`ph`), so one barrier per call is
+// enough: the half call n writes was last read by call n - 2, which every thread has left before it passes the barrier of call n - 1
+template <typename T, typename F>
+__device__ __forceinline__ T blk_all(T v, F f, uint32_t* sh, int& ph) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = f(v, __shfl_xor(v, o, 64));
+    uint32_t* b = sh + ((ph++ & 1) << 2);
+    if ((threadIdx.x & 63) == 0) b[threadIdx.x >> 6] = __builtin_bit_cast(uint32_t, v);
+    __syncthreads();
+    T r = __builtin_bit_cast(T, b[0]);
+    for (int w = 1; w < 4; ++w) r = f(r, __builtin_bit_cast(T, b[w]));
+    return r;
+}
+
+// key[] (out): trunc_key of every entry.  A column that is no candidate (past V, or banned) counts as a logit of -inf: below every
+// finite logit in the key order, and of weight exp(-inf) = 0.  w: the soft-max(z / temperature) weights of the candidates (the
+// nucleus measures them; top-k forms them for kept_mass alone: 40 exponentials beside a descent of 32 rounds).  Block-uniform result.
+template <int NPT, bool FASTEXP>
+__device__ __forceinline__ TruncCut trunc_select(const float (&z)[NPT], uint32_t (&key)[NPT], int V, int prev, float temperature, int top_k,
+                                                 float top_p, uint32_t* sh, int& ph) {
+    const int tid = threadIdx.x;
+    const auto iadd = [](int a, int b) { return a + b; };
+    const auto fadd = [](float a, float b) { return a + b; };
+    const auto imax = [](int a, int b) { return a > b ? a : b; };
+    const auto umin = [](uint32_t a, uint32_t b) { return a < b ? a : b; };
+    constexpr uint32_t KEY_NONE = 0x007FFFFFu;          // trunc_key(-inf)
+    float w[NPT];
+    int nc = 0;
+    float m = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+        const int v = tid + 256 * u;
+        const bool cand = v < V && v != prev;
+        w[u] = cand ? z[u] : -INFINITY;
+        key[u] = trunc_key(w[u]);
+        nc += cand ? 1 : 0;
+        m = fmaxf(m, w[u]);
+    }
+    const int ncand = blk_all(nc, iadd, sh, ph);
+    TruncCut cut{0xFFFFFFFFu, -1, 0, 0.f};
+    if (ncand == 0) return cut;
+    const float mxc = blk_all(m, [](float a, float b) { return fmaxf(a, b); }, sh, ph);
+    float s = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) { w[u] = exp_sel<FASTEXP>((w[u] - mxc) / temperature); s += w[u]; }
+    const float tot = blk_all(s, fadd, sh, ph);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) w[u] = w[u] / tot;
+    const bool by_count = top_k > 0;
+    const int kk = top_k < ncand ? top_k : ncand;
+    // mu{pred} < lambda
+    const auto below = [&](auto pred) -> bool {
+        if (by_count) {
+            int c = 0;
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) c += pred(u) ? 1 : 0;
+            return blk_all(c, iadd, sh, ph) < kk;
+        }
+        float a = 0.f;
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) a += pred(u) ? w[u] : 0.f;
+        return blk_all(a, fadd, sh, ph) < top_p;
+    };
+    // (top-k: the kk best candidates have finite keys, so T ends above KEY_NONE and no trial at or below it is ever accepted)
+    uint32_t T = 0;
+    for (int b = 31; b >= 0; --b) {
+        const uint32_t trial = T | (1u << b);
+        if (!below([&](int u) { return key[u] >= trial; })) T = trial;
+    }
+    int C = 256 * NPT - 1;
+    if (T == 0) {
+        // not even the whole row reaches top_p (fp32 rounding of a total of 1): everything is kept
+        uint32_t k = 0xFFFFFFFFu;
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) if (key[u] > KEY_NONE) k = umin(k, key[u]);
+        T = blk_all(k, umin, sh, ph);
+    } else {
+        int c = 0;
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) c += key[u] == T;
+        if (blk_all(c, iadd, sh, ph) > 1) {
+            // several candidates carry the cut's logit: the largest column C whose entry still has mu{strictly better} < lambda.
+            // tc: the column of an entry at the cut's logit; -1 for a better entry (before every column), past the row for a worse one
+            int tc[NPT];
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) tc[u] = key[u] == T ? tid + 256 * u : key[u] > T ? -1 : 256 * NPT;
+            C = 0;
+            for (int b = 13; b >= 0; --b) {
+                const int trial = C | (1 << b);
+                if (below([&](int u) { return tc[u] < trial; })) C = trial;
+            }
+        }
+    }
+    int lc = -1, kept = 0; float km = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (key[u] == T && tid + 256 * u <= C) lc = tid + 256 * u;      // (columns ascend with u)
+    cut.key = T; cut.col = blk_all(lc, imax, sh, ph);
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+        const bool in = trunc_in(key[u], tid + 256 * u, cut);
+        kept += in ? 1 : 0;
+        km += in ? w[u] : 0.f;
+    }
+    cut.kept = blk_all(kept, iadd, sh, ph);
+    cut.mass = blk_all(km, fadd, sh, ph);
+    return cut;
+}
+
+// sample_step_fused_kernel with the draw restricted to the kept set of the row: same statistics (the stored log-prob is that of the
+// FULL distribution at temperature 1), same hash row, same bookkeeping; with top_k >= V bit-identical to it.  The noise is evaluated
+// for the kept entries only.  Greedy rows (with_greedy) take the plain arg-max.
+template <int NPT, bool FASTEXP = false>
+__global__ __launch_bounds__(256) void sample_step_trunc_kernel(SampleState st, const float* __restrict__ logits, int t, int top_k, float top_p) {
+    __shared__ float sh_red[4];
+    __shared__ float red_v[4], red_l[4];
+    __shared__ int red_i[4];
+    __shared__ uint32_t sh_sel[8];
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* lp = logits + (int64_t)row * st.ldv;
+    float z[NPT];
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; z[u] = v < st.V ? lp[v] : 0.f; }
+    const int prev = (st.decoding_constraint && t > 0) ? (int)st.seq[(int64_t)row * st.L + t - 1] : -1;
+    const bool is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
+    const bool samp = st.sample && !is_greedy;
+    const int64_t grow = st.row_offset + row;
+    const int hrow = (int)(st.greedy_stride > 0 ? grow - grow / st.greedy_stride - 1 : grow);
+    float m = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) m = fmaxf(m, z[u]);
+    const float mx = blk_max(m, sh_red);
+    float sum = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) sum += exp_sel<FASTEXP>(z[u] - mx);
+    sum = blk_sum(sum, sh_red);
+    const float lse = logf(sum);
+    uint32_t key[NPT];
+    TruncCut cut{1u, 256 * NPT, 0, 0.f};        // every candidate (greedy rows)
+    int ph = 0;
+    if (samp) cut = trunc_select<NPT, FASTEXP>(z, key, st.V, prev, st.temperature, top_k, top_p, sh_sel, ph);
+    float mv = -INFINITY, ml = 0.f; int mi = 0x7FFFFFFF;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) {
+        const int v = tid + 256 * u;
+        if (v >= st.V || v == prev) continue;
+        if (samp && !trunc_in(key[u], v, cut)) continue;
+        const float l = (z[u] - mx) - lse;
+        float x = l;
+        if (samp) x = x / st.temperature + gumbel<FASTEXP>(st.seed, t, hrow, v);
+        if (better(x, v, mv, mi)) { mv = x; mi = v; ml = l; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mv, o, 64), ol = __shfl_xor(ml, o, 64); const int oi = __shfl_xor(mi, o, 64);
+        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; ml = ol; }
+    }
+    if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; red_l[wave] = ml; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w)
+            if (better(red_v[w], red_i[w], mv, mi)) { mv = red_v[w]; mi = red_i[w]; ml = red_l[w]; }
+        const int unf = st.unfinished[row];
+        st.it[row] = mi;
+        st.seq[(int64_t)row * st.L + t] = unf ? mi : 0;
+        st.lp[(int64_t)row * st.L + t] = ml;
+        const int now = unf && (mi != st.eos);
+        st.unfinished[row] = now;
+        int32_t* last = st.last_step + (is_greedy ? 1 : 0);
+        if (unf && !now) atomicMax(last, t);
+        if (now && t == st.L - 1) atomicMax(last, t);
+    }
+}
+
+// ortk_sample_truncate: the cut of every row, by the device function of the step kernel
+template <int NPT, bool FASTEXP>
+__global__ __launch_bounds__(256) void sample_truncate_kernel(const float* __restrict__ logits, int V, int64_t ld, float temperature, int top_k, float top_p,
+                                                              const int64_t* __restrict__ banned, int32_t* __restrict__ kept, float* __restrict__ thr,
+                                                              int32_t* __restrict__ thr_col, float* __restrict__ kept_mass) {
+    __shared__ uint32_t sh_sel[8];
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const float* lp = logits + (int64_t)row * ld;
+    float z[NPT];
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; z[u] = v < V ? lp[v] : 0.f; }
+    const int prev = banned ? (int)banned[row] : -1;
+    uint32_t key[NPT];
+    int ph = 0;
+    const TruncCut cut = trunc_select<NPT, FASTEXP>(z, key, V, prev, temperature, top_k, top_p, sh_sel, ph);
+    if (tid == 0) {
+        kept[row] = cut.kept; thr[row] = cut.kept ? trunc_unkey(cut.key) : -INFINITY; thr_col[row] = cut.col; kept_mass[row] = cut.mass;
+    }
+}
+
 // The sampling step on the generator's own epilogue output (ortk_gemm_args.tile_samp + tile_stats): per row and block of 64 logits the
 // best Gumbel-max candidate {key, column, logit} and the soft-max partials {max, sum exp}.  One wave per row: arg-max over the blocks
 // (same total order as the row kernels: larger key, lower column on a tie), log-sum-exp from the partials, log-prob of the chosen token,
@@ -686,6 +898,14 @@ int sample_step(const SampleState& st, const float* logp, int32_t t, hipStream_t
     ORTK_CHECK_LAUNCH();
     return 0;
 }
+int sample_step_trunc(const SampleState& st, const float* logits, int32_t t, hipStream_t s, bool fast_exp, int32_t top_k, float top_p) {
+    if (st.V > 256 * 40 || (top_k > 0) == (top_p > 0.f) || top_k < 0 || !(top_p >= 0.f && top_p < 1.f)) return ORTK_EINVAL;
+    if (st.rows == 0) return 0;
+    if (fast_exp) hipLaunchKernelGGL((sample_step_trunc_kernel<40, true>), dim3((unsigned)st.rows), dim3(256), 0, s, st, logits, t, top_k, top_p);
+    else hipLaunchKernelGGL(sample_step_trunc_kernel<40>, dim3((unsigned)st.rows), dim3(256), 0, s, st, logits, t, top_k, top_p);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
 int sample_combine(const SampleState& st, const float* gstats, const float* gsamp, int32_t nblk, int32_t t, hipStream_t s, bool fast_exp) {
     if (st.rows == 0) return 0;
     const dim3 grid((unsigned)((st.rows + 3) / 4));
@@ -702,3 +922,17 @@ int sample_finalize(const SampleState& st, hipStream_t s) {
 }
 
 }  // namespace ortk
+
+extern "C" int ortk_sample_truncate(const float* logits, int64_t rows, int32_t V, int64_t ld, float temperature, int32_t top_k, float top_p,
+                                    const int64_t* banned, int32_t fast_exp, int32_t* kept, float* thr, int32_t* thr_col, float* kept_mass,
+                                    ortk_stream stream) {
+    if (!logits || !kept || !thr || !thr_col || !kept_mass || rows < 0 || rows > 0x7FFFFFFF) return ORTK_EINVAL;
+    if (V < 1 || V > 256 * 40 || ld < V || !(temperature > 0.f) || top_k < 0 || !(top_p >= 0.f && top_p < 1.f)) return ORTK_EINVAL;
+    if ((top_k > 0) == (top_p > 0.f)) return ORTK_EINVAL;          // exactly one of the two
+    if (rows == 0) return 0;
+    hipStream_t s = ortk_s(stream);
+    if (fast_exp) hipLaunchKernelGGL((ortk::sample_truncate_kernel<40, true>), dim3((unsigned)rows), dim3(256), 0, s, logits, (int)V, ld, temperature, (int)top_k, top_p, banned, kept, thr, thr_col, kept_mass);
+    else hipLaunchKernelGGL((ortk::sample_truncate_kernel<40, false>), dim3((unsigned)rows), dim3(256), 0, s, logits, (int)V, ld, temperature, (int)top_k, top_p, banned, kept, thr, thr_col, kept_mass);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}

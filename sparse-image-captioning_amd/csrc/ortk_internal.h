@@ -87,6 +87,8 @@ struct SampleState {
 int sample_init(const SampleState& st, int32_t bos, hipStream_t s);
 // fused = true: `logp` holds raw logits (V <= 10 240) and the log-soft-max is taken inside the step
 int sample_step(const SampleState& st, const float* logp, int32_t t, hipStream_t s, bool fused = false, bool fast_exp = false);
+// the fused step with the draw restricted to the top-k / nucleus prefix of the row (ortk_decode_opts.top_k / top_p; V <= 10 240)
+int sample_step_trunc(const SampleState& st, const float* logits, int32_t t, hipStream_t s, bool fast_exp, int32_t top_k, float top_p);
 // the same step from the generator GEMM's sampling epilogue (ortk_gemm_args.tile_stats + tile_samp): the logit rows are never materialised
 int sample_combine(const SampleState& st, const float* gstats, const float* gsamp, int32_t nblk, int32_t t, hipStream_t s, bool fast_exp);
 int sample_finalize(const SampleState& st, hipStream_t s);

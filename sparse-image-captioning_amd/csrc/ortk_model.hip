@@ -1832,6 +1832,13 @@ static int encode_impl(const ortk_config* cfg, const float* params, const float*
     return encoder_forward(c, o, att_feats, boxes, att_masks, B, S, w.x0, w.logbias, ep, memory_out, ORTK_F32, w.st);      // (fp32 memory out: no chains)
 }
 
+// truncated sampling (ortk_decode_opts.top_k / top_p): 0 off, 1 on, -1 an option combination that is refused
+static int decode_trunc(const ortk_config* cfg, const ortk_decode_opts* o) {
+    if (o->top_k == 0 && o->top_p == 0.f) return 0;
+    if (o->top_k < 0 || !(o->top_p >= 0.f && o->top_p < 1.f) || (o->top_k > 0 && o->top_p > 0.f)) return -1;
+    if (o->num_random_sample <= 0 || cfg->vocab > 256 * 40) return -1;
+    return 1;
+}
 static int decode_K(const ortk_decode_opts* o) {
     if (o->num_random_sample > 0) return o->beam_size < 1 ? o->num_random_sample + (o->with_greedy ? 1 : 0) : -1;
     return o->beam_size >= 1 ? o->beam_size : -1;
@@ -1867,7 +1874,7 @@ static DecodePlan plan_decode(const ortk_config& cfg, int B, int K, const ortk_d
 extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o) {
     if (check_cfg(cfg) || !o || B < 1 || S < 1) return 0;
     const int K = decode_K(o);
-    if (K < 1) return 0;
+    if (K < 1 || decode_trunc(cfg, o) < 0) return 0;
     const DecodePlan pl = plan_decode(*cfg, B, K, o);
     if (!pl.ok) return 0;
     DecodeWS w; carve_decode(*cfg, B, S, K, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
@@ -2023,6 +2030,8 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     if (B < 1 || S < 1 || S > 128) return ORTK_EINVAL;
     const int K = decode_K(op);
     if (K < 1) return ORTK_EINVAL;   // the reference asserts the same option combinations (transformer.py:509,514)
+    const int trunc = decode_trunc(cfg, op);
+    if (trunc < 0) return ORTK_EINVAL;
     const bool beam = op->num_random_sample <= 0 && op->beam_size > 1;
     if (beam && (K > 8 || K > cfg->vocab)) return ORTK_EINVAL;
     if (op->temperature <= 0.f) return ORTK_EINVAL;
@@ -2140,7 +2149,8 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     // Sampling decodes in mixed precision on the dense generator: the generator GEMM's epilogue emits the Gumbel-max candidates and the
     // soft-max partials of every 64-logit block and a combine step picks the token — the (rows, V) fp32 logits are never stored
     // (the conditions are the statistics epilogue's: ortk_gemm; tuning().samp_epilogue = 0 keeps the logit rows and sample_step)
-    const bool samp_epi = !beam && w.gsamp && w.gstats && tuning().samp_epilogue && !op->sparse && !c.ell_f && A == ORTK_BF16 && d % 64 == 0 && w.ldv % 128 == 0 &&
+    // (truncated sampling needs the whole row: the logit rows are stored and sample_step_trunc reads them back)
+    const bool samp_epi = !beam && !trunc && w.gsamp && w.gstats && tuning().samp_epilogue && !op->sparse && !c.ell_f && A == ORTK_BF16 && d % 64 == 0 && w.ldv % 128 == 0 &&
                           w.ldv / 64 <= 256 && op->temperature > 0.f;
     int uniq_slot = 0;          // (profiling only) counter of the unique cache rows the NEXT pass references, filled by this pass's beam step
     TRY(c.wait_ev(sstream_done));
@@ -2166,6 +2176,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
         if (beam && stack && ortk_prof_active()) { int ix = -1; bs.uniq = prof_slot(&ix); uniq_slot = ix + 1; }
         if (beam) TRY(beam_step(bs, w.logits, t, s, true, scale, fast_exp));     // log-soft-max fused into the candidate scan
         else if (samp_epi) TRY(sample_combine(ss, w.gstats, w.gsamp, (int32_t)(w.ldv / 64), t, s, fast_exp));      // the generator's epilogue has the candidates
+        else if (trunc) TRY(sample_step_trunc(ss, w.logits, t, s, fast_exp, op->top_k, op->top_p));
         else if (V <= 256 * 40) TRY(sample_step(ss, w.logits, t, s, true, fast_exp));     // log-soft-max fused (scale is 1 on this branch)
         else {
             TRY(ortk_log_softmax(w.logits, rows, V, w.ldv, scale, stream));

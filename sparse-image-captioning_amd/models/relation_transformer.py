@@ -544,6 +544,24 @@ class RelationTransformerModel(CaptionModelBase):
         kind, alpha = s.split("_")
         return {"wu": 1, "avg": 2}[kind], float(alpha)
 
+    @staticmethod
+    def _parse_sample_method(method):
+        """``opt["sample_method"]`` (CaptionModel.sample_next_word, caption_model.py:246-266) -> (top_k, top_p); (0, 0.0) is plain
+        multinomial sampling.  Parsed as the reference does: ``float(method[3:])``, and 0 < x < 1 means nucleus."""
+        if method is None or method == "sample":
+            return 0, 0.0
+        if not isinstance(method, str) or not method.startswith("top"):
+            raise ValueError(f'sample_method={method!r}: expected "sample", "top<k>" (an integer k >= 1) or "top<p>" (0 < p < 1)')
+        try:
+            x = float(method[3:])
+        except ValueError:
+            raise ValueError(f'sample_method={method!r}: {method[3:]!r} is not a number') from None
+        if 0 < x < 1:
+            return 0, x
+        if 1 <= x < 2 ** 31 and x == int(x):
+            return int(x), 0.0
+        raise ValueError(f'sample_method={method!r}: the number must be an integer k >= 1 (top-k) or 0 < p < 1 (nucleus)')
+
     def _decode_opts(self, opt):
         """``opt`` dict of ``mode="sample"`` (transformer.py:471-561) -> (ortk_decode_opts without the sparse plan / memory, rows
         per image K, executor name)."""
@@ -565,6 +583,15 @@ class RelationTransformerModel(CaptionModelBase):
             # (with_greedy beside train-mode rows: the column-split stack kernel only — an unserved combination raises below)
             assert o.num_random_sample > 0, "train-mode sampling: multinomial rollouts"
             o.train, o.drop_seed = 1, int(opt["drop_seed"]) & 0xFFFFFFFFFFFFFFFF
+        # truncated sampling (ortk_decode_opts.top_k / top_p): sampling rows only; the row is held in registers (<= 10 240 tokens)
+        o.top_k, o.top_p = self._parse_sample_method(opt.get("sample_method"))
+        if o.top_k or o.top_p:
+            if o.num_random_sample <= 0:
+                raise ValueError(f'sample_method={opt["sample_method"]!r} truncates multinomial sampling: it needs num_random_sample > 0 '
+                                 "(greedy and beam decodes do not sample)")
+            if self.vocab_size > 10240:
+                raise ValueError(f'sample_method={opt["sample_method"]!r}: the truncating sampling kernel serves vocabularies of at most '
+                                 f"10240 tokens, this model has {self.vocab_size}")
         if o.num_random_sample > 0:
             assert o.beam_size < 1, f"Beam size must be < 1, saw {o.beam_size}"      # transformer.py:509
             K = o.num_random_sample + o.with_greedy
