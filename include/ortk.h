@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 8      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 9      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -377,8 +377,10 @@ int ortk_set_tuning(const ortk_tuning* t);
 #define ORTK_DEC_SPLIT_SMALL 32
 #define ORTK_DEC_SPARSE_GATHER 64
 #define ORTK_DEC_STACK_FP8 128
+#define ORTK_MAX_BEAM 32      /* widest beam search ortk_decode serves: 2 .. 8 beams run the narrow selection step, 9 .. 32 the wide one */
 typedef struct ortk_decode_opts {
-    int32_t beam_size;            /* 1 = greedy; >1 = beam search; <1 with num_random_sample > 0 = multinomial */
+    int32_t beam_size;            /* 1 = greedy; >1 = beam search, at most ORTK_MAX_BEAM beams (and at most cfg->vocab): wider is ORTK_EINVAL
+                                   * and ortk_decode_workspace_bytes 0; <1 with num_random_sample > 0 = multinomial */
     int32_t num_random_sample;
     float   temperature;
     int32_t decoding_constraint;  /* forbid repeating the previous token */
@@ -437,7 +439,8 @@ typedef struct ortk_decode_opts {
      *                           not serve;
      *   bits 8-15               measurement / tests only: skip self-attention (1) / cross-attention (2) / the FFN (4), no L2
      *                           prefetchers (8); column-split form: deal the members of a group over different XCDs (16), one member
-     *                           of group 0 never arrives (32). */
+     *                           of group 0 never arrives (32); beam decodes of every width run the wide selection step (64: ignored
+     *                           by the stack kernels). */
     int32_t exec_flags;
     /* multinomial only: also decode ONE greedy row per image in the same pass (the SCST baseline of
      * utils/training.py:220-237): K = num_random_sample + 1, row 0 of each image is the arg-max decode, rows 1.. are
@@ -724,6 +727,15 @@ int ortk_log_softmax(float* x, int64_t rows, int32_t V, int64_t ld, float scale,
 int ortk_sample_truncate(const float* logits, int64_t rows, int32_t V, int64_t ld, float temperature, int32_t top_k, float top_p,
                          const int64_t* banned, int32_t fast_exp, int32_t* kept, float* thr, int32_t* thr_col, float* kept_mass,
                          ortk_stream stream);
+/* One selection step of the beam search for B images through the device function of the wide beam step.
+ * Image i owns rows [i*q, (i+1)*q) of `logits` (row stride ld >= V; columns >= V are never read); q = 1 | b.
+ * fused = 0: `logits` holds log-probs, value = cum[row] + logits[row][v] (one fp32 add); fused = 1: raw logits, value =
+ * cum[row] + log_softmax(logits[row] * scale)[v] with the exact expf.  prev (may be NULL): B*q tokens that are no candidates.
+ * Candidates rank by larger value, then lower flat index row * V + v (-inf below every finite value, by index among itself).
+ * Out, in rank order: val (B, b) fp32, parent (B, b) int32 (row inside the image), token (B, b) int32.  1 <= b <= ORTK_MAX_BEAM,
+ * at ANY b (this is the wide code's test hook); ORTK_EINVAL for b > q * V, q not in {1, b}, null pointers. */
+int ortk_beam_select(const float* logits, int64_t ld, const float* cum, const int32_t* prev, int32_t B, int32_t q, int32_t b,
+                     int32_t V, int32_t fused, float scale, float* val, int32_t* parent, int32_t* token, ortk_stream stream);
 /* Fused cross-entropy on logits (rows, ld): *loss_dev = -sum logp[target]*w/norm (LanguageModelCriterion / RewardCriterion,
  * utils/losses.py:15-43); dlogits (rows, ld_dl; fp32 or bf16; may alias logits when fp32 with ld_dl == ld) <- dLoss/dlogits,
  * zero in the pad columns.  The sum is DETERMINISTIC: every row's term goes to row_loss[row] and one workgroup adds them in a

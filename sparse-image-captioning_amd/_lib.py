@@ -105,6 +105,7 @@ class Tuning(C.Structure):
                 ("wgrad_group", C.c_int32), ("wgrad_group_splitk", C.c_int32), ("wgrad_group_wgs", C.c_int32), ("wgrad_group_tail", C.c_int32), ("feats_bf16", C.c_int32), ("ln_fuse", C.c_int32), ("samp_epilogue", C.c_int32), ("gemm_epilogue", C.c_int32)]
 
 
+MAX_BEAM = 32      # include/ortk.h: ORTK_MAX_BEAM
 DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_SPLIT_SMALL, DEC_SPARSE_GATHER, DEC_STACK_FP8 = 1, 2, 4, 8, 16, 32, 64, 128      # ortk_decode_opts.exec_flags
 
 
@@ -218,6 +219,7 @@ SIGNATURES = {
     "ortk_embed_bwd": (_I32, [_P, _I64, _P, _P, _I64, _I32, _I32, _F, _U32, _P]),
     "ortk_log_softmax": (_I32, [_P, _I64, _I32, _I64, _F, _P]),
     "ortk_sample_truncate": (_I32, [_P, _I64, _I32, _I64, _F, _I32, _F, _P, _I32, _P, _P, _P, _P, _P]),
+    "ortk_beam_select": (_I32, [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
     "ortk_xent_scratch_floats": (_I64, [_I64]),
     "ortk_xent_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _P]),
     "ortk_xent_smooth_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _F, _P]),
@@ -252,7 +254,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 8      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 9      # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -337,6 +337,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
         }
         __syncthreads();
     }
+    // (beam_step_wide_kernel carries a copy of everything from here to the end of this kernel: a change goes to both)
     // histories, ancestry table, next tokens.  Every copy is spread over the whole workgroup: one thread per beam walking
     // its t history entries and t+1 ancestry entries was a chain of ~50 dependent global round trips (the tail of this kernel
     // grew with t and dominated it: 118 us per step at 1 024 images x 5 beams).
@@ -412,10 +413,341 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
     }
 }
 
+// ------------------------------------------------------------------------------------------------ wide beam step (9 .. 32 beams)
+// The same contract as beam_step_kernel for any b <= ORTK_MAX_BEAM, as kernel instances of its own (the narrow instances keep
+// their registers, LDS and code).  Selection, one workgroup per image:
+//   * row statistics and candidate values by the narrow kernel's expressions in the same mode (blk_max / blk_sum over the
+//     256-strided elements, or the generator's 64-logit block statistics under STATS): at b <= 8 the two kernels agree bit for bit;
+//     (logit * scale - max is formed with ONE rounding everywhere in this kernel, __fmaf_rn, as log_softmax_kernel's single-use
+//     product is contracted; in beam_step_kernel's register-resident rows the product also feeds the row maximum and is rounded
+//     first — only at a temperature other than 1 can that last bit differ between the two kernels);
+//   * pruning threshold: every row leaves 32 disjoint group maxima (8 lanes x the lane's strided elements, the excluded token
+//     left out).  The b largest group maxima seen SO FAR in the image are carried from row to row (a 64-entry rank merge per
+//     row); they are b distinct admissible candidates, so the smallest of them is a lower bound of the image's b-th
+//     best, and it only rises: row 0 (the best beam) pays ~b ln b list entries, later rows only what can still win;
+//   * elements >= the threshold go to an LDS list of WCAP entries; b rounds of block-wide arg-max (value, then flat index)
+//     pick the exact winners in rank order;
+//   * overflow (massive ties): b passes over the rows, each taking the best candidate that ranks strictly behind the
+//     previous winner — exact for any input, no list, no per-thread state.
+// No atomically ordered data reaches the result: list positions are arbitrary, the arg-max order is total.
+constexpr int WMAXB = ORTK_MAX_BEAM;
+constexpr int WCAP = 4096;
+struct WideLds {
+    float cv[WCAP];
+    int ci[WCAP];
+    float comb[2][64];        // [.][0..31] the largest group maxima so far (sorted), [.][32..63] the current row's
+    float row_mx[WMAXB], row_lse[WMAXB];
+    float win_v[WMAXB];
+    int win_i[WMAXB];
+    float sh_red[4], red_v[4];
+    int red_i[4], red_pos[4];
+    int cnt;
+};
+
+// block-wide best of (mv, mi) under better(); winner r -> S.win_v[r], S.win_i[r]; `clear`: mp is the winner's list position
+__device__ __forceinline__ void wide_argbest(WideLds& S, float mv, int mi, int mp, int r, bool clear) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(mv, o, 64); const int oi = __shfl_xor(mi, o, 64); const int op = __shfl_xor(mp, o, 64);
+        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; mp = op; }
+    }
+    if (lane == 0) { S.red_v[wave] = mv; S.red_i[wave] = mi; S.red_pos[wave] = mp; }
+    __syncthreads();
+    if (tid == 0) {
+        float fv = S.red_v[0]; int fi = S.red_i[0], fp = S.red_pos[0];
+        for (int w = 1; w < 4; ++w)
+            if (better(S.red_v[w], S.red_i[w], fv, fi)) { fv = S.red_v[w]; fi = S.red_i[w]; fp = S.red_pos[w]; }
+        S.win_v[r] = fv; S.win_i[r] = fi == 0x7FFFFFFF ? 0 : fi;      // (no candidate left — NaN rows: stay inside the tables)
+        if (clear && fp >= 0) S.cv[fp] = -INFINITY, S.ci[fp] = 0x7FFFFFFF;
+    }
+    __syncthreads();
+}
+
+// The b best of the image's nq x V candidates, in rank order, into S.win_v / S.win_i (flat index q * V + v); S.row_mx / S.row_lse
+// hold the rows' soft-max statistics when FUSED.  lp0: the image's first logit row; cum (nq values, NULL: 0); prev (token of row
+// q at prev[q * prev_stride], NULL: none) is no candidate; gs: the image's first row of block statistics (STATS).
+template <bool FUSED, int NPT, bool FASTEXP, bool STATS>
+__device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __restrict__ lp0, int64_t ldv, int nq, int b, int V, float scale,
+                                                 const float* __restrict__ cum, const int32_t* __restrict__ prev, int64_t prev_stride,
+                                                 const float* __restrict__ gs0, int nblk) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 32) S.comb[0][tid] = -INFINITY;
+    if (tid == 0) S.cnt = 0;
+    if (STATS) {
+        // one wave per row, the expressions of beam_step_kernel's STATS route
+        for (int q = wave; q < nq; q += 4) {
+            const float* gs = gs0 + (int64_t)q * nblk * 2;
+            float m[4], sb_[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int blk = lane + 64 * u;
+                const float2 v2 = blk < nblk ? *reinterpret_cast<const float2*>(gs + 2 * blk) : make_float2(-INFINITY, 0.f);
+                m[u] = v2.x; sb_[u] = v2.y;
+            }
+            const float mx = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
+            float sum = 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) sum += m[u] > -INFINITY ? sb_[u] * __expf(m[u] - mx) : 0.f;
+            const float lse = logf(wave_sum(sum));
+            if (lane == 0) { S.row_mx[q] = mx; S.row_lse[q] = lse; }
+        }
+    }
+    __syncthreads();
+    float zn[NPT > 0 ? NPT : 1];
+    if (NPT > 0) {
+#pragma unroll
+        for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; zn[u] = v < V ? lp0[v] : 0.f; }
+    }
+    for (int q = 0; q < nq; ++q) {
+        const float* lp = lp0 + (int64_t)q * ldv;
+        float z[NPT > 0 ? NPT : 1];
+        if (NPT > 0) {
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) z[u] = zn[u];
+            if (q + 1 < nq) {
+                const float* lpn = lp + ldv;
+#pragma unroll
+                for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; zn[u] = v < V ? lpn[v] : 0.f; }
+            }
+        }
+        const float cumq = cum ? cum[q] : 0.f;
+        const int pv = prev ? prev[(int64_t)q * prev_stride] : -1;
+        float mx = 0.f, lse = 0.f;
+        if (STATS) { mx = S.row_mx[q]; lse = S.row_lse[q]; }
+        else if (FUSED) {
+            float m = -INFINITY, sum = 0.f;
+            if (NPT > 0) {
+#pragma unroll
+                for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) m = fmaxf(m, z[u] * scale);
+                mx = blk_max(m, S.sh_red);
+#pragma unroll
+                for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) sum += exp_sel<FASTEXP>(__fmaf_rn(z[u], scale, -mx));
+            } else {
+                for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+                    float x[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; x[u] = v < V ? lp[v] * scale : -INFINITY; }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) m = fmaxf(m, x[u]);
+                }
+                mx = blk_max(m, S.sh_red);
+                for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+                    float x[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; x[u] = v < V ? lp[v] : 0.f; }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) if (v0 + 256 * u < V) sum += exp_sel<FASTEXP>(__fmaf_rn(x[u], scale, -mx));
+                }
+            }
+            sum = blk_sum(sum, S.sh_red);
+            lse = logf(sum);
+            if (tid == 0) { S.row_mx[q] = mx; S.row_lse[q] = lse; }
+        }
+        // candidate values and this thread's maximum
+        float tm = -INFINITY;
+        if (NPT > 0) {
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) {
+                const int v = tid + 256 * u;
+                const bool ok = v < V && v != pv;
+                z[u] = ok ? cumq + (__fmaf_rn(z[u], scale, -mx) - lse) : -INFINITY;
+                tm = fmaxf(tm, z[u]);
+            }
+        } else {
+            for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+                float x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; x[u] = v < V ? lp[v] : 0.f; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int v = v0 + 256 * u;
+                    if (v >= V || v == pv) continue;
+                    tm = fmaxf(tm, cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]));
+                }
+            }
+        }
+#pragma unroll
+        for (int o2 = 4; o2 > 0; o2 >>= 1) tm = fmaxf(tm, __shfl_xor(tm, o2, 64));
+        float* cb = S.comb[q & 1];
+        if ((lane & 7) == 0) cb[32 + wave * 8 + (lane >> 3)] = tm;
+        __syncthreads();
+        // rank of the 64 maxima (the carried 32 and this row's 32), every wave for itself: lane j ranks entry j
+        const float mine = cb[lane];
+        int rank = 0;
+        for (int j = 0; j < 64; ++j) { const float o = cb[j]; rank += (o > mine || (o == mine && j < lane)) ? 1 : 0; }
+        const float tau = __shfl(mine, __ffsll((unsigned long long)__ballot(rank == b - 1)) - 1, 64);
+        if (rank < 32) S.comb[(q + 1) & 1][rank] = mine;          // (all four waves store the same values)
+        if (NPT > 0) {
+#pragma unroll
+            for (int u = 0; u < NPT; ++u) {
+                const int v = tid + 256 * u;
+                if (v < V && v != pv && z[u] >= tau) {
+                    const int pos = atomicAdd(&S.cnt, 1);
+                    if (pos < WCAP) { S.cv[pos] = z[u]; S.ci[pos] = q * V + v; }
+                }
+            }
+        } else {
+            for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+                float x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; x[u] = v < V ? lp[v] : 0.f; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int v = v0 + 256 * u;
+                    if (v >= V || v == pv) continue;
+                    const float zz = cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]);
+                    if (zz >= tau) {
+                        const int pos = atomicAdd(&S.cnt, 1);
+                        if (pos < WCAP) { S.cv[pos] = zz; S.ci[pos] = q * V + v; }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int n = S.cnt;                 // block-uniform
+    if (n <= WCAP) {
+        for (int r = 0; r < b; ++r) {
+            float mv = -INFINITY; int mi = 0x7FFFFFFF, mp = -1;
+            for (int i = tid; i < n; i += 256) {
+                const float v = S.cv[i]; const int ix = S.ci[i];
+                if (better(v, ix, mv, mi)) { mv = v; mi = ix; mp = i; }
+            }
+            wide_argbest(S, mv, mi, mp, r, true);
+        }
+        return;
+    }
+    // overflow: winner r = the best candidate that ranks strictly behind winner r - 1
+    float lv = INFINITY; int li = -1;
+    for (int r = 0; r < b; ++r) {
+        float mv = -INFINITY; int mi = 0x7FFFFFFF;
+        for (int q = 0; q < nq; ++q) {
+            const float* lp = lp0 + (int64_t)q * ldv;
+            const float cumq = cum ? cum[q] : 0.f;
+            const int pv = prev ? prev[(int64_t)q * prev_stride] : -1;
+            const float mx = FUSED ? S.row_mx[q] : 0.f, lse = FUSED ? S.row_lse[q] : 0.f;
+            for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+                float x[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; x[u] = v < V ? lp[v] : 0.f; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int v = v0 + 256 * u;
+                    if (v >= V || v == pv) continue;
+                    const float zz = cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]);
+                    const int ix = q * V + v;
+                    if (better(lv, li, zz, ix) && better(zz, ix, mv, mi)) { mv = zz; mi = ix; }
+                }
+            }
+        }
+        wide_argbest(S, mv, mi, -1, r, false);
+        lv = S.win_v[r]; li = S.win_i[r];
+    }
+}
+
+template <bool FUSED, int NPT, bool FASTEXP = false, bool STATS = false>
+__global__ __launch_bounds__(256) void beam_step_wide_kernel(BeamState st, const float* __restrict__ logp, int t, float scale) {
+    __shared__ WideLds S;
+    __shared__ int end_slot[WMAXB];
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const int b = st.b, V = st.V, L = st.L;
+    const int nq = t == 0 ? 1 : b;
+    const int cur = t & 1, nxt = cur ^ 1;
+    const int64_t row0 = (int64_t)img * b;
+    const int64_t srow0 = t == 0 ? (int64_t)img : row0;
+    beam_select_wide<FUSED, NPT, FASTEXP, STATS>(S, logp + srow0 * st.ldv, st.ldv, nq, b, V, scale, t == 0 ? nullptr : st.cum + row0,
+                                                 (st.decoding_constraint && t > 0) ? st.seq[cur] + row0 * L + t - 1 : nullptr, L,
+                                                 STATS ? st.gstats + srow0 * st.nblk * 2 : nullptr, st.nblk);
+    // histories, ancestry table, next tokens, finished hypotheses: a copy of beam_step_kernel's tail (its instances keep their code
+    // bytes, so the tail is not shared): a change goes to both
+    for (int idx = tid; idx < b * t; idx += 256) {
+        const int q = idx / t, u = idx - q * t;
+        const int parent = S.win_i[q] / V;
+        const int64_t nrow = row0 + q, prow = row0 + parent;
+        st.seq[nxt][nrow * L + u] = st.seq[cur][prow * L + u];
+        st.tok_lp[nxt][nrow * L + u] = st.tok_lp[cur][prow * L + u];
+    }
+    for (int idx = tid; idx < b * (t + 1); idx += 256) {
+        const int q = idx / (t + 1), u = idx - q * (t + 1);
+        const int parent = S.win_i[q] / V;
+        const int64_t srow = t == 0 ? img : row0 + parent;
+        const int32_t v = st.kvidx[cur][srow * (t + 1) + u];
+        st.kvidx[nxt][(row0 + q) * (t + 2) + u] = v;
+        if (st.uniq) {
+            bool first = true;
+            for (int q2 = 0; q2 < q; ++q2) {
+                const int64_t s2 = t == 0 ? img : row0 + S.win_i[q2] / V;
+                if (st.kvidx[cur][s2 * (t + 1) + u] == v) first = false;
+            }
+            if (first) atomicAdd(st.uniq, 1ull);
+        }
+    }
+    if (tid < b) {
+        const int q = tid;
+        const int ix = S.win_i[q];
+        const int parent = ix / V, tok = ix - parent * V;
+        const int64_t nrow = row0 + q, prow = row0 + parent;
+        const int64_t srow = t == 0 ? img : prow;
+        st.seq[nxt][nrow * L + t] = tok;
+        const int pq = t == 0 ? 0 : parent;
+        st.tok_lp[nxt][nrow * L + t] = FUSED ? __fmaf_rn(logp[srow * st.ldv + tok], scale, -S.row_mx[pq]) - S.row_lse[pq] : logp[srow * st.ldv + tok];
+        st.it[nrow] = tok;
+        st.kvidx[nxt][nrow * (t + 2) + t + 1] = (int32_t)(nrow * st.tmax + t + 1);
+    }
+    const int cap = b * L;
+    if (tid == 0) {
+        int cnt = st.done_cnt[img];
+        for (int q = 0; q < b; ++q) {
+            const int64_t nrow = row0 + q;
+            const int ix = S.win_i[q];
+            const int tok = ix - (ix / V) * V;
+            float cum = S.win_v[q];
+            const bool end = tok == st.eos || t == L - 1;
+            end_slot[q] = -1;
+            if (end) {
+                if (cnt < cap) {
+                    const int64_t base = ((int64_t)img * cap + cnt);
+                    end_slot[q] = cnt;
+                    st.done_len[base] = t + 1;
+                    st.done_p[base] = length_pen(st.length_penalty, st.length_alpha, t + 1, (double)cum);
+                    ++cnt;
+                }
+                cum -= 1000.f;
+            }
+            st.cum[nrow] = cum;
+        }
+        st.done_cnt[img] = cnt;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < b * (t + 1); idx += 256) {
+        const int q = idx / (t + 1), u = idx - q * (t + 1);
+        if (end_slot[q] < 0) continue;
+        const int64_t base = (int64_t)img * cap + end_slot[q], nrow = row0 + q;
+        st.done_seq[base * L + u] = st.seq[nxt][nrow * L + u];
+        st.done_lp[base * L + u] = st.tok_lp[nxt][nrow * L + u];
+    }
+}
+
+// ortk_beam_select: the selection alone, winners to global memory
+template <bool FUSED, int NPT>
+__global__ __launch_bounds__(256) void beam_select_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ cum,
+                                                          const int32_t* __restrict__ prev, int q, int b, int V, float scale,
+                                                          float* __restrict__ val, int32_t* __restrict__ parent, int32_t* __restrict__ token) {
+    __shared__ WideLds S;
+    const int64_t row0 = (int64_t)blockIdx.x * q;
+    beam_select_wide<FUSED, NPT, false, false>(S, logits + row0 * ld, ld, q, b, V, scale, cum + row0, prev ? prev + row0 : nullptr, 1, nullptr, 0);
+    if ((int)threadIdx.x < b) {
+        const int ix = S.win_i[threadIdx.x];
+        const int64_t o = (int64_t)blockIdx.x * b + threadIdx.x;
+        val[o] = S.win_v[threadIdx.x]; parent[o] = ix / V; token[o] = ix - (ix / V) * V;
+    }
+}
+
 // stable top-b of each image's finished list by score (descending; earlier insertion wins ties)
 __global__ __launch_bounds__(64) void beam_finalize_kernel(BeamState st, int64_t* __restrict__ seq_out, float* __restrict__ lp_out,
                                                            float* __restrict__ score_out) {
-    __shared__ unsigned char taken[MAXB * 64];
+    __shared__ unsigned char taken[ORTK_MAX_BEAM * 64];
     const int img = blockIdx.x, lane = threadIdx.x;
     const int b = st.b, L = st.L, cap = b * L;
     const int cnt = st.done_cnt[img];
@@ -861,9 +1193,20 @@ int kvidx_init(int32_t* kvidx, int64_t rows, int32_t row_mult, int32_t tmax, hip
     ORTK_CHECK_LAUNCH();
     return 0;
 }
-int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, bool fused, float scale, bool fast_exp) {
-    if (st.b < 1 || st.b > MAXB) return ORTK_EINVAL;
+int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, bool fused, float scale, bool fast_exp, bool wide) {
+    if (st.b < 1 || st.b > ORTK_MAX_BEAM) return ORTK_EINVAL;
     if (st.B == 0) return 0;
+    const dim3 grid((unsigned)st.B);
+    if (wide || st.b > MAXB) {      // 9 .. 32 beams (and the test switch): the wide step, the same instance for the same mode
+        if (fused && fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V)
+            hipLaunchKernelGGL((beam_step_wide_kernel<true, 0, true, true>), grid, dim3(256), 0, s, st, logp, t, scale);
+        else if (fused && st.V <= 256 * 40 && fast_exp) hipLaunchKernelGGL((beam_step_wide_kernel<true, 40, true>), grid, dim3(256), 0, s, st, logp, t, scale);
+        else if (fused && st.V <= 256 * 40) hipLaunchKernelGGL((beam_step_wide_kernel<true, 40>), grid, dim3(256), 0, s, st, logp, t, scale);
+        else if (fused) hipLaunchKernelGGL((beam_step_wide_kernel<true, 0>), grid, dim3(256), 0, s, st, logp, t, scale);
+        else            hipLaunchKernelGGL((beam_step_wide_kernel<false, 0>), grid, dim3(256), 0, s, st, logp, t, 1.f);
+        ORTK_CHECK_LAUNCH();
+        return 0;
+    }
     if (fused && fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V)
         hipLaunchKernelGGL((beam_step_kernel<true, 0, true, true>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
     else if (fused && st.V <= 256 * 40 && fast_exp) hipLaunchKernelGGL((beam_step_kernel<true, 40, true>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
@@ -874,7 +1217,7 @@ int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, 
     return 0;
 }
 int beam_finalize(const BeamState& st, int64_t* seq_out, float* lp_out, float* score_out, hipStream_t s) {
-    if (st.b < 1 || st.b > MAXB || st.b * st.L > MAXB * 64) return ORTK_EINVAL;
+    if (st.b < 1 || st.b > ORTK_MAX_BEAM || st.b * st.L > ORTK_MAX_BEAM * 64) return ORTK_EINVAL;
     if (st.B == 0) return 0;
     hipLaunchKernelGGL(beam_finalize_kernel, dim3((unsigned)st.B), dim3(64), 0, s, st, seq_out, lp_out, score_out);
     ORTK_CHECK_LAUNCH();
@@ -933,6 +1276,20 @@ extern "C" int ortk_sample_truncate(const float* logits, int64_t rows, int32_t V
     hipStream_t s = ortk_s(stream);
     if (fast_exp) hipLaunchKernelGGL((ortk::sample_truncate_kernel<40, true>), dim3((unsigned)rows), dim3(256), 0, s, logits, (int)V, ld, temperature, (int)top_k, top_p, banned, kept, thr, thr_col, kept_mass);
     else hipLaunchKernelGGL((ortk::sample_truncate_kernel<40, false>), dim3((unsigned)rows), dim3(256), 0, s, logits, (int)V, ld, temperature, (int)top_k, top_p, banned, kept, thr, thr_col, kept_mass);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ortk_beam_select(const float* logits, int64_t ld, const float* cum, const int32_t* prev, int32_t B, int32_t q, int32_t b,
+                                int32_t V, int32_t fused, float scale, float* val, int32_t* parent, int32_t* token, ortk_stream stream) {
+    if (!logits || !cum || !val || !parent || !token || B < 0 || V < 1 || ld < V) return ORTK_EINVAL;
+    if (b < 1 || b > ORTK_MAX_BEAM || (q != 1 && q != b) || (int64_t)b > (int64_t)q * V || (int64_t)q * V > 0x7FFFFFFF) return ORTK_EINVAL;
+    if (B == 0) return 0;
+    hipStream_t s = ortk_s(stream);
+    const dim3 grid((unsigned)B);
+    if (!fused) hipLaunchKernelGGL((ortk::beam_select_kernel<false, 0>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, 1.f, val, parent, token);
+    else if (V <= 256 * 40) hipLaunchKernelGGL((ortk::beam_select_kernel<true, 40>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, scale, val, parent, token);
+    else hipLaunchKernelGGL((ortk::beam_select_kernel<true, 0>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, scale, val, parent, token);
     ORTK_CHECK_LAUNCH();
     return 0;
 }

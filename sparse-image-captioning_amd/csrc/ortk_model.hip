@@ -1875,6 +1875,7 @@ extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B,
     if (check_cfg(cfg) || !o || B < 1 || S < 1) return 0;
     const int K = decode_K(o);
     if (K < 1 || decode_trunc(cfg, o) < 0) return 0;
+    if (o->num_random_sample <= 0 && o->beam_size > 1 && (K > ORTK_MAX_BEAM || K > cfg->vocab)) return 0;      // (ortk_decode: ORTK_EINVAL)
     const DecodePlan pl = plan_decode(*cfg, B, K, o);
     if (!pl.ok) return 0;
     DecodeWS w; carve_decode(*cfg, B, S, K, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
@@ -2007,7 +2008,7 @@ static int decoder_stack_step(const Ctx& c, const Offsets& o, const StepBufs& w,
     a.rb = (flags & ORTK_DEC_STACK_RB20) ? 20 : 32;
     a.fa = P + o.dec_na; a.fb = P + o.dec_nb; a.att_masks = w.att_masks; a.kvidx = kvidx; a.ldx = o.ckv_slots * o.cw;
     a.rows = (int)rows; a.per_img = per_img; a.S = S; a.T = T; a.t = t; a.L = cfg->n_layers; a.NC = cfg->d_ff / 512; a.eps = 1e-6f;
-    a.debug = (flags >> 8) & 0xFF;       // phase-skipping measurement switches and the exchange tests (StackArgs.debug)
+    a.debug = (flags >> 8) & 0xBF;       // (bit 64 is the beam step's: ortk_decode) phase-skipping measurement switches and the exchange tests (StackArgs.debug)
     a.uniq_slot = uniq_slot;
     if (sp && sp->G) {
         a.tp = sp->G; a.tp_wpk = reinterpret_cast<const uint4*>(sp->wpk); a.tp_xbuf = sp->xbuf; a.tp_flag = sp->flag; a.tp_groups = sp->groups;
@@ -2033,7 +2034,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const int trunc = decode_trunc(cfg, op);
     if (trunc < 0) return ORTK_EINVAL;
     const bool beam = op->num_random_sample <= 0 && op->beam_size > 1;
-    if (beam && (K > 8 || K > cfg->vocab)) return ORTK_EINVAL;
+    if (beam && (K > ORTK_MAX_BEAM || K > cfg->vocab)) return ORTK_EINVAL;
     if (op->temperature <= 0.f) return ORTK_EINVAL;
     Offsets o; build_layout(*cfg, o, nullptr);
     // train-mode sampling (dropout on while the captions are drawn): multinomial rollouts only; with the greedy baseline as eval-mode
@@ -2174,7 +2175,8 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
         const float scale = (beam && t > 0) ? 1.f / op->temperature : 1.f;
         const bool fast_exp = cfg->precision == 1;                     // (the fp32 parity mode keeps libm's expf)
         if (beam && stack && ortk_prof_active()) { int ix = -1; bs.uniq = prof_slot(&ix); uniq_slot = ix + 1; }
-        if (beam) TRY(beam_step(bs, w.logits, t, s, true, scale, fast_exp));     // log-soft-max fused into the candidate scan
+        // log-soft-max fused into the candidate scan; 9 .. 32 beams (and debug bit 64, the parity tests' switch) run the wide step
+        if (beam) TRY(beam_step(bs, w.logits, t, s, true, scale, fast_exp, (op->exec_flags >> 8) & 64));
         else if (samp_epi) TRY(sample_combine(ss, w.gstats, w.gsamp, (int32_t)(w.ldv / 64), t, s, fast_exp));      // the generator's epilogue has the candidates
         else if (trunc) TRY(sample_step_trunc(ss, w.logits, t, s, fast_exp, op->top_k, op->top_p));
         else if (V <= 256 * 40) TRY(sample_step(ss, w.logits, t, s, true, fast_exp));     // log-soft-max fused (scale is 1 on this branch)

@@ -598,6 +598,9 @@ class RelationTransformerModel(CaptionModelBase):
         else:
             assert o.beam_size >= 1, f"Beam size must be >= 1, saw {o.beam_size}"    # transformer.py:514
             assert o.beam_size <= self.vocab_size                                    # transformer.py:482
+            if o.beam_size > L.MAX_BEAM:
+                raise ValueError(f"beam_size={o.beam_size}: the beam search serves at most ORTK_MAX_BEAM = {L.MAX_BEAM} beams "
+                                 "(include/ortk.h)")
             K = o.beam_size
         # executor choice (ortk_decode_opts.exec_flags): opt["executor"] = "auto" | "unfused" | "stack" | "sparse_stream" | "stack_fp8" ..;
         # "stack_fp8" (the stack kernel on FP8-quantised decoder weights, fp8_dequantized_decoder_state) is opt-in only: never "auto"
@@ -682,6 +685,8 @@ class RelationTransformerModel(CaptionModelBase):
     def decode_supported(self, B, S, opt, att_max_len=None):
         """Whether ``mode="sample"`` serves this option combination for B images of S regions (e.g. train-mode rollouts with the
         greedy baseline as eval-mode rows of the same launches: the column-split stack kernel only).  No device work."""
+        if int(opt.get("num_random_sample", 0)) <= 0 and int(opt.get("beam_size", 1)) > L.MAX_BEAM:
+            return False                                                     # (the decode itself raises ValueError: _decode_opts)
         o, _, ex = self._decode_opts(dict(opt, seed=opt.get("seed", 0)))      # (a probe draws no seed)
         if getattr(self, "_plans", None) is not None and self._plans[0] is not None and not ex.startswith("sparse_") and not o.train:
             o.sparse = self._plans[0].ref()

@@ -1,0 +1,411 @@
+"""Beam search wider than 8 beams (ortk.h: ORTK_MAX_BEAM = 32; the wide selection step beam_step_wide_kernel):
+  * the operator entry ortk_beam_select — the device function of the wide step — against numpy on the same fp32 values, exact,
+    ties and the overflow fallback included, and fused against ortk_log_softmax + unfused, bit for bit;
+  * the decode against the reference's own wide beams (golden G15), the wide step against the narrow one on the same logits at
+    widths <= 8 (bit for bit), the timed executors against the oracle, SCST with ten beam-search rollouts, and the limits."""
+import ctypes as Ct
+
+import numpy as np
+import pytest
+import torch
+
+import beam_ref as R
+import common as C
+import helpers as H
+from oracle import ort_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def P():
+    import sparse_image_captioning_amd as pkg
+    pkg._lib.require_gpu()
+    return pkg
+
+
+def _model(P, cfg, state, precision=0, **over):
+    from sparse_image_captioning_amd.utils.config import Config
+    m = P.get_model("relation_transformer")(Config(**dict(cfg, **over)), precision=precision)
+    missing, unexpected = m.load_state_dict(state, strict=False)
+    assert not unexpected and all(k.endswith(".pe") for k in missing), (missing, unexpected)
+    return m.cuda().eval()
+
+
+def _cuda(b):
+    return {k: v.cuda() for k, v in b.items()}
+
+
+def _oracle_cfg(cfg):
+    return O.OCfg(**{k: v for k, v in cfg.items() if not k.startswith("prune")})
+
+
+# ------------------------------------------------------------------------------------------------ operator
+N_IMG = 3
+WIDTHS = (9, 16, 17, 31, 32)               # 17: beyond the narrow kernel's 16 maxima per row
+VOCABS = (33, 255, 256, 257, 10001, 10240, 10241)      # the last two: either side of the register-resident rows
+LEVELS = np.array([-6.0, -4.5, -3.0, -2.0, -1.5, -1.0, -0.5, 0.0], np.float32)
+LEVEL_P = (0.9, 0.05, 0.03, 0.01, 0.005, 0.003, 0.0015, 0.0005)      # a thin top: ties at the cut, not only far above it
+CUM_LEVELS = np.array([-3.0, -2.5, -1.0, 0.0], np.float32)
+
+
+def _padded(x, ld):
+    """(rows, V) -> device (rows, ld) with NaN in the pad columns (never read)"""
+    out = np.full((x.shape[0], ld), np.nan, np.float32)
+    out[:, :x.shape[1]] = x
+    return torch.from_numpy(out).cuda()
+
+
+def _select(L, zd, ld, cum, prev, q, b, V, fused, scale):
+    val = torch.empty(N_IMG, b, device="cuda")
+    par = torch.empty(N_IMG, b, dtype=torch.int32, device="cuda")
+    tok = torch.empty(N_IMG, b, dtype=torch.int32, device="cuda")
+    rc = L.lib().ortk_beam_select(L.ptr(zd), ld, L.ptr(cum), L.ptr(prev) if prev is not None else None, N_IMG, q, b, V, fused, scale,
+                                  L.ptr(val), L.ptr(par), L.ptr(tok), L.stream_ptr())
+    assert rc == 0, rc
+    return val, par, tok
+
+
+def _expected(val, prev, q, b, V):
+    """numpy: the b best of every image's (q, V) values by (larger value, lower flat index), the previous tokens left out"""
+    ev, ep, et = [], [], []
+    for i in range(N_IMG):
+        v = val[i * q:(i + 1) * q]
+        ok = np.ones((q, V), bool)
+        if prev is not None:
+            ok[np.arange(q), prev[i * q:(i + 1) * q]] = False
+        flat = np.flatnonzero(ok.ravel())
+        vv = v.ravel()[flat]
+        win = flat[np.lexsort((flat, -vv))[:b]]
+        ev.append(v.ravel()[win]); ep.append(win // V); et.append(win % V)
+    return np.stack(ev), np.stack(ep).astype(np.int32), np.stack(et).astype(np.int32)
+
+
+@pytest.mark.parametrize("V", VOCABS)
+def test_operator_exact_order_with_ties(P, V):
+    """fused = 0 on values from a few exactly representable levels: ties inside a row, across rows and at the cut.  val, parent and
+    token equal numpy's lexsort by (-value, flat index), and a second run returns the same bytes."""
+    L = P._lib
+    ld = (V + 127) // 128 * 128
+    rs = np.random.RandomState(4000 + V)
+    case = 0
+    for b in WIDTHS:
+        for q in (1, b):
+            if b > q * V:
+                continue
+            rows = N_IMG * q
+            z = LEVELS[rs.choice(len(LEVELS), size=(rows, V), p=LEVEL_P)]
+            cum = CUM_LEVELS[rs.randint(0, len(CUM_LEVELS), size=rows)].copy()
+            cum[rs.uniform(size=rows) < 0.25] -= 1000.0               # finished beams
+            prev = None
+            if case % 2:
+                prev = rs.randint(0, V, size=rows).astype(np.int32)
+                prev[0::3] = z[0::3].argmax(1)                        # ... the row's best entry among them
+            case += 1
+            val = cum[:, None] + z                                    # one fp32 add, as the device does it
+            assert val.dtype == np.float32
+            want = _expected(val, prev, q, b, V)
+            zd, cd = _padded(z, ld), torch.from_numpy(cum).cuda()
+            pd = None if prev is None else torch.from_numpy(prev).cuda()
+            runs = [[o.cpu().numpy() for o in _select(L, zd, ld, cd, pd, q, b, V, 0, 1.0)] for _ in range(2)]
+            for a, c in zip(*runs):
+                assert a.tobytes() == c.tobytes(), ("two runs differ", V, b, q)
+            for name, got, w in zip(("val", "parent", "token"), runs[0], want):
+                np.testing.assert_array_equal(got, w, err_msg=f"{name} V={V} b={b} q={q} prev={prev is not None}")
+
+
+def test_operator_overflow_falls_back_to_the_exact_path(P):
+    """Every candidate of the image has the same value: the candidate list overflows and the winners are flat indices 0 .. 31."""
+    L = P._lib
+    b = q = 32
+    V = 10001
+    ld = (V + 127) // 128 * 128
+    z = np.full((N_IMG * q, V), -1.25, np.float32)
+    cum = np.full(N_IMG * q, -2.0, np.float32)
+    val, par, tok = _select(L, _padded(z, ld), ld, torch.from_numpy(cum).cuda(), None, q, b, V, 0, 1.0)
+    assert torch.equal(val.cpu(), torch.full((N_IMG, b), -3.25))
+    assert torch.equal(par.cpu(), torch.zeros(N_IMG, b, dtype=torch.int32))
+    assert torch.equal(tok.cpu(), torch.arange(b, dtype=torch.int32).expand(N_IMG, b))
+
+
+@pytest.mark.parametrize("V", [10001, 10241])
+def test_operator_overflow_fallback_of_the_fused_instances(P, V):
+    """The same flood through fused = 1 — register-resident rows (V <= 10 240) and streamed rows: the exact pass reuses the rows'
+    soft-max statistics, so the values are those of fused = 0 on ortk_log_softmax of the rows, and the winners flat indices 0 .. 31."""
+    L = P._lib
+    b = q = 32
+    ld = (V + 127) // 128 * 128
+    zd = _padded(np.full((N_IMG * q, V), 0.75, np.float32), ld)
+    cd = torch.full((N_IMG * q,), -2.0, device="cuda")
+    for scale in (1.0, 1.0 / 0.7):
+        lsm = zd.clone()
+        assert L.lib().ortk_log_softmax(L.ptr(lsm), N_IMG * q, V, ld, scale, L.stream_ptr()) == 0
+        fused = _select(L, zd, ld, cd, None, q, b, V, 1, scale)
+        plain = _select(L, lsm, ld, cd, None, q, b, V, 0, 1.0)
+        for name, f, u in zip(("val", "parent", "token"), fused, plain):
+            assert torch.equal(f, u), (name, V, scale)
+        assert torch.equal(fused[1].cpu(), torch.zeros(N_IMG, b, dtype=torch.int32))
+        assert torch.equal(fused[2].cpu(), torch.arange(b, dtype=torch.int32).expand(N_IMG, b))
+        assert abs(fused[0][0, 0].item() - (-2.0 - float(np.log(V)))) < 1e-4
+
+
+@pytest.mark.parametrize("V", VOCABS)
+def test_operator_fused_equals_log_softmax_then_unfused(P, V):
+    """fused = 1 (raw logits, exact expf) returns what fused = 0 returns on ortk_log_softmax of the same rows: the same bits."""
+    L = P._lib
+    ld = (V + 127) // 128 * 128
+    rs = np.random.RandomState(5000 + V)
+    for b in (9, 17, 32):
+        for q in (1, b):
+            if b > q * V:
+                continue
+            rows = N_IMG * q
+            z = (3.0 * rs.randn(rows, V)).astype(np.float32)
+            cd = torch.from_numpy((-4.0 * rs.uniform(size=rows)).astype(np.float32)).cuda()
+            pd = torch.from_numpy(rs.randint(0, V, size=rows).astype(np.int32)).cuda()
+            zd = _padded(z, ld)
+            for scale in (1.0, 1.0 / 0.7):
+                lsm = zd.clone()
+                assert L.lib().ortk_log_softmax(L.ptr(lsm), rows, V, ld, scale, L.stream_ptr()) == 0
+                fused = _select(L, zd, ld, cd, pd, q, b, V, 1, scale)
+                plain = _select(L, lsm, ld, cd, pd, q, b, V, 0, 1.0)
+                for name, f, u in zip(("val", "parent", "token"), fused, plain):
+                    assert torch.equal(f, u), (name, V, b, q, scale)
+
+
+# ------------------------------------------------------------------------------------------------ decode
+def close(a, b, tol):
+    a = a.detach().float().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    np.testing.assert_allclose(a, b, rtol=tol, atol=tol)
+
+
+@pytest.mark.parametrize("case", list(R.CASES))
+def test_wide_decode_vs_reference_golden(P, golden, case):
+    """Fp32 parity mode against the reference's own beams of width 10 / 12 / 16 / 32 (golden G15).  Images whose closest decision
+    of the whole search is at least GAP wide: tokens exact, log-probs and scores within 2e-4.  Every image: b distinct captions,
+    scores non-increasing, and without a length penalty the score is the sum of the caption's token log-probs."""
+    g = golden("g15_wide_beam")
+    b, opts, _, need = R.CASES[case]
+    cmp_ = g[f"{case}/min_gap"] >= R.GAP
+    assert int(cmp_.sum()) >= need
+    m = _model(P, C.TINY_CFG, H.g1_state())
+    bt = _cuda(H.torch_batch(R.case_inputs(C, int(g[f"{case}/seed"]))))
+    seq, lp = m(att_feats=bt["att_feats"], boxes=bt["boxes"], att_masks=bt["att_masks"], opt=dict(opts, beam_size=b), mode="sample")
+    p = torch.tensor([[d["p"] for d in img] for img in m.beams])
+    seq, lp = seq.cpu(), lp.cpu()
+    assert seq.shape == (R.N_IMG, b, C.TINY_CFG["max_seq_length"])
+    np.testing.assert_array_equal(seq.numpy()[cmp_], g[f"{case}/seq"][cmp_])
+    close(lp[torch.from_numpy(cmp_)], g[f"{case}/logprobs"][cmp_], 2e-4)
+    close(p[torch.from_numpy(cmp_)], g[f"{case}/p"][cmp_], 2e-4)
+    for n in range(R.N_IMG):
+        assert len({tuple(r) for r in seq[n].tolist()}) == b, (case, n)
+        assert bool((p[n, 1:] <= p[n, :-1]).all()), (case, n, p[n].tolist())
+    if not opts.get("length_penalty"):
+        close(lp.sum(-1), p.numpy(), 2e-4)
+
+
+def _decode(m, bt, opt):
+    seq, lp = m(att_feats=bt["att_feats"], boxes=bt["boxes"], att_masks=bt["att_masks"], opt=opt, mode="sample")
+    return seq, lp, m._last_decode[2]
+
+
+NARROW_CASES = ((2, {}), (5, {}), (8, {"decoding_constraint": 1, "length_penalty": "wu_0.7"}))
+
+
+def test_wide_step_equals_narrow_step_tiny_fp32(P):
+    """opt["stack_debug"] = 64 runs the wide step at any width: on the same logits it returns the narrow step's bytes."""
+    m, bt = _model(P, C.TINY_CFG, H.g1_state()), _cuda(H.g1_batch())
+    for b, opts in NARROW_CASES:
+        narrow = _decode(m, bt, dict(opts, beam_size=b))
+        wide = _decode(m, bt, dict(opts, beam_size=b, stack_debug=64))
+        for name, a, c in zip(("seq", "logprobs", "score"), narrow, wide):
+            assert torch.equal(a, c), (name, b)
+
+
+def test_wide_step_against_narrow_step_at_a_temperature(P):
+    """At a temperature other than 1 the two kernels are NOT required to agree in the last bit: the wide step forms
+    logit * scale - max with one rounding (as ortk_log_softmax does), the narrow kernel's register-resident rows round the product
+    first.  Expected: the same tokens wherever the search has no decision closer than GAP (tests/beam_ref.py), token log-probs
+    within 1e-5 — half an ulp of |logit * scale| < 32 (1.9e-6) in the term itself, as much in max and log-sum-exp, doubled — and
+    scores within 18 positions x 1e-5 = 2e-4 (rounded up)."""
+    m, cb = _model(P, C.TINY_CFG, H.g1_state()), H.g1_batch()
+    bt = _cuda(cb)
+    with torch.no_grad():
+        gap = R.beam_search(H.g1_state(), _oracle_cfg(C.TINY_CFG), cb["att_feats"], cb["boxes"], cb["att_masks"], 5, temperature=0.7)[3]
+    ok = gap >= R.GAP
+    assert bool(ok.any()), gap.tolist()
+    narrow = [x.cpu() for x in _decode(m, bt, {"beam_size": 5, "temperature": 0.7})]
+    wide = [x.cpu() for x in _decode(m, bt, {"beam_size": 5, "temperature": 0.7, "stack_debug": 64})]
+    print("[wide vs narrow, T 0.7] max |d logprob|", (narrow[1] - wide[1]).abs().max().item(), "max |d score|", (narrow[2] - wide[2]).abs().max().item(),
+          "bitwise", torch.equal(narrow[1], wide[1]))
+    assert torch.equal(narrow[0][ok], wide[0][ok])
+    assert (narrow[1] - wide[1])[ok].abs().max().item() < 1e-5
+    assert (narrow[2] - wide[2])[ok].abs().max().item() < 2e-4
+
+
+@pytest.fixture(scope="module")
+def margin_state():
+    """Full-size weights with real decision margins (generator x 3, EOS bias: tests/test_gpu_model.py::margin_state)."""
+    return H.torch_state(H.dense_param_shapes(C.FULL_CFG), C.G2_SEED, C.G1_GEN_SCALE, C.G1_EOS_BIAS)
+
+
+@pytest.fixture(scope="module")
+def full_bf16(P, margin_state):
+    return _model(P, C.FULL_CFG, margin_state, precision=1)
+
+
+@pytest.mark.parametrize("executor", ["unfused", "stack"])
+def test_wide_step_equals_narrow_step_full_size_bf16(P, full_bf16, executor):
+    """The same on the full-size model in mixed precision, 16 images: the fast-exp rows of the unfused executor and the generator's
+    block statistics of the stack kernel are the narrow step's, expression for expression."""
+    bt = _cuda(H.torch_batch(C.make_inputs(seed=1316, n_img=16, n_reg=36, feat=2048, vocab=10001, spi=1, ragged=True)))
+    for b, opts in NARROW_CASES:
+        narrow = _decode(full_bf16, bt, dict(opts, beam_size=b, executor=executor))
+        wide = _decode(full_bf16, bt, dict(opts, beam_size=b, executor=executor, stack_debug=64))
+        for name, a, c in zip(("seq", "logprobs", "score"), narrow, wide):
+            assert torch.equal(a, c), (name, b, executor)
+
+
+_ORACLE = {}
+
+
+def _oracle_beams(key, state, cfg, cb, beam):
+    """the oracle's beams, computed once per (weights, batch, width) and shared by the executors compared with them"""
+    if key not in _ORACLE:
+        with torch.no_grad():
+            _ORACLE[key] = O.beam_search(state, cfg, cb["att_feats"], cb["boxes"], cb["att_masks"], beam)
+    return _ORACLE[key]
+
+
+def _tf_logp_oracle(Pm, cfg, cb, rows):
+    tf_in = torch.cat([rows.new_full((rows.size(0), 1), C.BOS), rows], 1)
+    with torch.no_grad():
+        return O.forward_logp(Pm, cfg, cb["att_feats"], cb["boxes"], tf_in, cb["att_masks"], rollouts=True)
+
+
+_SPARSE = {}
+
+
+@pytest.mark.parametrize("executor,n_img,beam", [("unfused", 24, 10), ("stack", 24, 10), ("stack_split", 24, 10), ("sparse_stream", 24, 10),
+                                                 ("unfused", 12, 32), ("stack", 12, 32)])
+def test_bf16_wide_decode_executors_vs_oracle_with_real_margins(P, margin_state, executor, n_img, beam):
+    """The executors that serve beams, at widths 10 and 32 in mixed precision, against `O.beam_search` on full-size weights with real
+    margins — the rule of tests/test_gpu_model.py::test_bf16_decode_executors_vs_oracle_with_real_margins, unchanged: at least 90 %
+    of the best captions token-exact, their log-probs within 0.05, every differing image a near-tie under the oracle's
+    teacher-forced scores (0.05), and at least 90 % of the beam table equal where the best captions agree (that test counts
+    positions of the (images, b, L) token table).  Beyond it: EVERY beam row that differs from the oracle's row of the same rank is
+    shown to be a real, correctly scored hypothesis — the oracle's teacher-forced log-probs of the HIP path's tokens lie within 0.05
+    (the bar of the best captions' log-probs above) of the log-probs the decode returned for them, position by position — so a wrong
+    ancestry table, cache row or history at 10 or 32 rows per image cannot hide among them.  Whole rows equal to the oracle's row of
+    the same rank are printed: measured 0.95 - 0.98 at width 10 and 0.77 at width 32, where the lower ranks lie closer than bf16
+    activations resolve and swap places; at least 90 % of the rows must be rows of the oracle's list of that image, at any rank
+    (measured 0.988 - 0.996 at both widths: the difference to the rank-wise figure is order alone).  (Comparing the SCORES rank by rank is no
+    near-tie test: one hypothesis dropped at the cut of an earlier position shifts every later rank by one, and neighbouring ranks
+    lie up to 0.19 apart on these inputs.)"""
+    cfgd = dict(C.FULL_CFG)
+    state = margin_state
+    if executor.startswith("sparse_"):       # the reference's eval flow for pruned checkpoints: zero-filled dense weights (95 % zeros)
+        if "state" not in _SPARSE:
+            g = torch.Generator().manual_seed(17)
+            _SPARSE["state"] = {k: (v * (torch.rand(v.shape, generator=g) < 0.05).float() if v.dim() >= 2 else v) for k, v in margin_state.items()}
+        state = _SPARSE["state"]
+    m = _model(P, cfgd, state, precision=1)
+    cb = H.torch_batch(C.make_inputs(seed=1300 + n_img, n_img=n_img, n_reg=36, feat=2048, vocab=10001, spi=1, ragged=True))
+    b = _cuda(cb)
+    cfg = _oracle_cfg(cfgd)
+    oseq, olp, _ = _oracle_beams((executor.startswith("sparse_"), n_img, beam), state, cfg, cb, beam)
+    with torch.no_grad():
+        seq, lp = m(att_feats=b["att_feats"], boxes=b["boxes"], att_masks=b["att_masks"], opt={"beam_size": beam, "executor": executor},
+                    mode="sample")
+    seq, lp = seq.cpu(), lp.cpu()
+    best, obest = seq[:, 0], oseq[:, 0]
+    same = (best == obest).all(-1)
+    frac = same.float().mean().item()
+    assert frac >= 0.9, frac
+    v = (obest != 0) & same[:, None]
+    assert (lp[:, 0] - olp[:, 0])[v].abs().max().item() < 0.05
+    bad = (~same).nonzero().flatten().tolist()
+    if bad:
+        idx = torch.tensor(bad)
+        sub = {k: cb[k][idx] for k in ("att_feats", "boxes", "att_masks")}
+        full_o = _tf_logp_oracle(state, cfg, sub, obest[idx])
+        full_h = _tf_logp_oracle(state, cfg, sub, best[idx])
+        sc_o = (full_o.gather(2, obest[idx].unsqueeze(2)).squeeze(2) * (obest[idx] != 0)).sum(1)
+        sc_h = (full_h.gather(2, best[idx].unsqueeze(2)).squeeze(2) * (best[idx] != 0)).sum(1)
+        assert ((sc_o - sc_h).abs() < 0.05).all(), (bad, (sc_o - sc_h).tolist())
+    # the whole result where the best captions agree: the other beams of the image, in order
+    tok_same = (seq == oseq)[same].float().mean().item()
+    row_eq = (seq == oseq).all(-1)                                   # (images, b)
+    rows_same = row_eq[same].float().mean().item()
+    in_list = torch.tensor([[any(torch.equal(seq[n, r], oseq[n, k]) for k in range(beam)) for r in range(beam)] for n in range(n_img)])
+    # every differing row, all images: the oracle's teacher-forced log-probs of the HIP path's tokens against the decode's own
+    di, dr = (~row_eq).nonzero(as_tuple=True)
+    worst = 0.0
+    if di.numel():
+        sub = {k: cb[k][di] for k in ("att_feats", "boxes", "att_masks")}       # one (repeated) image per differing row
+        hrows = seq[di, dr]
+        tf_lp = _tf_logp_oracle(state, cfg, sub, hrows).gather(2, hrows.unsqueeze(2)).squeeze(2)
+        dev_ = ((tf_lp - lp[di, dr]) * (hrows != 0)).abs().max(1).values
+        worst = dev_.max().item()
+    print(f"[wide margins] {executor} n={n_img} beam={beam}: {frac:.3f} of the best captions token-exact, {len(bad)} near-ties, "
+          f"{tok_same:.3f} of the positions and {rows_same:.3f} of the whole beam rows equal, {in_list[same].float().mean().item():.3f} of the rows "
+          f"in the oracle's list; {di.numel()} differing rows, their log-probs against the oracle's teacher forcing: worst {worst:.4f}")
+    assert tok_same >= 0.9
+    assert in_list[same].float().mean().item() >= 0.9
+    assert worst < 0.05, (worst, [(int(i), int(r), float(d)) for i, r, d in zip(di, dr, dev_) if d >= 0.05][:8])
+
+
+def test_scst_ten_beam_search_rollouts_vs_oracle(P, golden):
+    """`scst_sample == "beam_search"` with the reference's default count (--scst_num_samples 10) on the inputs of golden case b10:
+    tokens equal the oracle's beam search, the loss its RewardCriterion on the oracle's teacher-forced log-probs (1e-4)."""
+    from sparse_image_captioning_amd.training import NativeTrainer
+    ns = 10
+    cb = H.torch_batch(R.case_inputs(C, int(golden("g15_wide_beam")["b10/seed"])))
+    m, b = _model(P, C.TINY_CFG, H.g1_state()), _cuda(cb)
+    cfg = _oracle_cfg(C.TINY_CFG)
+    N = cb["att_feats"].size(0)
+    rw = torch.linspace(-1.0, 1.0, N * ns)
+    tr = NativeTrainer(m, noamopt_factor=1.0, noamopt_warmup=10)
+    m.train()
+    loss, reward, seq, greedy = tr.scst_step(b, lambda s_, g_: rw, num_samples=ns, baseline="greedy", sample="beam_search")
+    Pm = H.g1_state()
+    with torch.no_grad():
+        oseq, _, _ = O.beam_search(Pm, cfg, cb["att_feats"], cb["boxes"], cb["att_masks"], ns)
+        ogreedy, _ = O.sample_greedy_or_multinomial(Pm, cfg, cb["att_feats"], cb["boxes"], cb["att_masks"])
+        assert torch.equal(seq.cpu(), oseq) and torch.equal(greedy.cpu(), ogreedy)
+        rows = oseq.view(-1, oseq.size(-1))
+        tf_in = torch.cat([rows.new_full((rows.size(0), 1), C.BOS), rows], 1)
+        logp = O.forward_logp(Pm, cfg, cb["att_feats"], cb["boxes"], tf_in, cb["att_masks"], rollouts=True)
+        ref_loss = O.reward_loss(logp.gather(2, rows.unsqueeze(2)).squeeze(2), rows, rw)
+    assert abs(loss.item() - ref_loss.item()) < 1e-4, (loss.item(), ref_loss.item())
+
+
+def test_width_limits(P):
+    """33 beams: ValueError from Python before any device work, decode_supported False, workspace query 0 and ORTK_EINVAL from the
+    library; 32 beams on the 101-token vocabulary are served."""
+    L = P._lib
+    assert L.MAX_BEAM == 32
+    m, bt = _model(P, C.TINY_CFG, H.g1_state()), _cuda(H.g1_batch())
+    kw = dict(att_feats=bt["att_feats"], boxes=bt["boxes"], att_masks=bt["att_masks"], mode="sample")
+    B, S = bt["att_feats"].shape[:2]
+    with pytest.raises(ValueError, match="ORTK_MAX_BEAM"):
+        m(**kw, opt={"beam_size": 33})
+    assert not m.decode_supported(B, S, {"beam_size": 33})
+    assert m.decode_supported(B, S, {"beam_size": 32})
+    o, K, _ = m._decode_opts({"beam_size": 32, "seed": 0})
+    lib = L.lib()
+    nb32 = lib.ortk_decode_workspace_bytes(Ct.byref(m._ccfg), B, S, Ct.byref(o))
+    assert nb32 > 0
+    o.beam_size = 33
+    assert lib.ortk_decode_workspace_bytes(Ct.byref(m._ccfg), B, S, Ct.byref(o)) == 0
+    feats, bxs, masks = m._prepare(bt["att_feats"], bt["boxes"], bt["att_masks"])
+    T = C.TINY_CFG["max_seq_length"]
+    ws = torch.empty(int(nb32) * 2, dtype=torch.uint8, device="cuda")
+    seq = torch.zeros(B, 33, T, dtype=torch.long, device="cuda")
+    lp = torch.zeros(B, 33, T, device="cuda")
+    sc = torch.zeros(B, 33, device="cuda")
+    rc = lib.ortk_decode(Ct.byref(m._ccfg), m._eff_params_ptr(False, 0), L.ptr(feats), L.ptr(bxs), L.ptr(masks), B, S, Ct.byref(o), L.ptr(ws),
+                         ws.numel(), L.ptr(seq), L.ptr(lp), L.ptr(sc), L.stream_ptr())
+    assert rc == -1, rc                                             # ORTK_EINVAL
+    seq32, lp32 = m(**kw, opt={"beam_size": 32})
+    assert seq32.shape == (B, 32, T) and all(len({tuple(r) for r in img.tolist()}) == 32 for img in seq32.cpu())
