@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 9      /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 10     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -572,6 +572,15 @@ typedef struct ortk_gemm_args {
     int32_t samp_L, samp_t, samp_greedy_stride, samp_sample, samp_fast, samp_no_store; float samp_inv_temperature;
 } ortk_gemm_args;
 int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream);
+/* Which kernels ortk_gemm(a) would launch: launches nothing, returns the code ortk_gemm would return for these arguments
+ * (ORTK_EINVAL included) and on success writes to buf (buf_bytes with the terminator) the launches in stream order.  Two codes of its
+ * own, for arguments ortk_gemm accepts: ORTK_EINVAL for a NULL buf or buf_bytes <= 0, ORTK_ENOSPC for a buf too short (left untouched).
+ * The launches are separated by ';': each kernel of ortk_gemm.hip as its family (the name without gemm_ / _kernel) and template instance,
+ * e.g. "bf16_dma256<1>;bf16_glds<0,1>" for a column count of 256 n + 128 with dropout; "colsum" ahead of the fp32 MFMA kernel where
+ * the column sums are a launch of their own; "layernorm_fwd" / "layernorm_bwd_drop_rows" behind the product of an ln_mode call that no
+ * fused kernel serves.  An empty string: nothing to do (M or N zero).  Built by the code that builds ortk_gemm's own plan, under
+ * the ortk_tuning values of the moment; pointers are tested for alignment only, never dereferenced (no device needed). */
+int ortk_gemm_plan(const ortk_gemm_args* a, char* buf, int32_t buf_bytes);
 /* The weight (and bias) gradients of up to ORTK_WGRAD_MAX projections over the SAME `rows` batch rows in one launch (mixed precision):
  *   dW_i (Nout_i x Kin_i, fp32, ld lddw) += dY_i^T X_i,   db_i (Nout_i, optional) += column sums of dY_i,
  * dY_i (rows x Nout_i) and X_i (rows x Kin_i) bf16 row-major, 16-byte aligned, leading dimensions and widths multiples of 8.

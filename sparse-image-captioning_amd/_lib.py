@@ -197,6 +197,7 @@ SIGNATURES = {
     "ortk_get_tuning": (None, [C.POINTER(Tuning)]),
     "ortk_set_tuning": (_I32, [C.POINTER(Tuning)]),
     "ortk_gemm": (_I32, [C.POINTER(GemmArgs), _P]),
+    "ortk_gemm_plan": (_I32, [C.POINTER(GemmArgs), C.c_char_p, _I32]),
     "ortk_wgrad_group": (_I32, [C.POINTER(WgradGroupArgs), _P]),
     "ortk_wgrad_group_workspace_bytes": (_SZ, [C.POINTER(WgradGroupArgs)]),
     "ortk_prof_enable": (_I32, [_I32]),
@@ -254,7 +255,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 9      # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 10     # include/ortk.h: ORTK_VERSION
 
 
 def lib():
@@ -289,6 +290,14 @@ def set_tuning(**kw):
         setattr(t, k, int(v))
     check(lib().ortk_set_tuning(C.byref(t)), "ortk_set_tuning")
     return old
+
+
+def gemm_plan(args):
+    """The launches ortk_gemm(args) would make, as a list of kernel-instance names (include/ortk.h: ortk_gemm_plan); raises
+    OrtkError where ortk_gemm would refuse the arguments.  Launches nothing and needs no device."""
+    buf = C.create_string_buffer(256)
+    check(lib().ortk_gemm_plan(C.byref(args), buf, len(buf)), "ortk_gemm_plan")
+    return [k for k in buf.value.decode().split(";") if k]
 
 
 def require_gpu():

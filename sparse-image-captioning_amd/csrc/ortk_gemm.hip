@@ -31,6 +31,7 @@
 // Workgroup ids are remapped so that the blocks resident on one XCD (ids b, b+8, ...) walk CONSECUTIVE tiles
 // (n fastest): they share the A panel in that XCD's L2 instead of fetching it 8 times.
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 #include "ortk_internal.h"
 
@@ -584,11 +585,25 @@ __device__ __forceinline__ void epilogue_from_lds(const Epi& e, float* sC, int m
     const int EN = FAST ? 0x7FFFFFFF : e.N, EM = FAST ? 0x7FFFFFFF : e.M;
     const bool first = e.first_split;
     if (e.accumulate) {
-        // 64 lanes = 64 consecutive columns of one row: 256 contiguous bytes per atomic instruction
+        // 64 lanes = 64 consecutive columns of one row: 256 contiguous bytes per atomic instruction.  C += v with v as epilogue_tile
+        // forms it (bias and residual by the first K split alone); a plain weight gradient passes the one workgroup-uniform test.
+        const bool plain = !((e.bias || e.resid) && first) && !e.relu && !e.rowscale && !(e.drop_p > 0.f) && !e.gate;
+        const float inv_keep = e.drop_p > 0.f ? 1.f / (1.f - e.drop_p) : 1.f;
         for (int it = 0; it < 64; ++it) {
             const int r = it * 2 + (wave >> 1), c = (wave & 1) * 64 + lane;
             const int m = mb + r, n = nb + c;
-            if (m < EM && n < EN) atomicAdd(reinterpret_cast<float*>(e.C) + (int64_t)m * e.ldc + n, sC[r * CP + c]);
+            if (m < EM && n < EN) {
+                float x = sC[r * CP + c];
+                if (!plain) {
+                    if (e.bias && first) x += e.bias[n];
+                    if (e.relu) x = fmaxf(x, 0.f);
+                    if (e.rowscale) x *= e.rowscale[m];
+                    if (e.drop_p > 0.f) x = ortk_keep(e.drop_seed, (((e.drop_rows ? (uint64_t)e.drop_rows[m] : (uint64_t)m)) * (uint64_t)e.drop_rs + (uint64_t)e.drop_r0) * (uint64_t)e.N + n, e.drop_p) ? x * inv_keep : 0.f;
+                    if (e.gate) x = ld_elem(e.gate, (int64_t)m * e.ldg + n, e.g_dt) > 0.f ? x * e.gate_scale : 0.f;
+                    if (e.resid && first) x += e.resid[(int64_t)m * e.ldr + n];
+                }
+                atomicAdd(reinterpret_cast<float*>(e.C) + (int64_t)m * e.ldc + n, x);
+            }
         }
         return;
     }
@@ -1567,15 +1582,28 @@ __global__ __launch_bounds__(256, NS > 4 ? 1 : NS == 4 ? 2 : 3) void gemm_bf16_d
 constexpr size_t DMA64_STAGE_BYTES = (size_t)2 * 64 * HBK * sizeof(__bf16);   // 16 KB
 
 typedef void (*gemm16_fn)(ortk_gemm_args, int, int, int);
-template <bool TA, bool TB, bool FAST> gemm16_fn pick16t(int adt, int bdt) {
-    if (adt == ORTK_F32 && bdt == ORTK_F32) return gemm_bf16_kernel<TA, TB, float, float, FAST>;
-    if (adt == ORTK_F32 && bdt == ORTK_BF16) return gemm_bf16_kernel<TA, TB, float, __bf16, FAST>;
-    if (adt == ORTK_BF16 && bdt == ORTK_F32) return gemm_bf16_kernel<TA, TB, __bf16, float, FAST>;
-    return gemm_bf16_kernel<TA, TB, __bf16, __bf16, FAST>;
+// A kernel instance and the name ortk_gemm_plan reports for it: the family without its gemm_ / _kernel affixes and the template
+// arguments (bool as 0 / 1, element types as f32 / bf16).  ORTK_INST forms both from ONE text, so the name cannot drift from the
+// instance: ORTK_INST(bf16_glds, 0,-1) is gemm_bf16_glds_kernel<0,-1> under the name "bf16_glds<0,-1>".  (The arguments are written
+// without blanks and in full, defaults included: the name is their text as it stands.)
+struct Inst { gemm16_fn fn; const char* name; };
+#define ORTK_INST_NAME(family, ...) #family "<" #__VA_ARGS__ ">"
+#define ORTK_INST(family, ...) Inst{gemm_##family##_kernel<__VA_ARGS__>, ORTK_INST_NAME(family, __VA_ARGS__)}
+#define ORTK_INST0(family) Inst{gemm_##family##_kernel, #family}      // a kernel that is no template
+using T_f32 = float;
+using T_bf16 = __bf16;
+#define ORTK_INST16(TA, TB, A, B, FAST) Inst{gemm_bf16_kernel<TA, TB, T_##A, T_##B, FAST>, "bf16<" #TA "," #TB "," #A "," #B "," #FAST ">"}
+#define ORTK_PICK16(TA, TB, FAST) \
+    return adt == ORTK_F32 ? (bdt == ORTK_F32 ? ORTK_INST16(TA, TB, f32, f32, FAST) : ORTK_INST16(TA, TB, f32, bf16, FAST)) \
+                           : (bdt == ORTK_F32 ? ORTK_INST16(TA, TB, bf16, f32, FAST) : ORTK_INST16(TA, TB, bf16, bf16, FAST));
+Inst pick16(int key, int adt, int bdt, bool fast) {
+    if (key == 4) { if (fast) { ORTK_PICK16(0, 0, 1) } ORTK_PICK16(0, 0, 0) }
+    if (key == 5) { if (fast) { ORTK_PICK16(0, 1, 1) } ORTK_PICK16(0, 1, 0) }
+    if (fast) { ORTK_PICK16(1, 1, 1) }
+    ORTK_PICK16(1, 1, 0)
 }
-template <bool TA, bool TB> gemm16_fn pick16(int adt, int bdt, bool fast) {
-    return fast ? pick16t<TA, TB, true>(adt, bdt) : pick16t<TA, TB, false>(adt, bdt);
-}
+#undef ORTK_PICK16
+#undef ORTK_INST16
 
 // ------------------------------------------------------------------------------------------------
 // fp32 products on the bf16 matrix cores (forward layout, fp32 operands and results: the fp32 parity mode).
@@ -2047,12 +2075,15 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void gemm_f32x3t_kernel(ortk_gemm
 // ------------------------------------------------------------------------------------------------ host side: validate -> plan -> launch
 // A plan is what the launch tail needs and nothing else.  Every kernel of this file but the short-panel one takes
 // (ortk_gemm_args, int, int, int); the tail hands all four to hipLaunchKernel, which reads as many as the kernel has parameters.
-struct Launch { const void* fn; unsigned grid, block; size_t lds; int a0, a1, a2; };
+struct Launch { const void* fn; const char* name; unsigned grid, block; size_t lds; int a0, a1, a2; };
 struct Plan {
     Launch l[2]; int n = 0;      // the second launch: the 128-column remainder of a 256 n + 128 column count (plan_dma)
     int key = 0; double bytes = 0.0;   // profiling: precision * 4 + transA * 2 + transB; algorithmic bytes
-    void add(gemm16_fn fn, int64_t grid, int block, size_t lds, int a0, int a1, int a2) {
-        l[n++] = Launch{reinterpret_cast<const void*>(fn), (unsigned)grid, (unsigned)block, lds, a0, a1, a2};
+    // what ortk_gemm launches around the plan's kernels: ortk_colsum ahead of the fp32 MFMA kernel, the separate LayerNorm
+    // (ln_mode of the call) behind the product of a call that no fused-LayerNorm kernel serves
+    bool colsum_first = false; int ln_after = 0;
+    void add(Inst k, int64_t grid, int block, size_t lds, int a0, int a1, int a2) {
+        l[n++] = Launch{reinterpret_cast<const void*>(k.fn), k.name, (unsigned)grid, (unsigned)block, lds, a0, a1, a2};
     }
 };
 // 128 x 128 output tiles and the K range of a workgroup (split-K only when accumulating)
@@ -2140,34 +2171,37 @@ void plan_ln(const ortk_gemm_args& p, Plan& pl) {
     const double ab = (double)p.M * p.K * 2 + (double)p.N * p.K * 2;
     if (p.ln_mode == 1) {
         pl.bytes = ab + (double)p.M * p.N * (4 + 4 + 2);
-        pl.add(gemm_bf16_row512_kernel, ortk_cdiv(p.M, RP_M), 512, RP_LDS_BYTES, 0, 0, 0);
+        pl.add(ORTK_INST0(bf16_row512), ortk_cdiv(p.M, RP_M), 512, RP_LDS_BYTES, 0, 0, 0);
         return;
     }
     // short row panels, about one workgroup per compute unit
     pl.bytes = ab + (double)p.M * p.N * (4 + 4 + 4 + 2);
     const int mt = (int)std::min<int64_t>(5, std::max<int64_t>(2, ortk_cdiv(p.M, 16 * 256)));      // (96-row panels spill)
-    const void* fn; size_t lds;
+    const void* fn; const char* name; size_t lds;
+#define ORTK_ROWLN(MT) fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<MT>); name = ORTK_INST_NAME(bf16_rowln_bwd, MT); lds = lb_lds_bytes<MT>(); break
     switch (mt) {
-        case 2:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<2>); lds = lb_lds_bytes<2>(); break;
-        case 3:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<3>); lds = lb_lds_bytes<3>(); break;
-        case 4:  fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<4>); lds = lb_lds_bytes<4>(); break;
-        default: fn = reinterpret_cast<const void*>(gemm_bf16_rowln_bwd_kernel<5>); lds = lb_lds_bytes<5>(); break;
+        case 2:  ORTK_ROWLN(2);
+        case 3:  ORTK_ROWLN(3);
+        case 4:  ORTK_ROWLN(4);
+        default: ORTK_ROWLN(5);
     }
-    pl.l[pl.n++] = Launch{fn, (unsigned)ortk_cdiv(p.M, 16 * mt), 512, lds, 0, 0, 0};
+#undef ORTK_ROWLN
+    pl.l[pl.n++] = Launch{fn, name, (unsigned)ortk_cdiv(p.M, 16 * mt), 512, lds, 0, 0, 0};
 }
 
 // ---- fp32, forward layout: three-way bf16 split on the bf16 matrix cores (gemm_f32x3_kernel / gemm_f32x3p_kernel)
+// (k: the instance of gemm_f32x3_kernel / gemm_f32x3p_kernel with these template arguments)
 template <int WM, int WN, int GM, int GN, int MINB>
-void add_f32x3(const ortk_gemm_args& p, Plan& pl) {
+void add_f32x3(const ortk_gemm_args& p, Plan& pl, Inst k) {
     const int tm = (int)ortk_cdiv(p.M, 32 * WM * GM), tn = (int)ortk_cdiv(p.N, 32 * WN * GN);
-    pl.add(gemm_f32x3_kernel<WM, WN, GM, GN, MINB>, (int64_t)tm * tn, 64 * GM * GN, 0, tm, tn, 0);
+    pl.add(k, (int64_t)tm * tn, 64 * GM * GN, 0, tm, tn, 0);
 }
 template <int WM, int WN, int GM, int GN, int MINB>
-void add_f32x3p(const ortk_gemm_args& p, Plan& pl) {
+void add_f32x3p(const ortk_gemm_args& p, Plan& pl, Inst k) {
     const int tm = (int)ortk_cdiv(p.M, 32 * WM * GM), tn = (int)ortk_cdiv(p.N, 32 * WN * GN);
-    pl.add(gemm_f32x3p_kernel<WM, WN, GM, GN, MINB>, (int64_t)tm * tn, 64 * GM * GN,
-           (size_t)2 * 3 * (32 * WM * GM + 32 * WN * GN) * 32 * sizeof(__bf16), tm, tn, 0);
+    pl.add(k, (int64_t)tm * tn, 64 * GM * GN, (size_t)2 * 3 * (32 * WM * GM + 32 * WN * GN) * 32 * sizeof(__bf16), tm, tn, 0);
 }
+#define ORTK_ADD_F32X3(family, ...) add_##family<__VA_ARGS__>(p, pl, ORTK_INST(family, __VA_ARGS__))
 bool plan_f32x3(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     if (!(layout_key(p) == 0 && ortk::tuning().f32_split && !p.accumulate && p.K > 0 && p.K % 32 == 0 && (p.lda & 3) == 0 && (p.ldb & 3) == 0 &&
           al(p.A, 16) && al(p.B, 16))) return false;
@@ -2179,22 +2213,23 @@ bool plan_f32x3(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     const int force = ortk::tuning().f32_split;     // 1 automatic | 2..7 a fixed kernel instance
     const int shape = force > 1 ? force : big * 4 >= ortk_cdiv(big, 256) * 256 * 3 ? 7 : t128 < 320 ? 5 : 3;
     switch (shape) {
-        case 2:  add_f32x3<1, 1, 2, 2, 2>(p, pl); break;    // single-buffered: 64 x 64 (24 KB)
-        case 3:  add_f32x3<2, 1, 2, 2, 3>(p, pl); break;    //                  128 x 64 (36 KB), three workgroups per unit
-        case 4:  add_f32x3<2, 2, 2, 2, 3>(p, pl); break;    //                  128 x 128 (48 KB), three
-        case 5:  add_f32x3p<1, 1, 2, 2, 3>(p, pl); break;   // pipelined:       64 x 64 (48 KB)
-        case 6:  add_f32x3p<2, 1, 2, 2, 2>(p, pl); break;   //                  128 x 64 (72 KB)
-        default: add_f32x3p<2, 2, 4, 2, 1>(p, pl); break;   //                  256 x 128, 8 waves (144 KB)
+        case 2:  ORTK_ADD_F32X3(f32x3, 1,1,2,2,2); break;    // single-buffered: 64 x 64 (24 KB)
+        case 3:  ORTK_ADD_F32X3(f32x3, 2,1,2,2,3); break;    //                  128 x 64 (36 KB), three workgroups per unit
+        case 4:  ORTK_ADD_F32X3(f32x3, 2,2,2,2,3); break;    //                  128 x 128 (48 KB), three
+        case 5:  ORTK_ADD_F32X3(f32x3p, 1,1,2,2,3); break;   // pipelined:       64 x 64 (48 KB)
+        case 6:  ORTK_ADD_F32X3(f32x3p, 2,1,2,2,2); break;   //                  128 x 64 (72 KB)
+        default: ORTK_ADD_F32X3(f32x3p, 2,2,4,2,1); break;   //                  256 x 128, 8 waves (144 KB)
     }
     return true;
 }
+#undef ORTK_ADD_F32X3
 // ---- fp32, transposed-operand layouts of the split product (gemm_f32x3t_kernel): dgrad without accumulation, wgrad with or without
 bool plan_f32x3t(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     const int key = layout_key(p);
     if (!(key != 0 && ortk::tuning().f32_split && p.K > 0 && (p.ldb & 3) == 0 && al(p.B, 16) && (p.N & 3) == 0 && p.N >= 4 && t.kchunk % 32 == 0 &&
           (key == 1 ? !p.accumulate && p.K % 32 == 0 && (p.lda & 3) == 0 && al(p.A, 16)
                     : (p.lda & 3) == 0 && al(p.A, 16) && (p.M & 3) == 0 && p.M >= 4))) return false;
-    const gemm16_fn fn = key == 1 ? gemm_f32x3t_kernel<false, false> : p.accumulate ? gemm_f32x3t_kernel<true, true> : gemm_f32x3t_kernel<true, false>;
+    const Inst fn = key == 1 ? ORTK_INST(f32x3t, 0,0) : p.accumulate ? ORTK_INST(f32x3t, 1,1) : ORTK_INST(f32x3t, 1,0);
     // (the accumulating instance stages its C tile over the six images)
     pl.add(fn, t.grid(), 256, p.accumulate ? BF16_LDS_BYTES_C : (size_t)6 * 128 * 32 * sizeof(__bf16), t.tilesM, t.tilesN, t.kchunk);
     return true;
@@ -2203,8 +2238,7 @@ bool plan_f32x3t(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
 // ortk_gemm launches ortk_colsum ahead of it.
 void plan_f32(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     const int key = layout_key(p);
-    pl.add(key == 0 ? gemm_f32_kernel<false, false> : key == 1 ? gemm_f32_kernel<false, true> : gemm_f32_kernel<true, true>,
-           t.grid(), 256, 0, t.tilesM, t.tilesN, t.kchunk);
+    pl.add(key == 0 ? ORTK_INST(f32, 0,0) : key == 1 ? ORTK_INST(f32, 0,1) : ORTK_INST(f32, 1,1), t.grid(), 256, 0, t.tilesM, t.tilesN, t.kchunk);
 }
 
 // ---- bf16, forward layout, short grids (decode-time projections): 64 x 64 tiles
@@ -2220,7 +2254,7 @@ bool plan_dma64(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
           p.drop_p == 0.f && !p.gate && !p.rowscale && (int64_t)t.tilesM * t.tilesN <= t64 && p.N <= 2048 && p.M <= 6144)) return false;
     const int tm = (int)ortk_cdiv(p.M, 64), tn = p.N / 64;
     const bool one = (int64_t)tm * tn <= 256 + 64;          // one workgroup per CU: the whole K = 512 panel in flight; else three per CU
-    pl.add(one ? gemm_bf16_dma64_kernel<8> : gemm_bf16_dma64_kernel<3>, (int64_t)tm * tn, 256, (one ? 8 : 3) * DMA64_STAGE_BYTES, tm, tn, t.kchunk);
+    pl.add(one ? ORTK_INST(bf16_dma64, 8) : ORTK_INST(bf16_dma64, 3), (int64_t)tm * tn, 256, (one ? 8 : 3) * DMA64_STAGE_BYTES, tm, tn, t.kchunk);
     return true;
 }
 
@@ -2229,21 +2263,21 @@ bool plan_dma64(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
 // everywhere 21.3 (the k-major layouts lose: dgrad 4.1 vs 3.3 ms, wgrad 4.1 vs 3.4 ms per step in isolation,
 // profiles/r03_wgrad_impl.txt); the k-major instances of these kernels are gone, the weight gradients have moved to
 // ortk_wgrad_group and the data gradients come here in the forward layout through the transposed weight copy.
-gemm16_fn lean_glds(const ortk_gemm_args& p) {
-    if (p.tile_stats) return p.tile_samp ? gemm_bf16_glds_kernel<false, 5> : gemm_bf16_glds_kernel<false, 4>;
+Inst lean_glds(const ortk_gemm_args& p) {
+    if (p.tile_stats) return p.tile_samp ? ORTK_INST(bf16_glds, 0,5) : ORTK_INST(bf16_glds, 0,4);
     switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
-        case 0:  return gemm_bf16_glds_kernel<false, 0>;
-        case 1:  return gemm_bf16_glds_kernel<false, 1>;
-        case 2:  return gemm_bf16_glds_kernel<false, 2>;
-        default: return gemm_bf16_glds_kernel<false, 3>;
+        case 0:  return ORTK_INST(bf16_glds, 0,0);
+        case 1:  return ORTK_INST(bf16_glds, 0,1);
+        case 2:  return ORTK_INST(bf16_glds, 0,2);
+        default: return ORTK_INST(bf16_glds, 0,3);
     }
 }
-gemm16_fn lean_dma256(const ortk_gemm_args& p) {
+Inst lean_dma256(const ortk_gemm_args& p) {
     switch ((p.drop_p > 0.f ? 1 : 0) | (p.gate ? 2 : 0)) {
-        case 0:  return gemm_bf16_dma256_kernel<0>;
-        case 1:  return gemm_bf16_dma256_kernel<1>;
-        case 2:  return gemm_bf16_dma256_kernel<2>;
-        default: return gemm_bf16_dma256_kernel<3>;
+        case 0:  return ORTK_INST(bf16_dma256, 0);
+        case 1:  return ORTK_INST(bf16_dma256, 1);
+        case 2:  return ORTK_INST(bf16_dma256, 2);
+        default: return ORTK_INST(bf16_dma256, 3);
     }
 }
 bool plan_dma(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
@@ -2271,17 +2305,17 @@ bool plan_dma(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     // (ortk_tuning.gemm_epilogue & 2: never split.)
     const bool nsplit = lean && !want_stats && !(ortk::tuning().gemm_epilogue & 2) && p.N % 256 == 128 && p.N > 256 && p.K % HBK == 0;
     const bool big = !p.accumulate && !want_stats && (p.M % 256 == 0 || fast4) && (p.N % 256 == 0 || nsplit) && fills;
-    const gemm16_fn small = lean ? lean_glds(p) : gemm_bf16_glds_kernel<false>;
+    const Inst small = lean ? lean_glds(p) : ORTK_INST(bf16_glds, 0,-1);
     if (!big) {
         pl.add(small, t.grid(), 256, GLDS_LDS_BYTES, t.tilesM, t.tilesN, t.kchunk);
     } else if (p.K % HBK == 0) {
         // 64-column stages (full cache lines)
-        pl.add(lean ? lean_dma256(p) : gemm_bf16_dma256_kernel<>, big_blocks, 512, DMA256_LDS_BYTES, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
+        pl.add(lean ? lean_dma256(p) : ORTK_INST(bf16_dma256, -1), big_blocks, 512, DMA256_LDS_BYTES, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
         if (nsplit)      // the last 128 columns: one column tile of the 128 x 128 kernel, starting at tile (N / 128 - 1)
             pl.add(small, t.tilesM, 256, GLDS_LDS_BYTES, t.tilesM, 1 | ((t.tilesN - 1) << 16), t.kchunk);
     } else {
         // K = 32 (mod 64): the 32-column ring on the big tile
-        pl.add(gemm_bf16_glds_kernel<true>, big_blocks, 512, GLDS_LDS_BYTES_BIG, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
+        pl.add(ORTK_INST(bf16_glds, 1,-1), big_blocks, 512, GLDS_LDS_BYTES_BIG, (int)ortk_cdiv(p.M, 256), p.N / 256, t.kchunk);
     }
     return true;
 }
@@ -2290,10 +2324,7 @@ bool plan_dma(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
 void plan_bf16(const ortk_gemm_args& p, const Tiling& t, Plan& pl) {
     const int key = layout_key(p);
     const bool fast = bf16_fast_nk(p, t) && p.M % BM == 0;
-    pl.add(key == 4 ? pick16<false, false>(p.a_dtype, p.b_dtype, fast)
-         : key == 5 ? pick16<false, true>(p.a_dtype, p.b_dtype, fast)
-                    : pick16<true, true>(p.a_dtype, p.b_dtype, fast),
-           t.grid(), 256, BF16_LDS_BYTES, t.tilesM, t.tilesN, t.kchunk);
+    pl.add(pick16(key, p.a_dtype, p.b_dtype, fast), t.grid(), 256, BF16_LDS_BYTES, t.tilesM, t.tilesN, t.kchunk);
 }
 
 // The one launch tail.  (> 64 KB of dynamic LDS needs the attribute once per kernel instance and device; it is set before the
@@ -2313,24 +2344,20 @@ int gemm_launch(ortk_gemm_args& p, Plan& pl, hipStream_t s) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
+// The one plan builder, for ortk_gemm and ortk_gemm_plan alike.  p: the arguments the plan's kernels are launched with (those of the
+// call; of a call with a separate LayerNorm, the plain product's).  A return of 0 with an empty plan: nothing to do.
+int gemm_build(const ortk_gemm_args* a, ortk_gemm_args& p, Plan& pl) {
     if (!a || !a->A || !a->B || !a->C || a->M < 0 || a->N < 0 || a->K < 0) return ORTK_EINVAL;
     if (a->M == 0 || a->N == 0) return 0;
-    ortk_gemm_args p = *a;
+    p = *a;
     if (int e = gemm_validate(p)) return e;
     if (p.ln_mode && !ln_fused(p)) {
         // any other shape / precision: the same result from the separate kernels
-        ortk_gemm_args q = p; q.ln_mode = 0;
-        if (p.ln_mode == 2) q.drop_p = 0.f;
-        if (int e = ortk_gemm(&q, stream)) return e;
-        float* Cf = reinterpret_cast<float*>(p.C);
-        if (p.ln_mode == 1) return ortk_layernorm_fwd(Cf, p.ln_a, p.ln_b, p.ln_y, p.ln_y_dtype, p.ln_stats, p.M, p.N, p.ln_eps, stream);
-        return ortk_layernorm_bwd_drop_rows(Cf, p.ln_x, p.ln_a, p.ln_stats, p.ln_dres, Cf, p.ln_da, p.ln_db, p.M, p.N, p.ln_eps,
-                                            p.ln_y, p.ln_y_dtype, p.drop_p, p.drop_seed, p.drop_rows, stream);
+        pl.ln_after = p.ln_mode;
+        if (p.ln_mode == 2) p.drop_p = 0.f;
+        p.ln_mode = 0;
+        if (int e = gemm_validate(p)) return e;
     }
-    Plan pl;
     if (p.ln_mode) {
         plan_ln(p, pl);
     } else {
@@ -2341,9 +2368,48 @@ extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
         if (p.precision) {
             if (!plan_dma64(p, t, pl) && !plan_dma(p, t, pl)) plan_bf16(p, t, pl);
         } else if (!plan_f32x3(p, t, pl) && !plan_f32x3t(p, t, pl)) {
-            if (p.colsum) { if (int e = ortk_colsum(p.A, ORTK_F32, p.lda, p.colsum, p.K, p.M, stream)) return e; }
+            pl.colsum_first = p.colsum != nullptr;
             plan_f32(p, t, pl);
         }
     }
-    return gemm_launch(p, pl, ortk_s(stream));
+    return 0;
+}
+#undef ORTK_INST
+#undef ORTK_INST0
+#undef ORTK_INST_NAME
+
+}  // namespace
+
+extern "C" int ortk_gemm(const ortk_gemm_args* a, ortk_stream stream) {
+    ortk_gemm_args p; Plan pl;
+    if (int e = gemm_build(a, p, pl)) return e;
+    if (pl.n == 0) return 0;
+    if (pl.colsum_first) { if (int e = ortk_colsum(p.A, ORTK_F32, p.lda, p.colsum, p.K, p.M, stream)) return e; }
+    if (int e = gemm_launch(p, pl, ortk_s(stream))) return e;
+    if (!pl.ln_after) return 0;
+    float* Cf = reinterpret_cast<float*>(a->C);
+    if (pl.ln_after == 1) return ortk_layernorm_fwd(Cf, a->ln_a, a->ln_b, a->ln_y, a->ln_y_dtype, a->ln_stats, a->M, a->N, a->ln_eps, stream);
+    return ortk_layernorm_bwd_drop_rows(Cf, a->ln_x, a->ln_a, a->ln_stats, a->ln_dres, Cf, a->ln_da, a->ln_db, a->M, a->N, a->ln_eps,
+                                        a->ln_y, a->ln_y_dtype, a->drop_p, a->drop_seed, a->drop_rows, stream);
+}
+
+extern "C" int ortk_gemm_plan(const ortk_gemm_args* a, char* buf, int32_t buf_bytes) {
+    ortk_gemm_args p; Plan pl;
+    if (int e = gemm_build(a, p, pl)) return e;
+    if (!buf || buf_bytes <= 0) return ORTK_EINVAL;
+    const char* part[4]; int n = 0;
+    if (pl.n && pl.colsum_first) part[n++] = "colsum";
+    for (int i = 0; i < pl.n; ++i) part[n++] = pl.l[i].name;
+    if (pl.n && pl.ln_after) part[n++] = pl.ln_after == 1 ? "layernorm_fwd" : "layernorm_bwd_drop_rows";
+    size_t need = 1;
+    for (int i = 0; i < n; ++i) need += strlen(part[i]) + (i ? 1 : 0);
+    if (need > (size_t)buf_bytes) return ORTK_ENOSPC;
+    char* w = buf;
+    for (int i = 0; i < n; ++i) {
+        if (i) *w++ = ';';
+        const size_t len = strlen(part[i]);
+        memcpy(w, part[i], len); w += len;
+    }
+    *w = 0;
+    return 0;
 }
