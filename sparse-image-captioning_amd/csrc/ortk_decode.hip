@@ -11,6 +11,7 @@
 //     ancestors (kvidx), re-threaded by parent pointer each step; cross-attention K/V exist once per image;
 //   * finished hypotheses go to a per-image list; the final stable top-b by (length-penalised) score runs on
 //     device too.  No host synchronisation anywhere in the 18 steps.
+#include <type_traits>
 #include "ortk_internal.h"
 
 namespace ortk {
@@ -49,8 +50,6 @@ __global__ void kvidx_init_kernel(int32_t* p, int64_t rows, int row_mult, int tm
 // ------------------------------------------------------------------------------------------------ beam step
 constexpr int MAXB = 8;   // beams kept per thread (>= beam size)
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
 __device__ __forceinline__ double length_pen(int kind, double alpha, int len, double p) {
     if (kind == 1) return p / (pow(5.0 + (double)len, alpha) / pow(6.0, alpha));   // utils/model_utils.py:134-140
     if (kind == 2) return p / (double)len;                                         // utils/model_utils.py:143-146
@@ -80,18 +79,151 @@ __device__ __forceinline__ float blk_sum(float v, float* sh) {
     return r;
 }
 
-// FUSED: `logp` holds raw generator logits; the row's log-soft-max (of logits * scale) is taken here — max, sum and
+// Arg-best under ortk_better (larger value, lower index on a tie) with a payload that travels with the winner: a list position
+// (beam steps), the token's log-prob (fused and truncated sampling), or nothing (NoPayload).
+struct NoPayload {};
+template <typename T> __device__ __forceinline__ T shfl_xor_payload(T p, int o) {
+    if constexpr (std::is_empty_v<T>) return p; else return __shfl_xor(p, o, 64);
+}
+// the wave's best in every lane
+template <typename T>
+__device__ __forceinline__ void wave_argbest(float& v, int& i, T& p) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o, 64); const int oi = __shfl_xor(i, o, 64); const T op = shfl_xor_payload(p, o);
+        if (ortk_better(ov, oi, v, i)) { v = ov; i = oi; p = op; }
+    }
+}
+__device__ __forceinline__ void wave_argbest(float& v, int& i) { NoPayload none; wave_argbest(v, i, none); }
+// the workgroup's best (four waves) in thread 0; red_*: 4 LDS entries each, free again after the caller's next barrier
+template <typename T>
+__device__ __forceinline__ void blk_argbest(float& v, int& i, T& p, float* red_v, int* red_i, T* red_p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_argbest(v, i, p);
+    if (lane == 0) { red_v[wave] = v; red_i[wave] = i; if constexpr (!std::is_empty_v<T>) red_p[wave] = p; }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int w = 1; w < 4; ++w)
+            if (ortk_better(red_v[w], red_i[w], v, i)) { v = red_v[w]; i = red_i[w]; if constexpr (!std::is_empty_v<T>) p = red_p[w]; }
+}
+__device__ __forceinline__ void blk_argbest(float& v, int& i, float* red_v, int* red_i) {
+    NoPayload none;
+    blk_argbest(v, i, none, red_v, red_i, static_cast<NoPayload*>(nullptr));
+}
+
+// STATS: maximum and log-sum-exp of one logit row from its block statistics gs (nblk x {max, sum exp(. - max)}), taken by one wave;
+// m[u] is left holding the maximum of block lane + 64 u (-inf past nblk)
+__device__ __forceinline__ void stats_row_lse(const float* __restrict__ gs, int nblk, float (&m)[4], float& mx, float& lse) {
+    const int lane = threadIdx.x & 63;
+    float sb_[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int blk = lane + 64 * u;
+        const float2 v2 = blk < nblk ? *reinterpret_cast<const float2*>(gs + 2 * blk) : make_float2(-INFINITY, 0.f);
+        m[u] = v2.x; sb_[u] = v2.y;
+    }
+    mx = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
+    float sum = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) sum += m[u] > -INFINITY ? sb_[u] * __expf(m[u] - mx) : 0.f;
+    lse = logf(wave_sum(sum));
+}
+
+// The tail of a beam step, shared by beam_step_kernel and beam_step_wide_kernel: the image's b winners (win_v, win_i = parent * V +
+// token, in rank order) become its next beams.  row_mx / row_lse: the soft-max statistics of the image's rows; end_slot: b LDS entries.
+// Histories, ancestry table, next tokens.  Every copy is spread over the whole workgroup: one thread per beam walking
+// its t history entries and t+1 ancestry entries was a chain of ~50 dependent global round trips (the tail of the step
+// grew with t and dominated it: 118 us per step at 1 024 images x 5 beams).
+__device__ __forceinline__ void beam_commit(const BeamState& st, const float* __restrict__ logp, int t, float scale, const float* win_v,
+                                            const int* win_i, const float* row_mx, const float* row_lse, int* end_slot) {
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const int b = st.b, V = st.V, L = st.L;
+    const int cur = t & 1, nxt = cur ^ 1;
+    const int64_t row0 = (int64_t)img * b;
+    for (int idx = tid; idx < b * t; idx += 256) {
+        const int q = idx / t, u = idx - q * t;
+        const int parent = win_i[q] / V;
+        const int64_t nrow = row0 + q, prow = row0 + parent;
+        st.seq[nxt][nrow * L + u] = st.seq[cur][prow * L + u];
+        st.tok_lp[nxt][nrow * L + u] = st.tok_lp[cur][prow * L + u];
+    }
+    for (int idx = tid; idx < b * (t + 1); idx += 256) {
+        const int q = idx / (t + 1), u = idx - q * (t + 1);
+        const int parent = win_i[q] / V;
+        const int64_t srow = t == 0 ? img : row0 + parent;
+        const int32_t v = st.kvidx[cur][srow * (t + 1) + u];
+        st.kvidx[nxt][(row0 + q) * (t + 2) + u] = v;                                   // ancestors' cache rows
+        if (st.uniq) {      // measurement only: is this the first of the image's new beams that references cache row v?
+            bool first = true;
+            for (int q2 = 0; q2 < q; ++q2) {
+                const int64_t s2 = t == 0 ? img : row0 + win_i[q2] / V;
+                if (st.kvidx[cur][s2 * (t + 1) + u] == v) first = false;
+            }
+            if (first) atomicAdd(st.uniq, 1ull);
+        }
+    }
+    if (tid < b) {
+        const int q = tid;
+        const int ix = win_i[q];
+        const int parent = ix / V, tok = ix - parent * V;
+        const int64_t nrow = row0 + q, prow = row0 + parent;
+        const int64_t srow = t == 0 ? img : prow;
+        st.seq[nxt][nrow * L + t] = tok;
+        const int pq = t == 0 ? 0 : parent;
+        // logit * scale - max with ONE rounding, spelled out: the product has this one use, and the compiler contracted it to an FMA in
+        // every instance of both kernels when the narrow one still wrote it as a product and a difference
+        st.tok_lp[nxt][nrow * L + t] = __fmaf_rn(logp[srow * st.ldv + tok], scale, -row_mx[pq]) - row_lse[pq];
+        st.it[nrow] = tok;
+        st.kvidx[nxt][nrow * (t + 2) + t + 1] = (int32_t)(nrow * st.tmax + t + 1);      // this beam's own slot at time t+1
+    }
+    // finished hypotheses: slots are handed out sequentially per image (insertion order matters for the final stable
+    // sort), the copies run in parallel afterwards
+    const int cap = b * L;
+    if (tid == 0) {
+        int cnt = st.done_cnt[img];
+        for (int q = 0; q < b; ++q) {
+            const int64_t nrow = row0 + q;
+            const int ix = win_i[q];
+            const int tok = ix - (ix / V) * V;
+            float cum = win_v[q];
+            const bool end = tok == st.eos || t == L - 1;
+            end_slot[q] = -1;
+            if (end) {
+                if (cnt < cap) {
+                    const int64_t base = ((int64_t)img * cap + cnt);
+                    end_slot[q] = cnt;
+                    st.done_len[base] = t + 1;
+                    st.done_p[base] = length_pen(st.length_penalty, st.length_alpha, t + 1, (double)cum);
+                    ++cnt;
+                }
+                cum -= 1000.f;
+            }
+            st.cum[nrow] = cum;
+        }
+        st.done_cnt[img] = cnt;
+    }
+    __syncthreads();          // end_slot, and the histories written above, are visible to the whole workgroup
+    for (int idx = tid; idx < b * (t + 1); idx += 256) {
+        const int q = idx / (t + 1), u = idx - q * (t + 1);
+        if (end_slot[q] < 0) continue;
+        const int64_t base = (int64_t)img * cap + end_slot[q], nrow = row0 + q;
+        st.done_seq[base * L + u] = st.seq[nxt][nrow * L + u];
+        st.done_lp[base * L + u] = st.tok_lp[nxt][nrow * L + u];
+    }
+}
+
+// `logp` holds raw generator logits; the row's log-soft-max (of logits * scale) is taken here — max, sum and
 // candidate scan are three strided passes over the row (the 2nd and 3rd hit L2), with 8 independent loads in flight
 // per thread.  Saves the separate log-soft-max launch (read + write of rows x V fp32 per step).
 // FASTEXP (mixed precision only): v_exp_f32 (__expf, ~1 ulp) for the soft-max sum instead of libm's expf — the step is bound by
 // the ~20 vector instructions per element of the exact function, not by its one read of the logits (111 -> 60 us per step of
 // the 1 024-image beam-5 decode); the fp32 parity mode keeps the exact function (token-exact goldens).
 template <bool FAST> __device__ __forceinline__ float exp_sel(float x) { return FAST ? __expf(x) : expf(x); }
-// STATS (with FUSED, scale = 1): the generator GEMM has left {max, sum exp(. - max)} of every block of 64 logits (st.gstats).
+// STATS (scale = 1): the generator GEMM has left {max, sum exp(. - max)} of every block of 64 logits (st.gstats).
 // The row's log-sum-exp comes from those 2 x 158 floats; the (b + 1)-th largest block maximum is a lower bound of the row's
 // b-th best admissible element (block maxima are elements of distinct blocks, at most one of them is the token the decoding
 // constraint excludes), so only the b + 1 blocks at or above it are read: 1.6 KB of a 40-KB logit row.
-template <bool FUSED, int NPT, bool FASTEXP = false, bool STATS = false>
+template <int NPT, bool FASTEXP = false, bool STATS = false>
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const float* __restrict__ logp, int t, float scale) {
     __shared__ float sv[256 * MAXB];
     __shared__ float sh_red[4];
@@ -100,11 +232,11 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
     __shared__ float red_v[4];
     __shared__ int red_i[4], red_pos[4];
     __shared__ float win_v[MAXB];
-    __shared__ int win_i[MAXB];
+    __shared__ int win_i[MAXB], end_slot[MAXB];
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = st.b, V = st.V, L = st.L;
     const int nq = t == 0 ? 1 : b;
-    const int cur = t & 1, nxt = cur ^ 1;
+    const int cur = t & 1;
 
     float bv[MAXB];
     int bi[MAXB];
@@ -123,21 +255,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
         const int want = min(b + 1, nblk);            // blocks to read per row
         for (int q = wave; q < nq; q += 4) {
             const int64_t srow = t == 0 ? (int64_t)img : (int64_t)img * b + q;
-            const float* gs = st.gstats + srow * nblk * 2;
-            float m[4], sb_[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int blk = lane + 64 * u;
-                const float2 v2 = blk < nblk ? *reinterpret_cast<const float2*>(gs + 2 * blk) : make_float2(-INFINITY, 0.f);
-                m[u] = v2.x; sb_[u] = v2.y;
-            }
+            float m[4], mx, lse;
+            stats_row_lse(st.gstats + srow * nblk * 2, nblk, m, mx, lse);
             const float cum = t == 0 ? 0.f : st.cum[(int64_t)img * b + q];
             const int prev = (st.decoding_constraint && t > 0) ? st.seq[cur][((int64_t)img * b + q) * L + t - 1] : -1;
-            const float mx = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sum += m[u] > -INFINITY ? sb_[u] * __expf(m[u] - mx) : 0.f;
-            const float lse = logf(wave_sum(sum));
             if (lane == 0) { row_mx[q] = mx; row_lse[q] = lse; }
             // the `want` largest block maxima, one wave arg-max round each (ties: the lower block)
             int selb[MAXB + 1];
@@ -149,11 +270,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
                     float bv_ = m[0]; int bb = lane;
 #pragma unroll
                     for (int u = 1; u < 4; ++u) if (m[u] > bv_) { bv_ = m[u]; bb = lane + 64 * u; }
-#pragma unroll
-                    for (int o2 = 32; o2 > 0; o2 >>= 1) {
-                        const float ov = __shfl_xor(bv_, o2, 64); const int ob = __shfl_xor(bb, o2, 64);
-                        if (ov > bv_ || (ov == bv_ && ob < bb)) { bv_ = ov; bb = ob; }
-                    }
+                    wave_argbest(bv_, bb);
                     selb[r] = bb; tau_raw = bv_;
 #pragma unroll
                     for (int u = 0; u < 4; ++u) if (bb == lane + 64 * u) m[u] = -INFINITY;      // (never selected twice)
@@ -181,7 +298,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
         __syncthreads();
         staged = cand_cnt2 <= 256 * MAXB;          // (massive ties: the exact per-thread lists below)
         __syncthreads();
-    } else if (FUSED && NPT > 0) {
+    } else if (NPT > 0) {
         // Register-resident rows: each thread holds its NPT strided elements of a row (ONE memory round trip per row, the
         // next row's loads are issued before the current row is reduced); max and sum-exp run in the element order of
         // log_softmax_kernel.  Candidate selection without per-thread sorted lists (their insertion network ran for almost
@@ -264,29 +381,26 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
         const float* lp = logp + srow * st.ldv;
         const float cum = t == 0 ? 0.f : st.cum[(int64_t)img * b + q];
         const int prev = (st.decoding_constraint && t > 0) ? st.seq[cur][((int64_t)img * b + q) * L + t - 1] : -1;
-        float mx = 0.f, lse = 0.f;
-        if (FUSED) {
-            float m = -INFINITY;
-            for (int v0 = tid; v0 < V; v0 += 256 * 8) {
-                float z[8];
+        float m = -INFINITY;
+        for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+            float z[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; z[u] = v < V ? lp[v] * scale : -INFINITY; }
+            for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; z[u] = v < V ? lp[v] * scale : -INFINITY; }
 #pragma unroll
-                for (int u = 0; u < 8; ++u) m = fmaxf(m, z[u]);
-            }
-            mx = blk_max(m, sh_red);
-            float sum = 0.f;
-            for (int v0 = tid; v0 < V; v0 += 256 * 8) {
-                float z[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; z[u] = v < V ? lp[v] : 0.f; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) if (v0 + 256 * u < V) sum += expf(z[u] * scale - mx);
-            }
-            sum = blk_sum(sum, sh_red);
-            lse = logf(sum);
-            if (tid == 0) { row_mx[q] = mx; row_lse[q] = lse; }
+            for (int u = 0; u < 8; ++u) m = fmaxf(m, z[u]);
         }
+        const float mx = blk_max(m, sh_red);
+        float sum = 0.f;
+        for (int v0 = tid; v0 < V; v0 += 256 * 8) {
+            float z[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int v = v0 + 256 * u; z[u] = v < V ? lp[v] : 0.f; }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) if (v0 + 256 * u < V) sum += expf(z[u] * scale - mx);
+        }
+        sum = blk_sum(sum, sh_red);
+        const float lse = logf(sum);
+        if (tid == 0) { row_mx[q] = mx; row_lse[q] = lse; }
         for (int v0 = tid; v0 < V; v0 += 256 * 8) {
             float z[8];
 #pragma unroll
@@ -295,12 +409,12 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
             for (int u = 0; u < 8; ++u) {
                 const int v = v0 + 256 * u;
                 if (v >= V || v == prev) continue;
-                float cv = cum + (FUSED ? (z[u] * scale - mx) - lse : z[u]);
+                float cv = cum + ((z[u] * scale - mx) - lse);
                 int ci = q * V + v;
-                if (better(cv, ci, bv[MAXB - 1], bi[MAXB - 1])) {
+                if (ortk_better(cv, ci, bv[MAXB - 1], bi[MAXB - 1])) {
 #pragma unroll
                     for (int k = 0; k < MAXB; ++k) {
-                        if (better(cv, ci, bv[k], bi[k])) {
+                        if (ortk_better(cv, ci, bv[k], bi[k])) {
                             const float tv = bv[k]; const int ti = bi[k];
                             bv[k] = cv; bi[k] = ci; cv = tv; ci = ti;
                         }
@@ -319,103 +433,21 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
 #pragma unroll
         for (int k = 0; k < MAXB; ++k) {
             const float v = sv[tid * MAXB + k]; const int i = si[tid * MAXB + k];
-            if (better(v, i, mv, mi)) { mv = v; mi = i; mp = tid * MAXB + k; }
+            if (ortk_better(v, i, mv, mi)) { mv = v; mi = i; mp = tid * MAXB + k; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(mv, o, 64); const int oi = __shfl_xor(mi, o, 64); const int op = __shfl_xor(mp, o, 64);
-            if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; mp = op; }
-        }
-        if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; red_pos[wave] = mp; }
-        __syncthreads();
+        blk_argbest(mv, mi, mp, red_v, red_i, red_pos);
         if (tid == 0) {
-            float fv = red_v[0]; int fi = red_i[0], fp = red_pos[0];
-            for (int w = 1; w < 4; ++w)
-                if (better(red_v[w], red_i[w], fv, fi)) { fv = red_v[w]; fi = red_i[w]; fp = red_pos[w]; }
-            win_v[r] = fv; win_i[r] = fi;
-            if (fp >= 0) sv[fp] = -INFINITY, si[fp] = 0x7FFFFFFF;
+            win_v[r] = mv; win_i[r] = mi;
+            if (mp >= 0) sv[mp] = -INFINITY, si[mp] = 0x7FFFFFFF;
         }
         __syncthreads();
     }
-    // (beam_step_wide_kernel carries a copy of everything from here to the end of this kernel: a change goes to both)
-    // histories, ancestry table, next tokens.  Every copy is spread over the whole workgroup: one thread per beam walking
-    // its t history entries and t+1 ancestry entries was a chain of ~50 dependent global round trips (the tail of this kernel
-    // grew with t and dominated it: 118 us per step at 1 024 images x 5 beams).
-    const int64_t row0 = (int64_t)img * b;
-    for (int idx = tid; idx < b * t; idx += 256) {
-        const int q = idx / t, u = idx - q * t;
-        const int parent = win_i[q] / V;
-        const int64_t nrow = row0 + q, prow = row0 + parent;
-        st.seq[nxt][nrow * L + u] = st.seq[cur][prow * L + u];
-        st.tok_lp[nxt][nrow * L + u] = st.tok_lp[cur][prow * L + u];
-    }
-    for (int idx = tid; idx < b * (t + 1); idx += 256) {
-        const int q = idx / (t + 1), u = idx - q * (t + 1);
-        const int parent = win_i[q] / V;
-        const int64_t srow = t == 0 ? img : row0 + parent;
-        const int32_t v = st.kvidx[cur][srow * (t + 1) + u];
-        st.kvidx[nxt][(row0 + q) * (t + 2) + u] = v;                                   // ancestors' cache rows
-        if (st.uniq) {      // measurement only: is this the first of the image's new beams that references cache row v?
-            bool first = true;
-            for (int q2 = 0; q2 < q; ++q2) {
-                const int64_t s2 = t == 0 ? img : row0 + win_i[q2] / V;
-                if (st.kvidx[cur][s2 * (t + 1) + u] == v) first = false;
-            }
-            if (first) atomicAdd(st.uniq, 1ull);
-        }
-    }
-    __shared__ int end_slot[MAXB];
-    if (tid < b) {
-        const int q = tid;
-        const int ix = win_i[q];
-        const int parent = ix / V, tok = ix - parent * V;
-        const int64_t nrow = row0 + q, prow = row0 + parent;
-        const int64_t srow = t == 0 ? img : prow;
-        st.seq[nxt][nrow * L + t] = tok;
-        const int pq = t == 0 ? 0 : parent;
-        st.tok_lp[nxt][nrow * L + t] = FUSED ? (logp[srow * st.ldv + tok] * scale - row_mx[pq]) - row_lse[pq] : logp[srow * st.ldv + tok];
-        st.it[nrow] = tok;
-        st.kvidx[nxt][nrow * (t + 2) + t + 1] = (int32_t)(nrow * st.tmax + t + 1);      // this beam's own slot at time t+1
-    }
-    // finished hypotheses: slots are handed out sequentially per image (insertion order matters for the final stable
-    // sort), the copies run in parallel afterwards
-    const int cap = b * L;
-    if (tid == 0) {
-        int cnt = st.done_cnt[img];
-        for (int q = 0; q < b; ++q) {
-            const int64_t nrow = row0 + q;
-            const int ix = win_i[q];
-            const int tok = ix - (ix / V) * V;
-            float cum = win_v[q];
-            const bool end = tok == st.eos || t == L - 1;
-            end_slot[q] = -1;
-            if (end) {
-                if (cnt < cap) {
-                    const int64_t base = ((int64_t)img * cap + cnt);
-                    end_slot[q] = cnt;
-                    st.done_len[base] = t + 1;
-                    st.done_p[base] = length_pen(st.length_penalty, st.length_alpha, t + 1, (double)cum);
-                    ++cnt;
-                }
-                cum -= 1000.f;
-            }
-            st.cum[nrow] = cum;
-        }
-        st.done_cnt[img] = cnt;
-    }
-    __syncthreads();          // end_slot, and the histories written above, are visible to the whole workgroup
-    for (int idx = tid; idx < b * (t + 1); idx += 256) {
-        const int q = idx / (t + 1), u = idx - q * (t + 1);
-        if (end_slot[q] < 0) continue;
-        const int64_t base = (int64_t)img * cap + end_slot[q], nrow = row0 + q;
-        st.done_seq[base * L + u] = st.seq[nxt][nrow * L + u];
-        st.done_lp[base * L + u] = st.tok_lp[nxt][nrow * L + u];
-    }
+    beam_commit(st, logp, t, scale, win_v, win_i, row_mx, row_lse, end_slot);
 }
 
 // ------------------------------------------------------------------------------------------------ wide beam step (9 .. 32 beams)
-// The same contract as beam_step_kernel for any b <= ORTK_MAX_BEAM, as kernel instances of its own (the narrow instances keep
-// their registers, LDS and code).  Selection, one workgroup per image:
+// The same contract as beam_step_kernel for any b <= ORTK_MAX_BEAM, as kernel instances of its own (the narrow selection keeps
+// its registers and LDS); the tail after the selection is the narrow kernel's, beam_commit.  Selection, one workgroup per image:
 //   * row statistics and candidate values by the narrow kernel's expressions in the same mode (blk_max / blk_sum over the
 //     256-strided elements, or the generator's 64-logit block statistics under STATS): at b <= 8 the two kernels agree bit for bit;
 //     (logit * scale - max is formed with ONE rounding everywhere in this kernel, __fmaf_rn, as log_softmax_kernel's single-use
@@ -444,22 +476,12 @@ struct WideLds {
     int cnt;
 };
 
-// block-wide best of (mv, mi) under better(); winner r -> S.win_v[r], S.win_i[r]; `clear`: mp is the winner's list position
+// block-wide best of (mv, mi) under ortk_better; winner r -> S.win_v[r], S.win_i[r]; `clear`: mp is the winner's list position
 __device__ __forceinline__ void wide_argbest(WideLds& S, float mv, int mi, int mp, int r, bool clear) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mv, o, 64); const int oi = __shfl_xor(mi, o, 64); const int op = __shfl_xor(mp, o, 64);
-        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; mp = op; }
-    }
-    if (lane == 0) { S.red_v[wave] = mv; S.red_i[wave] = mi; S.red_pos[wave] = mp; }
-    __syncthreads();
-    if (tid == 0) {
-        float fv = S.red_v[0]; int fi = S.red_i[0], fp = S.red_pos[0];
-        for (int w = 1; w < 4; ++w)
-            if (better(S.red_v[w], S.red_i[w], fv, fi)) { fv = S.red_v[w]; fi = S.red_i[w]; fp = S.red_pos[w]; }
-        S.win_v[r] = fv; S.win_i[r] = fi == 0x7FFFFFFF ? 0 : fi;      // (no candidate left — NaN rows: stay inside the tables)
-        if (clear && fp >= 0) S.cv[fp] = -INFINITY, S.ci[fp] = 0x7FFFFFFF;
+    blk_argbest(mv, mi, mp, S.red_v, S.red_i, S.red_pos);
+    if (threadIdx.x == 0) {
+        S.win_v[r] = mv; S.win_i[r] = mi == 0x7FFFFFFF ? 0 : mi;      // (no candidate left — NaN rows: stay inside the tables)
+        if (clear && mp >= 0) S.cv[mp] = -INFINITY, S.ci[mp] = 0x7FFFFFFF;
     }
     __syncthreads();
 }
@@ -477,19 +499,8 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
     if (STATS) {
         // one wave per row, the expressions of beam_step_kernel's STATS route
         for (int q = wave; q < nq; q += 4) {
-            const float* gs = gs0 + (int64_t)q * nblk * 2;
-            float m[4], sb_[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int blk = lane + 64 * u;
-                const float2 v2 = blk < nblk ? *reinterpret_cast<const float2*>(gs + 2 * blk) : make_float2(-INFINITY, 0.f);
-                m[u] = v2.x; sb_[u] = v2.y;
-            }
-            const float mx = wave_max(fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3])));
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sum += m[u] > -INFINITY ? sb_[u] * __expf(m[u] - mx) : 0.f;
-            const float lse = logf(wave_sum(sum));
+            float m[4], mx, lse;
+            stats_row_lse(gs0 + (int64_t)q * nblk * 2, nblk, m, mx, lse);
             if (lane == 0) { S.row_mx[q] = mx; S.row_lse[q] = lse; }
         }
     }
@@ -612,7 +623,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
             float mv = -INFINITY; int mi = 0x7FFFFFFF, mp = -1;
             for (int i = tid; i < n; i += 256) {
                 const float v = S.cv[i]; const int ix = S.ci[i];
-                if (better(v, ix, mv, mi)) { mv = v; mi = ix; mp = i; }
+                if (ortk_better(v, ix, mv, mi)) { mv = v; mi = ix; mp = i; }
             }
             wide_argbest(S, mv, mi, mp, r, true);
         }
@@ -637,7 +648,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
                     if (v >= V || v == pv) continue;
                     const float zz = cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]);
                     const int ix = q * V + v;
-                    if (better(lv, li, zz, ix) && better(zz, ix, mv, mi)) { mv = zz; mi = ix; }
+                    if (ortk_better(lv, li, zz, ix) && ortk_better(zz, ix, mv, mi)) { mv = zz; mi = ix; }
                 }
             }
         }
@@ -646,87 +657,19 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
     }
 }
 
-template <bool FUSED, int NPT, bool FASTEXP = false, bool STATS = false>
+template <int NPT, bool FASTEXP = false, bool STATS = false>
 __global__ __launch_bounds__(256) void beam_step_wide_kernel(BeamState st, const float* __restrict__ logp, int t, float scale) {
     __shared__ WideLds S;
     __shared__ int end_slot[WMAXB];
-    const int img = blockIdx.x, tid = threadIdx.x;
-    const int b = st.b, V = st.V, L = st.L;
+    const int b = st.b, L = st.L;
     const int nq = t == 0 ? 1 : b;
-    const int cur = t & 1, nxt = cur ^ 1;
-    const int64_t row0 = (int64_t)img * b;
-    const int64_t srow0 = t == 0 ? (int64_t)img : row0;
-    beam_select_wide<FUSED, NPT, FASTEXP, STATS>(S, logp + srow0 * st.ldv, st.ldv, nq, b, V, scale, t == 0 ? nullptr : st.cum + row0,
-                                                 (st.decoding_constraint && t > 0) ? st.seq[cur] + row0 * L + t - 1 : nullptr, L,
-                                                 STATS ? st.gstats + srow0 * st.nblk * 2 : nullptr, st.nblk);
-    // histories, ancestry table, next tokens, finished hypotheses: a copy of beam_step_kernel's tail (its instances keep their code
-    // bytes, so the tail is not shared): a change goes to both
-    for (int idx = tid; idx < b * t; idx += 256) {
-        const int q = idx / t, u = idx - q * t;
-        const int parent = S.win_i[q] / V;
-        const int64_t nrow = row0 + q, prow = row0 + parent;
-        st.seq[nxt][nrow * L + u] = st.seq[cur][prow * L + u];
-        st.tok_lp[nxt][nrow * L + u] = st.tok_lp[cur][prow * L + u];
-    }
-    for (int idx = tid; idx < b * (t + 1); idx += 256) {
-        const int q = idx / (t + 1), u = idx - q * (t + 1);
-        const int parent = S.win_i[q] / V;
-        const int64_t srow = t == 0 ? img : row0 + parent;
-        const int32_t v = st.kvidx[cur][srow * (t + 1) + u];
-        st.kvidx[nxt][(row0 + q) * (t + 2) + u] = v;
-        if (st.uniq) {
-            bool first = true;
-            for (int q2 = 0; q2 < q; ++q2) {
-                const int64_t s2 = t == 0 ? img : row0 + S.win_i[q2] / V;
-                if (st.kvidx[cur][s2 * (t + 1) + u] == v) first = false;
-            }
-            if (first) atomicAdd(st.uniq, 1ull);
-        }
-    }
-    if (tid < b) {
-        const int q = tid;
-        const int ix = S.win_i[q];
-        const int parent = ix / V, tok = ix - parent * V;
-        const int64_t nrow = row0 + q, prow = row0 + parent;
-        const int64_t srow = t == 0 ? img : prow;
-        st.seq[nxt][nrow * L + t] = tok;
-        const int pq = t == 0 ? 0 : parent;
-        st.tok_lp[nxt][nrow * L + t] = FUSED ? __fmaf_rn(logp[srow * st.ldv + tok], scale, -S.row_mx[pq]) - S.row_lse[pq] : logp[srow * st.ldv + tok];
-        st.it[nrow] = tok;
-        st.kvidx[nxt][nrow * (t + 2) + t + 1] = (int32_t)(nrow * st.tmax + t + 1);
-    }
-    const int cap = b * L;
-    if (tid == 0) {
-        int cnt = st.done_cnt[img];
-        for (int q = 0; q < b; ++q) {
-            const int64_t nrow = row0 + q;
-            const int ix = S.win_i[q];
-            const int tok = ix - (ix / V) * V;
-            float cum = S.win_v[q];
-            const bool end = tok == st.eos || t == L - 1;
-            end_slot[q] = -1;
-            if (end) {
-                if (cnt < cap) {
-                    const int64_t base = ((int64_t)img * cap + cnt);
-                    end_slot[q] = cnt;
-                    st.done_len[base] = t + 1;
-                    st.done_p[base] = length_pen(st.length_penalty, st.length_alpha, t + 1, (double)cum);
-                    ++cnt;
-                }
-                cum -= 1000.f;
-            }
-            st.cum[nrow] = cum;
-        }
-        st.done_cnt[img] = cnt;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < b * (t + 1); idx += 256) {
-        const int q = idx / (t + 1), u = idx - q * (t + 1);
-        if (end_slot[q] < 0) continue;
-        const int64_t base = (int64_t)img * cap + end_slot[q], nrow = row0 + q;
-        st.done_seq[base * L + u] = st.seq[nxt][nrow * L + u];
-        st.done_lp[base * L + u] = st.tok_lp[nxt][nrow * L + u];
-    }
+    const int cur = t & 1;
+    const int64_t row0 = (int64_t)blockIdx.x * b;
+    const int64_t srow0 = t == 0 ? (int64_t)blockIdx.x : row0;
+    beam_select_wide<true, NPT, FASTEXP, STATS>(S, logp + srow0 * st.ldv, st.ldv, nq, b, st.V, scale, t == 0 ? nullptr : st.cum + row0,
+                                                (st.decoding_constraint && t > 0) ? st.seq[cur] + row0 * L + t - 1 : nullptr, L,
+                                                STATS ? st.gstats + srow0 * st.nblk * 2 : nullptr, st.nblk);
+    beam_commit(st, logp, t, scale, S.win_v, S.win_i, S.row_mx, S.row_lse, end_slot);
 }
 
 // ortk_beam_select: the selection alone, winners to global memory
@@ -792,50 +735,67 @@ __global__ void sample_init_kernel(SampleState st, int bos) {
     if (blockIdx.x == 0 && threadIdx.x == 0) { st.last_step[0] = -1; st.last_step[1] = -1; }
 }
 
-// FAST (mixed precision only, with the fast exponential of the soft-max): v_log_f32 for the two logarithms — the same uniforms,
-// the noise to ~1 ulp (the SCST step did not move measurably: 23.2 ms either way)
-template <bool FAST = false>
-__device__ __forceinline__ float gumbel(uint64_t seed, int t, int row, int v) { return ortk_gumbel<FAST>(seed, t, row, v); }
+// what a row of the sampling state is at step t: the token it may not repeat (-1: none), whether it is one of the greedy rows of a
+// combined call, whether its token is drawn, and the row the noise hash is keyed by
+struct SampleRow { int prev; bool is_greedy, samp; int hrow; };
+__device__ __forceinline__ SampleRow sample_row_id(const SampleState& st, int row, int t) {
+    SampleRow r;
+    r.prev = (st.decoding_constraint && t > 0) ? (int)st.seq[(int64_t)row * st.L + t - 1] : -1;
+    r.is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
+    r.samp = st.sample && !r.is_greedy;
+    // the hash is keyed by the row index the sample would have in a samples-only call
+    const int64_t grow = st.row_offset + row;
+    r.hrow = (int)(st.greedy_stride > 0 ? grow - grow / st.greedy_stride - 1 : grow);
+    return r;
+}
+
+// the row's token of step t and its log-prob are known: the bookkeeping of every sampling step (one thread per row)
+__device__ __forceinline__ void sample_commit(const SampleState& st, int row, int t, int tok, float lp, bool is_greedy) {
+    const int unf = st.unfinished[row];
+    st.it[row] = tok;
+    st.seq[(int64_t)row * st.L + t] = unf ? tok : 0;     // seq[:, t] = it * unfinished   (transformer.py:546)
+    st.lp[(int64_t)row * st.L + t] = lp;                 // NOT masked after EOS          (transformer.py:548)
+    const int now = unf && (tok != st.eos);
+    st.unfinished[row] = now;
+    // the reference leaves the loop at the first step where no row is unfinished (transformer.py:550-551)
+    int32_t* last = st.last_step + (is_greedy ? 1 : 0);
+    if (unf && !now) atomicMax(last, t);
+    if (now && t == st.L - 1) atomicMax(last, t);
+}
 
 __global__ __launch_bounds__(256) void sample_step_kernel(SampleState st, const float* __restrict__ logp, int t) {
     __shared__ float red_v[4];
     __shared__ int red_i[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = blockIdx.x, tid = threadIdx.x;
     const float* lp = logp + (int64_t)row * st.ldv;
-    const int prev = (st.decoding_constraint && t > 0) ? (int)st.seq[(int64_t)row * st.L + t - 1] : -1;
-    const bool is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
-    const bool samp = st.sample && !is_greedy;
-    // the hash is keyed by the row index the sample would have in a samples-only call
-    const int64_t grow = st.row_offset + row;
-    const int hrow = (int)(st.greedy_stride > 0 ? grow - grow / st.greedy_stride - 1 : grow);
+    const SampleRow id = sample_row_id(st, row, t);
     float mv = -INFINITY; int mi = 0x7FFFFFFF;
     for (int v = tid; v < st.V; v += 256) {
-        if (v == prev) continue;
+        if (v == id.prev) continue;
         float x = lp[v];
-        if (samp) x = x / st.temperature + gumbel(st.seed, t, hrow, v);
-        if (better(x, v, mv, mi)) { mv = x; mi = v; }
+        if (id.samp) x = x / st.temperature + ortk_gumbel<false>(st.seed, t, id.hrow, v);
+        if (ortk_better(x, v, mv, mi)) { mv = x; mi = v; }
     }
+    blk_argbest(mv, mi, red_v, red_i);
+    if (tid == 0) sample_commit(st, row, t, mi, lp[mi], id.is_greedy);
+}
+
+// A row of raw logits into registers (one read: z[u] is column tid + 256 u, 0 past V) and the statistics of its log-soft-max, max and
+// lse = log sum exp(. - max), with the reductions of log_softmax_kernel in its element order
+template <int NPT, bool FASTEXP>
+__device__ __forceinline__ void row_lse(const float* __restrict__ lp, int V, float (&z)[NPT], float* sh_red, float& mx, float& lse) {
+    const int tid = threadIdx.x;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mv, o, 64); const int oi = __shfl_xor(mi, o, 64);
-        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; }
-    }
-    if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(red_v[w], red_i[w], mv, mi)) { mv = red_v[w]; mi = red_i[w]; }
-        const int unf = st.unfinished[row];
-        st.it[row] = mi;
-        st.seq[(int64_t)row * st.L + t] = unf ? mi : 0;      // seq[:, t] = it * unfinished   (transformer.py:546)
-        st.lp[(int64_t)row * st.L + t] = lp[mi];             // NOT masked after EOS          (transformer.py:548)
-        const int now = unf && (mi != st.eos);
-        st.unfinished[row] = now;
-        // the reference leaves the loop at the first step where no row is unfinished (transformer.py:550-551)
-        int32_t* last = st.last_step + (is_greedy ? 1 : 0);
-        if (unf && !now) atomicMax(last, t);
-        if (now && t == st.L - 1) atomicMax(last, t);
-    }
+    for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; z[u] = v < V ? lp[v] : 0.f; }
+    float m = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) m = fmaxf(m, z[u]);
+    mx = blk_max(m, sh_red);
+    float sum = 0.f;
+#pragma unroll
+    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < V) sum += exp_sel<FASTEXP>(z[u] - mx);
+    sum = blk_sum(sum, sh_red);
+    lse = logf(sum);
 }
 
 // Same step on RAW generator logits: the row stays in registers (one read), its log-soft-max statistics are taken with the
@@ -846,55 +806,22 @@ __global__ __launch_bounds__(256) void sample_step_fused_kernel(SampleState st, 
     __shared__ float sh_red[4];
     __shared__ float red_v[4], red_l[4];
     __shared__ int red_i[4];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* lp = logits + (int64_t)row * st.ldv;
-    float z[NPT];
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; z[u] = v < st.V ? lp[v] : 0.f; }
-    const int prev = (st.decoding_constraint && t > 0) ? (int)st.seq[(int64_t)row * st.L + t - 1] : -1;
-    const bool is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
-    const bool samp = st.sample && !is_greedy;
-    const int64_t grow = st.row_offset + row;
-    const int hrow = (int)(st.greedy_stride > 0 ? grow - grow / st.greedy_stride - 1 : grow);
-    float m = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) m = fmaxf(m, z[u]);
-    const float mx = blk_max(m, sh_red);
-    float sum = 0.f;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) sum += exp_sel<FASTEXP>(z[u] - mx);
-    sum = blk_sum(sum, sh_red);
-    const float lse = logf(sum);
+    const int row = blockIdx.x, tid = threadIdx.x;
+    float z[NPT], mx, lse;
+    row_lse<NPT, FASTEXP>(logits + (int64_t)row * st.ldv, st.V, z, sh_red, mx, lse);
+    const SampleRow id = sample_row_id(st, row, t);
     float mv = -INFINITY, ml = 0.f; int mi = 0x7FFFFFFF;
 #pragma unroll
     for (int u = 0; u < NPT; ++u) {
         const int v = tid + 256 * u;
-        if (v >= st.V || v == prev) continue;
+        if (v >= st.V || v == id.prev) continue;
         const float l = (z[u] - mx) - lse;
         float x = l;
-        if (samp) x = x / st.temperature + gumbel<FASTEXP>(st.seed, t, hrow, v);
-        if (better(x, v, mv, mi)) { mv = x; mi = v; ml = l; }
+        if (id.samp) x = x / st.temperature + ortk_gumbel<FASTEXP>(st.seed, t, id.hrow, v);
+        if (ortk_better(x, v, mv, mi)) { mv = x; mi = v; ml = l; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mv, o, 64), ol = __shfl_xor(ml, o, 64); const int oi = __shfl_xor(mi, o, 64);
-        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; ml = ol; }
-    }
-    if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; red_l[wave] = ml; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(red_v[w], red_i[w], mv, mi)) { mv = red_v[w]; mi = red_i[w]; ml = red_l[w]; }
-        const int unf = st.unfinished[row];
-        st.it[row] = mi;
-        st.seq[(int64_t)row * st.L + t] = unf ? mi : 0;
-        st.lp[(int64_t)row * st.L + t] = ml;
-        const int now = unf && (mi != st.eos);
-        st.unfinished[row] = now;
-        int32_t* last = st.last_step + (is_greedy ? 1 : 0);
-        if (unf && !now) atomicMax(last, t);
-        if (now && t == st.L - 1) atomicMax(last, t);
-    }
+    blk_argbest(mv, mi, ml, red_v, red_i, red_l);
+    if (tid == 0) sample_commit(st, row, t, mi, ml, id.is_greedy);
 }
 
 // ------------------------------------------------------------------------------------------------ truncated sampling (top-k / nucleus)
@@ -1033,60 +960,27 @@ __global__ __launch_bounds__(256) void sample_step_trunc_kernel(SampleState st, 
     __shared__ float red_v[4], red_l[4];
     __shared__ int red_i[4];
     __shared__ uint32_t sh_sel[8];
-    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* lp = logits + (int64_t)row * st.ldv;
-    float z[NPT];
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) { const int v = tid + 256 * u; z[u] = v < st.V ? lp[v] : 0.f; }
-    const int prev = (st.decoding_constraint && t > 0) ? (int)st.seq[(int64_t)row * st.L + t - 1] : -1;
-    const bool is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
-    const bool samp = st.sample && !is_greedy;
-    const int64_t grow = st.row_offset + row;
-    const int hrow = (int)(st.greedy_stride > 0 ? grow - grow / st.greedy_stride - 1 : grow);
-    float m = -INFINITY;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) m = fmaxf(m, z[u]);
-    const float mx = blk_max(m, sh_red);
-    float sum = 0.f;
-#pragma unroll
-    for (int u = 0; u < NPT; ++u) if (tid + 256 * u < st.V) sum += exp_sel<FASTEXP>(z[u] - mx);
-    sum = blk_sum(sum, sh_red);
-    const float lse = logf(sum);
+    const int row = blockIdx.x, tid = threadIdx.x;
+    float z[NPT], mx, lse;
+    row_lse<NPT, FASTEXP>(logits + (int64_t)row * st.ldv, st.V, z, sh_red, mx, lse);
+    const SampleRow id = sample_row_id(st, row, t);
     uint32_t key[NPT];
     TruncCut cut{1u, 256 * NPT, 0, 0.f};        // every candidate (greedy rows)
     int ph = 0;
-    if (samp) cut = trunc_select<NPT, FASTEXP>(z, key, st.V, prev, st.temperature, top_k, top_p, sh_sel, ph);
+    if (id.samp) cut = trunc_select<NPT, FASTEXP>(z, key, st.V, id.prev, st.temperature, top_k, top_p, sh_sel, ph);
     float mv = -INFINITY, ml = 0.f; int mi = 0x7FFFFFFF;
 #pragma unroll
     for (int u = 0; u < NPT; ++u) {
         const int v = tid + 256 * u;
-        if (v >= st.V || v == prev) continue;
-        if (samp && !trunc_in(key[u], v, cut)) continue;
+        if (v >= st.V || v == id.prev) continue;
+        if (id.samp && !trunc_in(key[u], v, cut)) continue;
         const float l = (z[u] - mx) - lse;
         float x = l;
-        if (samp) x = x / st.temperature + gumbel<FASTEXP>(st.seed, t, hrow, v);
-        if (better(x, v, mv, mi)) { mv = x; mi = v; ml = l; }
+        if (id.samp) x = x / st.temperature + ortk_gumbel<FASTEXP>(st.seed, t, id.hrow, v);
+        if (ortk_better(x, v, mv, mi)) { mv = x; mi = v; ml = l; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mv, o, 64), ol = __shfl_xor(ml, o, 64); const int oi = __shfl_xor(mi, o, 64);
-        if (better(ov, oi, mv, mi)) { mv = ov; mi = oi; ml = ol; }
-    }
-    if (lane == 0) { red_v[wave] = mv; red_i[wave] = mi; red_l[wave] = ml; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(red_v[w], red_i[w], mv, mi)) { mv = red_v[w]; mi = red_i[w]; ml = red_l[w]; }
-        const int unf = st.unfinished[row];
-        st.it[row] = mi;
-        st.seq[(int64_t)row * st.L + t] = unf ? mi : 0;
-        st.lp[(int64_t)row * st.L + t] = ml;
-        const int now = unf && (mi != st.eos);
-        st.unfinished[row] = now;
-        int32_t* last = st.last_step + (is_greedy ? 1 : 0);
-        if (unf && !now) atomicMax(last, t);
-        if (now && t == st.L - 1) atomicMax(last, t);
-    }
+    blk_argbest(mv, mi, ml, red_v, red_i, red_l);
+    if (tid == 0) sample_commit(st, row, t, mi, ml, id.is_greedy);
 }
 
 // ortk_sample_truncate: the cut of every row, by the device function of the step kernel
@@ -1112,7 +1006,7 @@ __global__ __launch_bounds__(256) void sample_truncate_kernel(const float* __res
 // The sampling step on the generator's own epilogue output (ortk_gemm_args.tile_samp + tile_stats): per row and block of 64 logits the
 // best Gumbel-max candidate {key, column, logit} and the soft-max partials {max, sum exp}.  One wave per row: arg-max over the blocks
 // (same total order as the row kernels: larger key, lower column on a tie), log-sum-exp from the partials, log-prob of the chosen token,
-// then the bookkeeping of sample_step_fused_kernel.  The logit rows (62 MB per position of the SCST rollout) are neither written nor read.
+// then sample_commit.  The logit rows (62 MB per position of the SCST rollout) are neither written nor read.
 template <bool FASTEXP>
 __global__ __launch_bounds__(256) void sample_combine_kernel(SampleState st, const float* __restrict__ gstats, const float* __restrict__ gsamp, int nblk, int t) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1129,24 +1023,8 @@ __global__ __launch_bounds__(256) void sample_combine_kernel(SampleState st, con
     float sum = 0.f;
     for (int b = lane; b < nblk; b += 64) { const float sb = gs[2 * b + 1]; if (sb > 0.f) sum += sb * exp_sel<FASTEXP>(gs[2 * b] - m); }
     sum = wave_sum(sum);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(mv, o, 64), oz = __shfl_xor(mz, o, 64); const int oi = __shfl_xor(mi, o, 64);
-        if (ortk_better(ov, oi, mv, mi)) { mv = ov; mi = oi; mz = oz; }
-    }
-    if (lane == 0) {
-        const float ml = (mz - m) - logf(sum);
-        const bool is_greedy = st.greedy_stride > 0 && row % st.greedy_stride == 0;
-        const int unf = st.unfinished[row];
-        st.it[row] = mi;
-        st.seq[(int64_t)row * st.L + t] = unf ? mi : 0;
-        st.lp[(int64_t)row * st.L + t] = ml;
-        const int now = unf && (mi != st.eos);
-        st.unfinished[row] = now;
-        int32_t* last = st.last_step + (is_greedy ? 1 : 0);
-        if (unf && !now) atomicMax(last, t);
-        if (now && t == st.L - 1) atomicMax(last, t);
-    }
+    wave_argbest(mv, mi, mz);
+    if (lane == 0) sample_commit(st, row, t, mi, (mz - m) - logf(sum), st.greedy_stride > 0 && row % st.greedy_stride == 0);
 }
 
 __global__ void sample_finalize_kernel(SampleState st) {
@@ -1193,26 +1071,21 @@ int kvidx_init(int32_t* kvidx, int64_t rows, int32_t row_mult, int32_t tmax, hip
     ORTK_CHECK_LAUNCH();
     return 0;
 }
-int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, bool fused, float scale, bool fast_exp, bool wide) {
+int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale, bool fast_exp, bool wide) {
     if (st.b < 1 || st.b > ORTK_MAX_BEAM) return ORTK_EINVAL;
     if (st.B == 0) return 0;
-    const dim3 grid((unsigned)st.B);
-    if (wide || st.b > MAXB) {      // 9 .. 32 beams (and the test switch): the wide step, the same instance for the same mode
-        if (fused && fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V)
-            hipLaunchKernelGGL((beam_step_wide_kernel<true, 0, true, true>), grid, dim3(256), 0, s, st, logp, t, scale);
-        else if (fused && st.V <= 256 * 40 && fast_exp) hipLaunchKernelGGL((beam_step_wide_kernel<true, 40, true>), grid, dim3(256), 0, s, st, logp, t, scale);
-        else if (fused && st.V <= 256 * 40) hipLaunchKernelGGL((beam_step_wide_kernel<true, 40>), grid, dim3(256), 0, s, st, logp, t, scale);
-        else if (fused) hipLaunchKernelGGL((beam_step_wide_kernel<true, 0>), grid, dim3(256), 0, s, st, logp, t, scale);
-        else            hipLaunchKernelGGL((beam_step_wide_kernel<false, 0>), grid, dim3(256), 0, s, st, logp, t, 1.f);
-        ORTK_CHECK_LAUNCH();
-        return 0;
-    }
-    if (fused && fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V)
-        hipLaunchKernelGGL((beam_step_kernel<true, 0, true, true>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
-    else if (fused && st.V <= 256 * 40 && fast_exp) hipLaunchKernelGGL((beam_step_kernel<true, 40, true>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
-    else if (fused && st.V <= 256 * 40) hipLaunchKernelGGL((beam_step_kernel<true, 40>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
-    else if (fused) hipLaunchKernelGGL((beam_step_kernel<true, 0>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale);
-    else            hipLaunchKernelGGL((beam_step_kernel<false, 0>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, 1.f);
+    // the instance <NPT, FASTEXP, STATS> of either step kernel: the same mode picks the same instance of both
+    const bool stats = fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V, reg_rows = st.V <= 256 * 40;
+#define ORTK_BEAM_STEP(kernel, ...) hipLaunchKernelGGL((kernel<__VA_ARGS__>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale)
+#define ORTK_BEAM_STEP_PICK(kernel)                                   \
+    if (stats) ORTK_BEAM_STEP(kernel, 0, true, true);                 \
+    else if (reg_rows && fast_exp) ORTK_BEAM_STEP(kernel, 40, true);  \
+    else if (reg_rows) ORTK_BEAM_STEP(kernel, 40);                    \
+    else ORTK_BEAM_STEP(kernel, 0)
+    if (wide || st.b > MAXB) { ORTK_BEAM_STEP_PICK(beam_step_wide_kernel); }      // 9 .. 32 beams (and the test switch)
+    else { ORTK_BEAM_STEP_PICK(beam_step_kernel); }
+#undef ORTK_BEAM_STEP_PICK
+#undef ORTK_BEAM_STEP
     ORTK_CHECK_LAUNCH();
     return 0;
 }

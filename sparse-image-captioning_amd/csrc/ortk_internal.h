@@ -66,10 +66,9 @@ struct BeamState {
     const float* gstats; int32_t nblk;
     unsigned long long* uniq = nullptr;   // measurement only (prof_slot): += the distinct cache rows the images' new beams reference at positions 0..t
 };
-// fused = true: `logp` holds raw logits and the log-soft-max of (logits * scale) is taken inside the step
+// `logp` holds raw logits: the log-soft-max of (logits * scale) is taken inside the step
 // wide = true: the wide step (beam_step_wide_kernel) at any width; widths above 8 always run it
-int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, bool fused = false, float scale = 1.f, bool fast_exp = false,
-              bool wide = false);
+int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale = 1.f, bool fast_exp = false, bool wide = false);
 int beam_finalize(const BeamState& st, int64_t* seq_out, float* lp_out, float* score_out, hipStream_t s);
 
 struct SampleState {

@@ -2176,7 +2176,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
         const bool fast_exp = cfg->precision == 1;                     // (the fp32 parity mode keeps libm's expf)
         if (beam && stack && ortk_prof_active()) { int ix = -1; bs.uniq = prof_slot(&ix); uniq_slot = ix + 1; }
         // log-soft-max fused into the candidate scan; 9 .. 32 beams (and debug bit 64, the parity tests' switch) run the wide step
-        if (beam) TRY(beam_step(bs, w.logits, t, s, true, scale, fast_exp, (op->exec_flags >> 8) & 64));
+        if (beam) TRY(beam_step(bs, w.logits, t, s, scale, fast_exp, (op->exec_flags >> 8) & 64));
         else if (samp_epi) TRY(sample_combine(ss, w.gstats, w.gsamp, (int32_t)(w.ldv / 64), t, s, fast_exp));      // the generator's epilogue has the candidates
         else if (trunc) TRY(sample_step_trunc(ss, w.logits, t, s, fast_exp, op->top_k, op->top_p));
         else if (V <= 256 * 40) TRY(sample_step(ss, w.logits, t, s, true, fast_exp));     // log-soft-max fused (scale is 1 on this branch)

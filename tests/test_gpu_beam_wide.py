@@ -266,6 +266,29 @@ def test_wide_step_equals_narrow_step_full_size_bf16(P, full_bf16, executor):
             assert torch.equal(a, c), (name, b, executor)
 
 
+TIE_V = 601       # 7 live rows x 601 > 4 096 (the wide list), 8 x 601 > 2 048 and 9 blocks x 64 x 8 > 2 048 (the narrow lists)
+
+
+@pytest.mark.parametrize("cfg,precision,opts", [(C.TINY_CFG, 0, {}), (dict(C.FULL_CFG, num_layers=2), 1, {"executor": "stack"})],
+                         ids=["fp32_register_rows", "bf16_stack_block_stats"])
+def test_narrow_step_tie_overflow_equals_wide_step(P, cfg, precision, opts):
+    """A generator of zeros: every logit of every row is equal, every element reaches the pruning bound of its row and the candidate
+    list overflows — in the narrow step (its exact per-thread lists take over: the register-resident rows in fp32, the generator's
+    block statistics in mixed precision on the stack executor) and in the wide step (its ranked passes).  Width 8, 2 images: both
+    return the same bytes, all of them finite."""
+    cfg = dict(cfg, vocab_size=TIE_V)
+    state = H.torch_state(H.dense_param_shapes(cfg), C.G2_SEED)
+    state["model.generator.proj.weight"].zero_()
+    state["model.generator.proj.bias"].zero_()
+    m = _model(P, cfg, state, precision=precision)
+    bt = _cuda(H.torch_batch(C.make_inputs(seed=1401, n_img=2, n_reg=12, feat=cfg["att_feat_size"], vocab=TIE_V, spi=1)))
+    narrow = _decode(m, bt, dict(opts, beam_size=8))
+    wide = _decode(m, bt, dict(opts, beam_size=8, stack_debug=64))
+    for name, a, c in zip(("seq", "logprobs", "score"), narrow, wide):
+        assert torch.equal(a, c), name
+        assert bool(torch.isfinite(a.float()).all()), name
+
+
 _ORACLE = {}
 
 
