@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 10     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 11     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -254,6 +254,26 @@ typedef struct ortk_spmm_args {
     const int32_t* drop_rows;
 } ortk_spmm_args;
 int ortk_spmm(const ortk_sparse_plan* plan, int32_t block, const ortk_spmm_args* a, ortk_stream stream);
+/* Which kernel form ortk_spmm(plan, block, a) would run: launches nothing, returns the code ortk_spmm would return for these arguments
+ * (ORTK_EINVAL included) and on success writes the form to buf (buf_bytes with the terminator).  Two codes of its own, for arguments
+ * ortk_spmm accepts: ORTK_EINVAL for a NULL buf or buf_bytes <= 0, ORTK_ENOSPC for a buf too short (left untouched).  An empty string:
+ * nothing to do (M zero).  Built by the code that builds ortk_spmm's own launch, under the ortk_tuning values of the moment; of the plan
+ * only blocks_host is read (the buffer pointers must be set, as for ortk_spmm), pointers of `a` are tested for alignment only, never
+ * dereferenced (no device needed).  Grammar:
+ *   form   = ell | gu
+ *   ell    = "ell<" XT "," KT "," NT "," ALIAS ">:rpw=" R ":stage=" ("fast" | "slow") ":epi=" epi
+ *   gu     = "gu<" MT "," MULTI ">:gsplit=" GS ":stage=" ("fast" | "slow" | "fast+tail") ":epi=" epi
+ *   epi    = "lean" | "general"
+ * ell<..> is the instance of spmm_ell_kernel: XT "f32" (ORTK_SP_ELL32) | "bf16" (ORTK_SP_ELL16), KT 512 | 2048 (plane capacity: K <= 512
+ * or more), NT 512 | 256 (threads per workgroup), ALIAS 0 | 1 (output tile over the planes); R = 1..4, the 512-column output ranges a
+ * workgroup walks.  gu<..> is the instance of spmm_gu_kernel: MT 1 | 2 | 4 (row tiles of 16 per workgroup), MULTI 0 | 1 (K > 512);
+ * GS = groups of 16 outputs per workgroup (a multiple of 8).  stage: how the activation tile reaches the LDS: "fast" = 16-byte loads of
+ * bf16 rows (bf16 X, ldx a multiple of 8, 16-byte aligned base; ELL: a bf16 format and K a multiple of 8), "slow" = element by element
+ * through fp32.  GU16 chooses per 512-wide chunk of K: "fast" = every chunk (K a multiple of 8), "fast+tail" = every whole chunk fast,
+ * the ragged last chunk (K > 512, K not a multiple of 8) element by element; a single ragged chunk is "slow".  epi: "lean" = bias / ReLU /
+ * residual on aligned vectors of 4, "general" otherwise.  Not in the string: the unrolled k-step count of the GU16 kernel (8 / 12 / 16),
+ * chosen on the device from plan->perm[block], the block's largest step count as the builder left it. */
+int ortk_spmm_plan(const ortk_sparse_plan* plan, int32_t block, const ortk_spmm_args* a, char* buf, int32_t buf_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Rows-stationary chain of the row-wise operators between two attention calls (csrc/ortk_chain.hip; mixed precision, d_model 512):

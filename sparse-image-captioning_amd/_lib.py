@@ -252,10 +252,11 @@ SIGNATURES = {
     "ortk_linear_block": (_I32, [_CFG, _I32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ortk_sparse_build": (_I32, [C.POINTER(EllPlanStruct), _P, _I32, _P]),
     "ortk_spmm": (_I32, [C.POINTER(EllPlanStruct), _I32, C.POINTER(SpmmArgs), _P]),
+    "ortk_spmm_plan": (_I32, [C.POINTER(EllPlanStruct), _I32, C.POINTER(SpmmArgs), C.c_char_p, _I32]),
 }
 
 _lib = None
-ABI_VERSION = 10     # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 11     # include/ortk.h: ORTK_VERSION
 
 
 def lib():
@@ -298,6 +299,19 @@ def gemm_plan(args):
     buf = C.create_string_buffer(256)
     check(lib().ortk_gemm_plan(C.byref(args), buf, len(buf)), "ortk_gemm_plan")
     return [k for k in buf.value.decode().split(";") if k]
+
+
+def spmm_plan(plan, block, args):
+    """The kernel form ortk_spmm(plan, block, args) would run, as one string (include/ortk.h: ortk_spmm_plan; "" for M == 0); raises
+    OrtkError where ortk_spmm would refuse the arguments.  plan: an EllPlanStruct, a pointer to one, or an object with ``ref()``.
+    Launches nothing and needs no device."""
+    if hasattr(plan, "ref"):
+        plan = plan.ref()
+    elif isinstance(plan, EllPlanStruct):
+        plan = C.pointer(plan)
+    buf = C.create_string_buffer(128)
+    check(lib().ortk_spmm_plan(plan, block, C.byref(args), buf, len(buf)), "ortk_spmm_plan")
+    return buf.value.decode()
 
 
 def require_gpu():

@@ -20,6 +20,8 @@
 //   VALU issue (4 cycles per wave instruction) and by 3-way bank conflicts of random 16-byte gathers and stays BELOW the dense
 //   MFMA GEMM at 95 % (profiles/r02_spmm_*).
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 #include "ortk_common.h"
 #include "ortk_internal.h"
 
@@ -60,6 +62,24 @@ __device__ __forceinline__ void load8(const void* X, int dt, int64_t ld, int64_t
             for (int i = 0; i < 8; ++i) v[i] = k0 + i < K ? p[i] : 0.f;
         }
     }
+}
+
+// The staging and epilogue choices of the product kernels.  The kernels evaluate them on the device; spmm_form() (the host
+// side of ortk_spmm and ortk_spmm_plan) evaluates the SAME functions, so the reported form cannot drift from the executed one.
+// ELL: bf16 rows go straight into the bf16 planes (16-byte loads, byte permutes)
+__host__ __device__ inline bool ell_xfast(bool f32, const ortk_spmm_args& a, int K) {
+    return !f32 && a.x_dtype == ORTK_BF16 && (K & 7) == 0 && (a.ldx & 7) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
+}
+// GU16: the same, per chunk of 512 input columns whose width is a multiple of 8 (a ragged last chunk is converted by elements)
+__host__ __device__ inline bool gu_xfast(const ortk_spmm_args& a) {
+    return a.x_dtype == ORTK_BF16 && (a.ldx & 7) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
+}
+// lean epilogue: bias / ReLU / residual only, everything vector-aligned, whole groups of 4 columns
+__host__ __device__ inline bool epi_lean(const ortk_spmm_args& a, int N) {
+    const bool al_b = !a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0;
+    const bool al_r = !a.resid || ((reinterpret_cast<uintptr_t>(a.resid) & 15) == 0 && (a.ldr & 3) == 0);
+    const bool al_y = (reinterpret_cast<uintptr_t>(a.Y) & (a.y_dtype == ORTK_BF16 ? 7 : 15)) == 0 && (a.ldy & 3) == 0;
+    return !a.gate && a.drop_p == 0.f && !a.rowscale && al_b && al_r && al_y && (N & 3) == 0;
 }
 
 struct SpmmP {
@@ -142,7 +162,7 @@ __global__ __launch_bounds__(NT) void spmm_ell_kernel(SpmmP p, int rpw, int ngro
     if (tid < MAXRPW) sNext[tid] = 0;
     // ---- stage the X tile transposed: plane h, slot(k): rows 8h..8h+7 (bf16) / 4h..4h+3 (fp32) of input column k
     const int Kp = (p.K + 7) & ~7;
-    const bool xfast = !F32 && a.x_dtype == ORTK_BF16 && (p.K & 7) == 0 && (a.ldx & 7) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
+    const bool xfast = ell_xfast(F32, a, p.K);
     if (xfast) {
         // bf16 rows straight into bf16 planes: the two rows of a pair are interleaved with byte permutes, no float round trip
         const unsigned short* X16 = reinterpret_cast<const unsigned short*>(a.X);
@@ -182,8 +202,7 @@ __global__ __launch_bounds__(NT) void spmm_ell_kernel(SpmmP p, int rpw, int ngro
     const bool al_r = !a.resid || ((reinterpret_cast<uintptr_t>(a.resid) & 15) == 0 && (a.ldr & 3) == 0);
     const bool al_g = a.gate && (reinterpret_cast<uintptr_t>(a.gate) & (a.gate_dtype == ORTK_BF16 ? 7 : 15)) == 0 && (a.ldg & 3) == 0;
     const bool al_y = (reinterpret_cast<uintptr_t>(a.Y) & (a.y_dtype == ORTK_BF16 ? 7 : 15)) == 0 && (a.ldy & 3) == 0;
-    // lean epilogue: bias / ReLU / residual only, everything vector-aligned, whole groups of 4 columns
-    const bool lean = !a.gate && a.drop_p == 0.f && !a.rowscale && al_b && al_r && al_y && (p.N & 3) == 0;
+    const bool lean = epi_lean(a, p.N);
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
     for (int ri = 0; ri < rpw; ++ri) {
         const int rg = rg0 + ri;
@@ -650,10 +669,7 @@ __global__ __launch_bounds__(GNT) void spmm_gu_kernel(GuP p) {
     const ortk_spmm_args& a = p.a;
     const int lg = lane >> 4, pp = lane & 3;
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-    const bool lean = !a.gate && a.drop_p == 0.f && !a.rowscale && (p.N & 3) == 0 && (a.ldy & 3) == 0 &&
-                      (reinterpret_cast<uintptr_t>(a.Y) & (a.y_dtype == ORTK_BF16 ? 7 : 15)) == 0 &&
-                      (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15) == 0) &&
-                      (!a.resid || ((reinterpret_cast<uintptr_t>(a.resid) & 15) == 0 && (a.ldr & 3) == 0));
+    const bool lean = epi_lean(a, p.N);
     auto store_group = [&](int gg, f32x4 (&v)[MT]) {
         const int n0 = 16 * gg + 4 * lg;
         if (lean) {
@@ -671,7 +687,7 @@ __global__ __launch_bounds__(GNT) void spmm_gu_kernel(GuP p) {
     for (int gi = 0; gi < (MULTI ? GPW : 1); ++gi)
 #pragma unroll
         for (int t = 0; t < MT; ++t) acc[gi][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bool xfast = a.x_dtype == ORTK_BF16 && (a.ldx & 7) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0;
+    const bool xfast = gu_xfast(a);
     const unsigned char* xcol = smem + 8 * pp;        // this lane's 4 columns inside a row tile (+ 32 t)
     const int smax = *p.smax;                          // block-wide bound of the k-steps per (group, chunk)
     const int sbound = smax <= 8 ? 8 : smax <= 12 ? 12 : 16;    // the unrolled body that serves it
@@ -786,8 +802,64 @@ bool plan_ok(const ortk_sparse_plan* p) {
     return (p->format == ORTK_SP_ELL32 || p->format == ORTK_SP_ELL16) && p->perm && p->overflow;
 }
 
+// Everything ortk_spmm decides on the host, for one (plan, block, args): the kernel instance, its grid parameters and the staging /
+// epilogue paths the kernel will take.  ortk_spmm launches from it, ortk_spmm_plan prints it.
+struct SpmmForm {
+    bool empty;                                   // M == 0: nothing to launch
+    bool gu;
+    // ELL
+    bool f32; int KT, NT, rpw, ngroups, nranges; bool alias;
+    // GU16
+    int mt, gsplit, G, nkc; bool multi;
+    int stage;                                    // 0 slow (element-wise conversion), 1 fast, 2 fast on the whole chunks + a ragged last chunk by elements
+    bool lean;
+};
+
+// 0 and `f` filled, or the code ortk_spmm returns for these arguments.  Reads blocks_host only; pointers are tested, never followed.
+int spmm_form(const ortk_sparse_plan* plan, int32_t block, const ortk_spmm_args* a, SpmmForm& f) {
+    if (!plan_ok(plan) || !a || block < 0 || block >= plan->nblocks || !a->X || !a->Y || a->M < 0) return ORTK_EINVAL;
+    auto dt_ok = [](int d) { return d == ORTK_F32 || d == ORTK_BF16; };
+    if (!dt_ok(a->x_dtype) || !dt_ok(a->y_dtype) || !dt_ok(a->gate_dtype)) return ORTK_EINVAL;
+    f = SpmmForm{};
+    if (a->M == 0) { f.empty = true; return 0; }
+    const ortk_sparse_block& b = plan->blocks_host[block];
+    f.lean = epi_lean(*a, b.N);
+    if (plan->format == ORTK_SP_GU16) {
+        f.gu = true;
+        f.G = (int)ortk_cdiv(b.N, 16); f.nkc = (int)ortk_cdiv(b.K, GKC);
+        f.multi = f.nkc > 1;
+        if (f.multi && f.G > 8 * GPW) return ORTK_EINVAL;
+        // Row tile: as many rows as still give the chip enough workgroups (the compacted weights are streamed once per row
+        // tile); short grids are widened by splitting the groups of a row tile over several workgroups.
+        f.mt = a->M >= 8192 ? 4 : a->M >= 2048 ? 2 : 1;      // (a 128-row tile spills registers: not offered)
+        const int64_t tiles = ortk_cdiv(a->M, 16 * f.mt);
+        int split = 1;                                   // workgroups per row tile
+        while (tiles * split < 384 && f.G / (split * 2) >= 8) split *= 2;
+        f.gsplit = (int)ortk_cdiv(f.G, split);
+        f.gsplit = (int)ortk_cdiv(f.gsplit, 8) * 8;      // whole rounds of the 8 waves
+        // the kernel stages chunk kc fast when gu_xfast and its width min(512, K - 512 kc) is a multiple of 8
+        f.stage = !gu_xfast(*a) ? 0 : (b.K & 7) == 0 ? 1 : f.multi ? 2 : 0;
+        return 0;
+    }
+    if (b.K > KMAX) return ORTK_EINVAL;
+    f.f32 = plan->format != ORTK_SP_ELL16;
+    f.KT = b.K <= 512 ? 512 : 2048;
+    f.nranges = (int)ortk_cdiv(b.N, RANGE);
+    const int64_t tiles = ortk_cdiv(a->M, f.f32 ? 8 : 16);
+    // long grids: a workgroup walks up to 4 ranges (X staged once); short grids: one range per workgroup and 8 waves
+    f.rpw = tiles * f.nranges > 2048 ? std::min(4, f.nranges) : 1;
+    f.ngroups = (int)ortk_cdiv(f.nranges, f.rpw);
+    // one range per workgroup: the output tile over the planes (wide inputs: two workgroups per compute unit instead of one)
+    // (wide inputs only: with 512 input columns the planes are 16 KB, three workgroups share a CU either way, and the held tile measured
+    //  no faster)
+    f.alias = f.rpw == 1 && f.KT > 512 && ortk::tuning().spmm_alias != 0;
+    f.NT = tiles * f.ngroups <= 640 ? 512 : 256;
+    f.stage = ell_xfast(f.f32, *a, b.K) ? 1 : 0;
+    return 0;
+}
+
 template <typename XT, int KT>
-int launch_spmm(const SpmmP& p, hipStream_t s) {
+int launch_spmm(const SpmmP& p, const SpmmForm& f, hipStream_t s) {
     constexpr int RB = sizeof(XT) == 4 ? 8 : 16;
     const size_t tile_b = (size_t)RB * OP * sizeof(float);
     const size_t lds = (size_t)2 * KT * 16 + tile_b + MAXRPW * sizeof(int);
@@ -797,20 +869,13 @@ int launch_spmm(const SpmmP& p, hipStream_t s) {
     ortk::lds_attr(reinterpret_cast<const void*>(spmm_ell_kernel<XT, KT, 256, true>), lds_alias);
     ortk::lds_attr(reinterpret_cast<const void*>(spmm_ell_kernel<XT, KT, 512, true>), lds_alias);
     const int64_t tiles = ortk_cdiv(p.a.M, RB);
-    // long grids: a workgroup walks up to 4 ranges (X staged once); short grids: one range per workgroup and 8 waves
-    const int rpw = tiles * p.nranges > 2048 ? std::min(4, p.nranges) : 1;
-    const int ngroups = (int)ortk_cdiv(p.nranges, rpw);
-    const dim3 grid((unsigned)(tiles * ngroups));
-    // one range per workgroup: the output tile over the planes (wide inputs: two workgroups per compute unit instead of one)
-    // (wide inputs only: with 512 input columns the planes are 16 KB, three workgroups share a CU either way, and the held tile measured
-    //  no faster)
-    const bool alias = rpw == 1 && KT > 512 && ortk::tuning().spmm_alias != 0;
-    if (tiles * ngroups <= 640) {
-        if (alias) hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 512, true>), grid, dim3(512), lds_alias, s, p, rpw, ngroups);
-        else hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 512, false>), grid, dim3(512), lds, s, p, rpw, ngroups);
+    const dim3 grid((unsigned)(tiles * f.ngroups));
+    if (f.NT == 512) {
+        if (f.alias) hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 512, true>), grid, dim3(512), lds_alias, s, p, f.rpw, f.ngroups);
+        else hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 512, false>), grid, dim3(512), lds, s, p, f.rpw, f.ngroups);
     } else {
-        if (alias) hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 256, true>), grid, dim3(256), lds_alias, s, p, rpw, ngroups);
-        else hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 256, false>), grid, dim3(256), lds, s, p, rpw, ngroups);
+        if (f.alias) hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 256, true>), grid, dim3(256), lds_alias, s, p, f.rpw, f.ngroups);
+        else hipLaunchKernelGGL((spmm_ell_kernel<XT, KT, 256, false>), grid, dim3(256), lds, s, p, f.rpw, f.ngroups);
     }
     ORTK_CHECK_LAUNCH();
     return 0;
@@ -865,38 +930,45 @@ extern "C" int ortk_sparse_build(const ortk_sparse_plan* plan, const void* dense
 }
 
 extern "C" int ortk_spmm(const ortk_sparse_plan* plan, int32_t block, const ortk_spmm_args* a, ortk_stream stream) {
-    if (!plan_ok(plan) || !a || block < 0 || block >= plan->nblocks || !a->X || !a->Y || a->M < 0) return ORTK_EINVAL;
-    auto dt_ok = [](int d) { return d == ORTK_F32 || d == ORTK_BF16; };
-    if (!dt_ok(a->x_dtype) || !dt_ok(a->y_dtype) || !dt_ok(a->gate_dtype)) return ORTK_EINVAL;
-    if (a->M == 0) return 0;
+    SpmmForm f;
+    if (const int rc = spmm_form(plan, block, a, f)) return rc;
+    if (f.empty) return 0;
     const ortk_sparse_block& b = plan->blocks_host[block];
     hipStream_t s = ortk_s(stream);
-    if (plan->format == ORTK_SP_GU16) {
+    if (f.gu) {
         GuP p;
         p.wfrag = reinterpret_cast<const unsigned short*>(plan->stream); p.kofs = reinterpret_cast<const uint32_t*>(plan->chunk_ptr);
         p.nsteps = plan->chunk_len; p.smax = plan->perm + block; p.slot0 = b.chunk0; p.N = b.N; p.K = b.K;
-        p.G = (int)ortk_cdiv(b.N, 16); p.nkc = (int)ortk_cdiv(b.K, GKC);
+        p.G = f.G; p.nkc = f.nkc; p.gsplit = f.gsplit;
         p.a = *a;
-        const bool multi = p.nkc > 1;
-        if (multi && p.G > 8 * GPW) return ORTK_EINVAL;
-        // Row tile: as many rows as still give the chip enough workgroups (the compacted weights are streamed once per row
-        // tile); short grids are widened by splitting the groups of a row tile over several workgroups.
-        const int mt = a->M >= 8192 ? 4 : a->M >= 2048 ? 2 : 1;      // (a 128-row tile spills registers: not offered)
-        const int64_t tiles = ortk_cdiv(a->M, 16 * mt);
-        int split = 1;                                   // workgroups per row tile
-        while (tiles * split < 384 && p.G / (split * 2) >= 8) split *= 2;
-        p.gsplit = (int)ortk_cdiv(p.G, split);
-        p.gsplit = (int)ortk_cdiv(p.gsplit, 8) * 8;      // whole rounds of the 8 waves
-        if (multi) return mt == 1 ? launch_gu<1, true>(p, s) : mt == 2 ? launch_gu<2, true>(p, s) : launch_gu<4, true>(p, s);
-        return mt == 1 ? launch_gu<1, false>(p, s) : mt == 2 ? launch_gu<2, false>(p, s) : launch_gu<4, false>(p, s);
+        if (f.multi) return f.mt == 1 ? launch_gu<1, true>(p, s) : f.mt == 2 ? launch_gu<2, true>(p, s) : launch_gu<4, true>(p, s);
+        return f.mt == 1 ? launch_gu<1, false>(p, s) : f.mt == 2 ? launch_gu<2, false>(p, s) : launch_gu<4, false>(p, s);
     }
-    if (b.K > KMAX) return ORTK_EINVAL;
     SpmmP p;
     p.stream = plan->stream; p.chunk_ptr = plan->chunk_ptr + b.chunk0; p.chunk_len = plan->chunk_len + b.chunk0;
     p.perm = plan->perm + (int64_t)b.chunk0 * 64;
-    p.N = b.N; p.K = b.K; p.nchunks = (int)ortk_cdiv(b.N, 64); p.nranges = (int)ortk_cdiv(b.N, RANGE);
+    p.N = b.N; p.K = b.K; p.nchunks = (int)ortk_cdiv(b.N, 64); p.nranges = f.nranges;
     p.a = *a;
-    const bool small = b.K <= 512;
-    if (plan->format == ORTK_SP_ELL16) return small ? launch_spmm<__bf16, 512>(p, s) : launch_spmm<__bf16, 2048>(p, s);
-    return small ? launch_spmm<float, 512>(p, s) : launch_spmm<float, 2048>(p, s);
+    if (!f.f32) return f.KT == 512 ? launch_spmm<__bf16, 512>(p, f, s) : launch_spmm<__bf16, 2048>(p, f, s);
+    return f.KT == 512 ? launch_spmm<float, 512>(p, f, s) : launch_spmm<float, 2048>(p, f, s);
+}
+
+extern "C" int ortk_spmm_plan(const ortk_sparse_plan* plan, int32_t block, const ortk_spmm_args* a, char* buf, int32_t buf_bytes) {
+    SpmmForm f;
+    if (const int rc = spmm_form(plan, block, a, f)) return rc;
+    if (!buf || buf_bytes <= 0) return ORTK_EINVAL;
+    char text[96];
+    int n = 0;
+    text[0] = 0;
+    static const char* const stage[3] = {"slow", "fast", "fast+tail"};
+    if (f.empty) {
+    } else if (f.gu) {
+        n = snprintf(text, sizeof text, "gu<%d,%d>:gsplit=%d:stage=%s:epi=%s", f.mt, (int)f.multi, f.gsplit, stage[f.stage], f.lean ? "lean" : "general");
+    } else {
+        n = snprintf(text, sizeof text, "ell<%s,%d,%d,%d>:rpw=%d:stage=%s:epi=%s", f.f32 ? "f32" : "bf16", f.KT, f.NT, (int)f.alias, f.rpw,
+                     stage[f.stage], f.lean ? "lean" : "general");
+    }
+    if (n + 1 > buf_bytes) return ORTK_ENOSPC;
+    memcpy(buf, text, (size_t)n + 1);
+    return 0;
 }

@@ -11,12 +11,10 @@ import pytest
 import torch
 
 import gemm_exact as X
+from exact_gpu import SLACK, _KEEP, mismatch, place
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-SLACK = 64          # elements around every operand (a multiple of 8: the alignment of the buffer carries over)
-_KEEP = []
 _PLANS = {}
 _RECORD = []
 _REF = {}
@@ -36,19 +34,6 @@ def release_buffers():
     del _KEEP[:]
 
 
-def place(t, ld, off, dtype, fill=NAN):
-    """The (rows, cols) CPU matrix (or vector) inside a device buffer of `fill`: SLACK + off elements ahead of it, row pitch ld, two more
-    rows and SLACK behind.  Returns (buffer, matrix view, address of the first element)."""
-    t2 = t if t.dim() == 2 else t[None, :]
-    rows, cols = t2.shape
-    ld = cols if ld is None else ld
-    buf = torch.full((SLACK + off + (rows + 2) * ld + SLACK,), fill, dtype=dtype, device="cuda")
-    view = buf[SLACK + off: SLACK + off + rows * ld].view(rows, ld)[:, :cols]
-    view.copy_(t2.to(dtype).cuda())
-    _KEEP.append(buf)
-    return buf, view, buf.data_ptr() + (SLACK + off) * buf.element_size()
-
-
 def keep_mask(L, c, o, seed):
     """0 / 2 per output element: the draws of ortk_dropout_apply on ones over the index space, taken at each element's index"""
     idx = X.drop_index(c, o)
@@ -59,14 +44,6 @@ def keep_mask(L, c, o, seed):
     k = out[idx.cuda()].cpu().double()
     assert set(k.unique().tolist()) <= {0.0, 2.0}
     return k
-
-
-def mismatch(got, want, what):
-    bad = (got != want).nonzero()
-    rows = ["%s: %d of %d elements differ" % (what, bad.shape[0], want.numel())]
-    for ix in bad[:8].tolist():
-        rows.append("  %s: got %r, want %r" % (tuple(ix), got[tuple(ix)].item(), want[tuple(ix)].item()))
-    return "\n".join(rows)
 
 
 def run_case(L, c):

@@ -256,3 +256,80 @@ def test_label_smoothing_criterion_vs_reference_golden():
         assert abs(float(loss) - want["loss"]) < 1e-5
         assert abs(float(grad.abs().sum()) - want["grad_abs_sum"]) < 1e-4
         assert abs(float(grad[0, 0, 5]) - want["grad_0_0_5"]) < 1e-6
+
+
+def test_spmm_plan_query_answers_without_a_device():
+    """ortk_spmm_plan: the form strings for a few shapes of each format, its own two error codes, and what ortk_spmm refuses."""
+    import spmm_exact as X
+    import sparse_image_captioning_amd as P
+    L = P._lib
+    lib = L.lib()
+
+    def args(M, xdt=1, ydt=0, ldx=528, ldy=1104, **kw):
+        a = L.SpmmArgs()
+        a.X, a.Y, a.ldx, a.ldy, a.M, a.x_dtype, a.y_dtype = 0x1000000, 0x2000000, ldx, ldy, M, xdt, ydt
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    shapes = [(70, 40), (1100, 520), (512, 2048), (132, 72)]
+    want = {
+        X.ELL32: [((1, 9), "ell<f32,2048,512,1>:rpw=1:stage=slow:epi=lean"), ((1, 5500), "ell<f32,2048,256,0>:rpw=3:stage=slow:epi=lean"),
+                  ((2, 9), "ell<f32,2048,512,1>:rpw=1:stage=slow:epi=lean"), ((3, 9), "ell<f32,512,512,0>:rpw=1:stage=slow:epi=lean"),
+                  ((0, 6000), "ell<f32,512,256,0>:rpw=1:stage=slow:epi=general")],
+        X.ELL16: [((1, 9), "ell<bf16,2048,512,1>:rpw=1:stage=fast:epi=lean"), ((1, 11000), "ell<bf16,2048,256,0>:rpw=3:stage=fast:epi=lean"),
+                  ((2, 3600), "ell<bf16,2048,512,1>:rpw=1:stage=fast:epi=lean"), ((3, 9), "ell<bf16,512,512,0>:rpw=1:stage=fast:epi=lean"),
+                  ((0, 20000), "ell<bf16,512,256,0>:rpw=1:stage=fast:epi=general")],
+        X.GU16: [((0, 9), "gu<1,0>:gsplit=8:stage=fast:epi=general"), ((2, 9), "gu<1,1>:gsplit=8:stage=fast:epi=lean"),
+                 ((2, 2048), "gu<2,1>:gsplit=8:stage=fast:epi=lean"), ((2, 30000), "gu<4,1>:gsplit=32:stage=fast:epi=lean"),
+                 ((3, 8192), "gu<4,0>:gsplit=16:stage=fast:epi=lean")],
+    }
+    for fmt, rows in want.items():
+        p, host = X.fake_plan(L, fmt, shapes if fmt != X.GU16 else [shapes[0], (512, 520), shapes[2], shapes[3]])
+        for (block, M), form in rows:
+            assert L.spmm_plan(p, block, args(M)) == form, (fmt, block, M)
+    # staging and epilogue follow the pointers and strides, never what they point to; the tuning switch is read as the call reads it
+    p, host = X.fake_plan(L, X.ELL16, shapes)
+    assert L.spmm_plan(p, 1, args(9, ldx=523)).endswith("stage=slow:epi=lean")
+    assert L.spmm_plan(p, 1, args(9, X=0x1000004)).endswith("stage=slow:epi=lean")
+    assert L.spmm_plan(p, 1, args(9, xdt=0)).endswith("stage=slow:epi=lean")
+    assert L.spmm_plan(p, 1, args(9, ldy=1101)).endswith("stage=fast:epi=general")
+    assert L.spmm_plan(p, 1, args(9, bias=0x3000004)).endswith("epi=general")
+    assert L.spmm_plan(p, 1, args(9, resid=0x3000000, ldr=1101)).endswith("epi=general")
+    assert L.spmm_plan(p, 1, args(9, rowscale=0x3000000)).endswith("epi=general")
+    assert L.spmm_plan(p, 1, args(9, drop_p=0.5)).endswith("epi=general")
+    assert L.spmm_plan(p, 1, args(9, gate=0x3000000, ldg=1104)).endswith("epi=general")
+    prev = L.set_tuning(spmm_alias=0)
+    try:
+        assert L.spmm_plan(p, 1, args(9)) == "ell<bf16,2048,512,0>:rpw=1:stage=fast:epi=lean"
+    finally:
+        L.set_tuning(**prev)
+    g, ghost = X.fake_plan(L, X.GU16, [(70, 40), (48, 1030), (5, 3)])
+    assert L.spmm_plan(g, 1, args(9, ldx=1032)) == "gu<1,1>:gsplit=8:stage=fast+tail:epi=lean"
+    assert L.spmm_plan(g, 1, args(9, ldx=1031)) == "gu<1,1>:gsplit=8:stage=slow:epi=lean"
+    assert L.spmm_plan(g, 2, args(9, ldx=8)) == "gu<1,0>:gsplit=8:stage=slow:epi=general"
+    # an empty product launches nothing; a buffer that is too short is refused, never overrun
+    a = args(9)
+    assert L.spmm_plan(p, 1, args(0)) == ""
+    buf = C.create_string_buffer(b"#" * 64, 64)
+    form = b"ell<bf16,2048,512,1>:rpw=1:stage=fast:epi=lean"
+    assert lib.ortk_spmm_plan(C.byref(p), 1, C.byref(a), buf, len(form)) == -2 and buf.raw == b"#" * 64
+    assert lib.ortk_spmm_plan(C.byref(p), 1, C.byref(a), buf, len(form) + 1) == 0 and buf.value == form
+    assert lib.ortk_spmm_plan(C.byref(p), 1, C.byref(a), None, 64) == -1
+    assert lib.ortk_spmm_plan(C.byref(p), 1, C.byref(a), buf, 0) == -1
+    # what ortk_spmm refuses, refused with its code: block out of range, bad dtypes, missing pointers, a GU16 block with K > 512 and
+    # N > 512, an ELL block with K > 2 048, a plan without its buffers
+    q = lambda plan, block, a: lib.ortk_spmm_plan(C.byref(plan), block, C.byref(a), buf, 64)
+    bad = [q(p, 4, a), q(p, -1, a), q(p, 1, args(9, xdt=2)), q(p, 1, args(9, ydt=-1)), q(p, 1, args(9, gate_dtype=2)), q(p, 1, args(-1)),
+           q(p, 1, args(9, X=0)), q(p, 1, args(9, Y=0)), lib.ortk_spmm_plan(None, 0, C.byref(a), buf, 64), lib.ortk_spmm_plan(C.byref(p), 1, None, buf, 64)]
+    wide, whost = X.fake_plan(L, X.GU16, [(70, 40), (528, 520)])
+    long_, lhost = X.fake_plan(L, X.ELL16, [(70, 40), (64, 2049)])
+    bad += [q(wide, 1, a), q(long_, 1, a)]
+    assert q(wide, 0, a) == 0 and q(long_, 0, a) == 0
+    for field in ("stream", "perm", "blocks_dev"):
+        nobuf, nhost = X.fake_plan(L, X.ELL16, shapes)
+        setattr(nobuf, field, None)
+        bad.append(q(nobuf, 1, a))
+    nobuf, nhost = X.fake_plan(L, 3, shapes)
+    bad.append(q(nobuf, 1, a))
+    assert bad == [-1] * len(bad)
