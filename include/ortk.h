@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 11     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 12     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -506,6 +506,23 @@ typedef struct ortk_decode_opts {
      * cfg->vocab > 10 240 (the row is held in registers: ortk_sample_truncate). */
     int32_t top_k;
     float   top_p;
+    /* Beam decodes only: DIVERSE beam search, the groups of CaptionModel.batch_beam_search (caption_model.py:33-52, 151-218).
+     * group_size = G (0 and 1: one group, the plain beam search, diversity_lambda is not read) splits the beam_size = b beams of an
+     * image into G groups of bd = b / G; every group is a beam search of width bd of its own (histories, cumulative scores, caches,
+     * finished lists) decoded at its own position.  The schedule is staggered: at global step T = 0 .. seq_len + G - 2, group
+     * g = 0 .. G - 1 in this order does its local step t = T - g (if 0 <= t < seq_len).  In that step the log-prob of token v of every
+     * row of the group first loses fl32(cnt * diversity_lambda) (one fp32 multiply, one fp32 subtract), cnt = the number of the
+     * g * bd current beams of groups 0 .. g-1 of the image that hold v at column t of their histories as they stand at that moment
+     * (group p has then done min(t + g - p, seq_len - 1) + 1 steps and re-ordered its histories by parent since its own step t).
+     * Candidates cum + augmented log-prob rank as in the plain step; cum is the augmented sum, the stored token log-prob the
+     * unaugmented one (with the -inf of decoding_constraint), finished beams score length_penalty(t + 1, cum).  Output rows
+     * g * bd .. (g + 1) * bd - 1 of an image: group g's best bd finished hypotheses.  Group 0 is the plain beam search of width bd.
+     * bd = 1 (G = b) is served.  Executors: the unfused one (exec_flags 0, ORTK_DEC_SPLIT_SMALL alone or ORTK_DEC_UNFUSED), in both
+     * precisions and with a sparse plan; G launch sequences per position.
+     * ORTK_EINVAL (ortk_decode_workspace_bytes: 0): G < 0; with G > 1: b % G != 0, G > b, b > ORTK_MAX_BEAM, diversity_lambda negative
+     * or not finite, num_random_sample > 0, train, an exec_flags bit of the stack family. */
+    int32_t group_size;
+    float   diversity_lambda;
 } ortk_decode_opts;
 
 size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o);
@@ -765,6 +782,15 @@ int ortk_sample_truncate(const float* logits, int64_t rows, int32_t V, int64_t l
  * at ANY b (this is the wide code's test hook); ORTK_EINVAL for b > q * V, q not in {1, b}, null pointers. */
 int ortk_beam_select(const float* logits, int64_t ld, const float* cum, const int32_t* prev, int32_t B, int32_t q, int32_t b,
                      int32_t V, int32_t fused, float scale, float* val, int32_t* parent, int32_t* token, ortk_stream stream);
+/* One GROUPED selection step (ortk_decode_opts.group_size > 1) through the device function of the diverse beam step: ortk_beam_select
+ * with a diversity penalty.  pen_tok (B, n_pen) int32: the tokens the image's earlier groups hold at this position (-1: no entry;
+ * a token listed c times counts c times; may be NULL when n_pen = 0).  value = cum[row] + (logp[row][v] - fl32(c * lambda)), logp as
+ * in ortk_beam_select (fused = 0 | 1): one fp32 multiply, one fp32 subtract, one fp32 add.  tok_lp (B, b): the UNAUGMENTED logp of
+ * every pick.  n_pen = 0 gives ortk_beam_select's val / parent / token byte for byte.  Deterministic: no atomics on the result path.
+ * ORTK_EINVAL: as ortk_beam_select, and n_pen < 0, n_pen > ORTK_MAX_BEAM - 1, lambda negative or not finite. */
+int ortk_beam_select_diverse(const float* logits, int64_t ld, const float* cum, const int32_t* prev, const int32_t* pen_tok, int32_t n_pen,
+                             float lambda, int32_t B, int32_t q, int32_t b, int32_t V, int32_t fused, float scale, float* val,
+                             int32_t* parent, int32_t* token, float* tok_lp, ortk_stream stream);
 /* Fused cross-entropy on logits (rows, ld): *loss_dev = -sum logp[target]*w/norm (LanguageModelCriterion / RewardCriterion,
  * utils/losses.py:15-43); dlogits (rows, ld_dl; fp32 or bf16; may alias logits when fp32 with ld_dl == ld) <- dLoss/dlogits,
  * zero in the pad columns.  The sum is DETERMINISTIC: every row's term goes to row_loss[row] and one workgroup adds them in a

@@ -113,7 +113,8 @@ class DecodeOpts(C.Structure):
     _fields_ = [("beam_size", C.c_int32), ("num_random_sample", C.c_int32), ("temperature", C.c_float),
                 ("decoding_constraint", C.c_int32), ("length_penalty", C.c_int32), ("length_alpha", C.c_double),
                 ("seed", C.c_uint64), ("sparse", C.POINTER(EllPlanStruct)), ("exec_flags", C.c_int32), ("with_greedy", C.c_int32), ("sample_row_offset", C.c_int64),
-                ("train", C.c_int32), ("drop_seed", C.c_uint64), ("memory", C.c_void_p), ("top_k", C.c_int32), ("top_p", C.c_float)]
+                ("train", C.c_int32), ("drop_seed", C.c_uint64), ("memory", C.c_void_p), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("group_size", C.c_int32), ("diversity_lambda", C.c_float)]
 
 
 class GemmArgs(C.Structure):
@@ -221,6 +222,7 @@ SIGNATURES = {
     "ortk_log_softmax": (_I32, [_P, _I64, _I32, _I64, _F, _P]),
     "ortk_sample_truncate": (_I32, [_P, _I64, _I32, _I64, _F, _I32, _F, _P, _I32, _P, _P, _P, _P, _P]),
     "ortk_beam_select": (_I32, [_P, _I64, _P, _P, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P]),
+    "ortk_beam_select_diverse": (_I32, [_P, _I64, _P, _P, _P, _I32, _F, _I32, _I32, _I32, _I32, _I32, _F, _P, _P, _P, _P, _P]),
     "ortk_xent_scratch_floats": (_I64, [_I64]),
     "ortk_xent_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _P]),
     "ortk_xent_smooth_fwd_bwd": (_I32, [_P, _P, _I64, _I32, _P, _P, _P, _P, _I64, _I32, _I64, _P, _I32, _I64, _F, _P]),
@@ -256,7 +258,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 11     # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 12     # include/ortk.h: ORTK_VERSION
 
 
 def lib():

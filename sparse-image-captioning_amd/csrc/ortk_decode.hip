@@ -476,6 +476,44 @@ struct WideLds {
     int cnt;
 };
 
+// Diversity penalty of a grouped (diverse) beam step: the tokens the image's earlier groups hold at this position, each with
+// pen = fl32(count * lambda) (every copy of a repeated token carries the full count: a lookup takes the first match).  bits: a
+// filter of PEN_BITS bits over token & (PEN_BITS - 1) — exact for vocabularies of up to 65 536 tokens — so that the common candidate
+// pays one bit test and only a hit walks the list (a wave walks whenever one of its lanes does: at 2 048 bits and 24 entries that was
+// every second iteration, profiles/diverse_beam.txt).
+constexpr int PEN_BITS = 65536, PEN_WORDS = PEN_BITS / 32;
+struct PenLds {
+    int tok[ORTK_MAX_BEAM];
+    float pen[ORTK_MAX_BEAM];
+    unsigned bits[PEN_WORDS];
+    int n;
+};
+// raw: this thread's list entry (threads 0 .. n_pen - 1; -1 = no entry), n_pen <= ORTK_MAX_BEAM - 1; ends with a barrier
+__device__ __forceinline__ void pen_build(PenLds& Pn, int raw, int n_pen, float lambda) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < PEN_WORDS; i += 256) Pn.bits[i] = 0u;
+    if (tid < ORTK_MAX_BEAM) Pn.tok[tid] = tid < n_pen ? raw : -1;
+    if (tid == 0) Pn.n = n_pen;
+    __syncthreads();
+    if (tid < n_pen && raw >= 0) {
+        int cnt = 0;
+        for (int j = 0; j < n_pen; ++j) cnt += Pn.tok[j] == raw ? 1 : 0;
+        Pn.pen[tid] = __fmul_rn((float)cnt, lambda);
+        atomicOr(&Pn.bits[(raw >> 5) & (PEN_WORDS - 1)], 1u << (raw & 31));      // (a set: the order of the ORs does not reach the result)
+    }
+    __syncthreads();
+}
+// log-prob x of token v minus its penalty (one fp32 subtract; x itself for a token no earlier group holds)
+template <bool PEN> __device__ __forceinline__ float pen_sub(const PenLds* Pn, float x, int v) {
+    if constexpr (PEN) {
+        if (Pn->n > 0 && ((Pn->bits[(v >> 5) & (PEN_WORDS - 1)] >> (v & 31)) & 1u)) {
+            const int n = Pn->n;
+            for (int i = 0; i < n; ++i) if (Pn->tok[i] == v) return x - Pn->pen[i];
+        }
+    }
+    return x;
+}
+
 // block-wide best of (mv, mi) under ortk_better; winner r -> S.win_v[r], S.win_i[r]; `clear`: mp is the winner's list position
 __device__ __forceinline__ void wide_argbest(WideLds& S, float mv, int mi, int mp, int r, bool clear) {
     blk_argbest(mv, mi, mp, S.red_v, S.red_i, S.red_pos);
@@ -489,10 +527,12 @@ __device__ __forceinline__ void wide_argbest(WideLds& S, float mv, int mi, int m
 // The b best of the image's nq x V candidates, in rank order, into S.win_v / S.win_i (flat index q * V + v); S.row_mx / S.row_lse
 // hold the rows' soft-max statistics when FUSED.  lp0: the image's first logit row; cum (nq values, NULL: 0); prev (token of row
 // q at prev[q * prev_stride], NULL: none) is no candidate; gs: the image's first row of block statistics (STATS).
-template <bool FUSED, int NPT, bool FASTEXP, bool STATS>
+// PEN (grouped steps): every candidate's log-prob first loses the penalty of its token, pen_sub(Pn, ., v); the group maxima behind the
+// pruning threshold are maxima of the PENALISED values, so they stay admissible candidates and the threshold stays a lower bound.
+template <bool FUSED, int NPT, bool FASTEXP, bool STATS, bool PEN = false>
 __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __restrict__ lp0, int64_t ldv, int nq, int b, int V, float scale,
                                                  const float* __restrict__ cum, const int32_t* __restrict__ prev, int64_t prev_stride,
-                                                 const float* __restrict__ gs0, int nblk) {
+                                                 const float* __restrict__ gs0, int nblk, const PenLds* Pn = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 32) S.comb[0][tid] = -INFINITY;
     if (tid == 0) S.cnt = 0;
@@ -562,7 +602,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
             for (int u = 0; u < NPT; ++u) {
                 const int v = tid + 256 * u;
                 const bool ok = v < V && v != pv;
-                z[u] = ok ? cumq + (__fmaf_rn(z[u], scale, -mx) - lse) : -INFINITY;
+                z[u] = ok ? cumq + pen_sub<PEN>(Pn, __fmaf_rn(z[u], scale, -mx) - lse, v) : -INFINITY;
                 tm = fmaxf(tm, z[u]);
             }
         } else {
@@ -574,7 +614,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
                 for (int u = 0; u < 8; ++u) {
                     const int v = v0 + 256 * u;
                     if (v >= V || v == pv) continue;
-                    tm = fmaxf(tm, cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]));
+                    tm = fmaxf(tm, cumq + pen_sub<PEN>(Pn, FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u], v));
                 }
             }
         }
@@ -607,7 +647,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
                 for (int u = 0; u < 8; ++u) {
                     const int v = v0 + 256 * u;
                     if (v >= V || v == pv) continue;
-                    const float zz = cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]);
+                    const float zz = cumq + pen_sub<PEN>(Pn, FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u], v);
                     if (zz >= tau) {
                         const int pos = atomicAdd(&S.cnt, 1);
                         if (pos < WCAP) { S.cv[pos] = zz; S.ci[pos] = q * V + v; }
@@ -646,7 +686,7 @@ __device__ __forceinline__ void beam_select_wide(WideLds& S, const float* __rest
                 for (int u = 0; u < 8; ++u) {
                     const int v = v0 + 256 * u;
                     if (v >= V || v == pv) continue;
-                    const float zz = cumq + (FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u]);
+                    const float zz = cumq + pen_sub<PEN>(Pn, FUSED ? __fmaf_rn(x[u], scale, -mx) - lse : x[u], v);
                     const int ix = q * V + v;
                     if (ortk_better(lv, li, zz, ix) && ortk_better(zz, ix, mv, mi)) { mv = zz; mi = ix; }
                 }
@@ -684,6 +724,64 @@ __global__ __launch_bounds__(256) void beam_select_kernel(const float* __restric
         const int ix = S.win_i[threadIdx.x];
         const int64_t o = (int64_t)blockIdx.x * b + threadIdx.x;
         val[o] = S.win_v[threadIdx.x]; parent[o] = ix / V; token[o] = ix - (ix / V) * V;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ grouped (diverse) beam step
+// One local step t of ONE group of a diverse beam search (CaptionModel.batch_beam_search with group_size > 1, caption_model.py:33-52,
+// 151-218): beam_step_wide_kernel's contract on the group's own BeamState (width b = beams per group), with every candidate's log-prob
+// lowered by lambda x the number of beams of the image's EARLIER groups that hold the candidate's token at column t of their
+// histories as they stand now.  Group p < g has then done min(t + g - p, L - 1) + 1 local steps (the schedule is staggered), so its
+// current history is the ping-pong buffer of that parity.  The token log-prob stored by beam_commit is the unaugmented one; cum is
+// the augmented sum.  g = 0: no penalty, the wide step's results bit for bit.
+struct PenSrc {
+    const int32_t* seq[2];    // group 0's ping-pong histories (BeamState.seq of group 0); group p's lie gstride elements further each
+    int64_t gstride;
+    int32_t g;                // index of this group = number of earlier groups; g * b <= ORTK_MAX_BEAM - 1
+};
+template <int NPT, bool FASTEXP = false, bool STATS = false>
+__global__ __launch_bounds__(256) void beam_step_diverse_kernel(BeamState st, const float* __restrict__ logp, int t, float scale, PenSrc ps,
+                                                                float lambda) {
+    __shared__ WideLds S;
+    __shared__ PenLds Pn;
+    __shared__ int end_slot[WMAXB];
+    const int b = st.b, L = st.L, tid = threadIdx.x;
+    const int nq = t == 0 ? 1 : b;
+    const int cur = t & 1;
+    const int64_t row0 = (int64_t)blockIdx.x * b;
+    const int64_t srow0 = t == 0 ? (int64_t)blockIdx.x : row0;
+    const int n_pen = ps.g * b;
+    int raw = -1;
+    if (tid < n_pen) {
+        const int p = tid / b, q = tid - p * b;
+        const int steps = min(t + ps.g - p, L - 1) + 1;              // local steps group p has done
+        raw = ((steps & 1) ? ps.seq[1] : ps.seq[0])[(int64_t)p * ps.gstride + (row0 + q) * L + t];
+    }
+    pen_build(Pn, raw, n_pen, lambda);
+    beam_select_wide<true, NPT, FASTEXP, STATS, true>(S, logp + srow0 * st.ldv, st.ldv, nq, b, st.V, scale, t == 0 ? nullptr : st.cum + row0,
+                                                      (st.decoding_constraint && t > 0) ? st.seq[cur] + row0 * L + t - 1 : nullptr, L,
+                                                      STATS ? st.gstats + srow0 * st.nblk * 2 : nullptr, st.nblk, &Pn);
+    beam_commit(st, logp, t, scale, S.win_v, S.win_i, S.row_mx, S.row_lse, end_slot);
+}
+
+// ortk_beam_select_diverse: the grouped selection alone, winners and their unaugmented log-probs to global memory
+template <bool FUSED, int NPT>
+__global__ __launch_bounds__(256) void beam_select_diverse_kernel(const float* __restrict__ logits, int64_t ld, const float* __restrict__ cum,
+                                                                  const int32_t* __restrict__ prev, const int32_t* __restrict__ pen_tok, int n_pen,
+                                                                  float lambda, int q, int b, int V, float scale, float* __restrict__ val,
+                                                                  int32_t* __restrict__ parent, int32_t* __restrict__ token, float* __restrict__ tok_lp) {
+    __shared__ WideLds S;
+    __shared__ PenLds Pn;
+    const int64_t row0 = (int64_t)blockIdx.x * q;
+    pen_build(Pn, (int)threadIdx.x < n_pen ? pen_tok[(int64_t)blockIdx.x * n_pen + threadIdx.x] : -1, n_pen, lambda);
+    beam_select_wide<FUSED, NPT, false, false, true>(S, logits + row0 * ld, ld, q, b, V, scale, cum + row0, prev ? prev + row0 : nullptr, 1, nullptr, 0, &Pn);
+    if ((int)threadIdx.x < b) {
+        const int ix = S.win_i[threadIdx.x];
+        const int pr = ix / V, tk = ix - pr * V;
+        const int64_t o = (int64_t)blockIdx.x * b + threadIdx.x;
+        const float x = logits[(row0 + pr) * ld + tk];
+        val[o] = S.win_v[threadIdx.x]; parent[o] = pr; token[o] = tk;
+        tok_lp[o] = FUSED ? __fmaf_rn(x, scale, -S.row_mx[pr]) - S.row_lse[pr] : x;
     }
 }
 
@@ -1089,6 +1187,22 @@ int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, 
     ORTK_CHECK_LAUNCH();
     return 0;
 }
+int beam_step_diverse(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale, bool fast_exp, const int32_t* const seq0[2],
+                      int64_t gstride, int32_t g, float lambda) {
+    if (st.b < 1 || st.b > ORTK_MAX_BEAM || g < 0 || (int64_t)g * st.b > ORTK_MAX_BEAM - 1 || !(lambda >= 0.f) || lambda == INFINITY) return ORTK_EINVAL;
+    if (st.B == 0) return 0;
+    PenSrc ps; ps.seq[0] = seq0[0]; ps.seq[1] = seq0[1]; ps.gstride = gstride; ps.g = g;
+    // the instance <NPT, FASTEXP, STATS> beam_step picks in the same mode
+    const bool stats = fast_exp && st.gstats && scale == 1.f && st.nblk <= 256 && st.nblk * 64 >= st.V, reg_rows = st.V <= 256 * 40;
+#define ORTK_BEAM_STEP(...) hipLaunchKernelGGL((beam_step_diverse_kernel<__VA_ARGS__>), dim3((unsigned)st.B), dim3(256), 0, s, st, logp, t, scale, ps, lambda)
+    if (stats) ORTK_BEAM_STEP(0, true, true);
+    else if (reg_rows && fast_exp) ORTK_BEAM_STEP(40, true);
+    else if (reg_rows) ORTK_BEAM_STEP(40);
+    else ORTK_BEAM_STEP(0);
+#undef ORTK_BEAM_STEP
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
 int beam_finalize(const BeamState& st, int64_t* seq_out, float* lp_out, float* score_out, hipStream_t s) {
     if (st.b < 1 || st.b > ORTK_MAX_BEAM || st.b * st.L > ORTK_MAX_BEAM * 64) return ORTK_EINVAL;
     if (st.B == 0) return 0;
@@ -1163,6 +1277,24 @@ extern "C" int ortk_beam_select(const float* logits, int64_t ld, const float* cu
     if (!fused) hipLaunchKernelGGL((ortk::beam_select_kernel<false, 0>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, 1.f, val, parent, token);
     else if (V <= 256 * 40) hipLaunchKernelGGL((ortk::beam_select_kernel<true, 40>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, scale, val, parent, token);
     else hipLaunchKernelGGL((ortk::beam_select_kernel<true, 0>), grid, dim3(256), 0, s, logits, ld, cum, prev, (int)q, (int)b, (int)V, scale, val, parent, token);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ortk_beam_select_diverse(const float* logits, int64_t ld, const float* cum, const int32_t* prev, const int32_t* pen_tok,
+                                        int32_t n_pen, float lambda, int32_t B, int32_t q, int32_t b, int32_t V, int32_t fused, float scale,
+                                        float* val, int32_t* parent, int32_t* token, float* tok_lp, ortk_stream stream) {
+    if (!logits || !cum || !val || !parent || !token || !tok_lp || B < 0 || V < 1 || ld < V) return ORTK_EINVAL;
+    if (b < 1 || b > ORTK_MAX_BEAM || (q != 1 && q != b) || (int64_t)b > (int64_t)q * V || (int64_t)q * V > 0x7FFFFFFF) return ORTK_EINVAL;
+    if (n_pen < 0 || n_pen > ORTK_MAX_BEAM - 1 || (n_pen > 0 && !pen_tok) || !(lambda >= 0.f) || lambda == INFINITY) return ORTK_EINVAL;
+    if (B == 0) return 0;
+    hipStream_t s = ortk_s(stream);
+    const dim3 grid((unsigned)B);
+#define ORTK_SELECT_DIVERSE(F, N, sc) hipLaunchKernelGGL((ortk::beam_select_diverse_kernel<F, N>), grid, dim3(256), 0, s, logits, ld, cum, prev, pen_tok, (int)n_pen, lambda, (int)q, (int)b, (int)V, sc, val, parent, token, tok_lp)
+    if (!fused) ORTK_SELECT_DIVERSE(false, 0, 1.f);
+    else if (V <= 256 * 40) ORTK_SELECT_DIVERSE(true, 40, scale);
+    else ORTK_SELECT_DIVERSE(true, 0, scale);
+#undef ORTK_SELECT_DIVERSE
     ORTK_CHECK_LAUNCH();
     return 0;
 }

@@ -69,6 +69,11 @@ struct BeamState {
 // `logp` holds raw logits: the log-soft-max of (logits * scale) is taken inside the step
 // wide = true: the wide step (beam_step_wide_kernel) at any width; widths above 8 always run it
 int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale = 1.f, bool fast_exp = false, bool wide = false);
+// One local step t of group g of a diverse beam search (ortk_decode_opts.group_size > 1): `st` is the GROUP's state (b = beams per
+// group); seq0: BeamState.seq of group 0, the histories of group p lie p * gstride elements further.  Every candidate's log-prob
+// first loses lambda x (beams of groups 0 .. g-1 of the image that hold its token at column t now); g = 0: the wide step.
+int beam_step_diverse(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale, bool fast_exp, const int32_t* const seq0[2],
+                      int64_t gstride, int32_t g, float lambda);
 int beam_finalize(const BeamState& st, int64_t* seq_out, float* lp_out, float* score_out, hipStream_t s);
 
 struct SampleState {

@@ -1725,6 +1725,7 @@ struct DecodeWS {
     void* chain_pk = nullptr;          // encoder chains' weight units in streaming order (chain_layout; mixed precision)
     int32_t* status = nullptr;         // [64] decode status word (ortk_decode_status): ALWAYS the first bytes of the workspace
     void* ckv_g = nullptr;             // train-mode decode with greedy rows: projection of the EVAL-mode encoder memory
+    int64_t* fin_seq = nullptr; float *fin_lp = nullptr, *fin_score = nullptr;      // diverse beam groups: one group's finalised rows (B * K each)
     size_t bytes;
 };
 
@@ -1753,8 +1754,10 @@ static int split_degree(bool dense_stack, int32_t flags, int64_t rows) {
     if (flags & ORTK_DEC_STACK_SPLIT) return G;                                   // whenever its groups fit the chip
     return ((flags & ORTK_DEC_SPLIT_SMALL) && !(flags & ORTK_DEC_STACK) && G >= 4) ? G : 0;     // the small decodes only (8 or 4 per group)
 }
+// groups > 1 (diverse beam search): K is the width of ONE group; every per-row buffer holds `groups` blocks of B * K rows (beam
+// state, self-attention caches and tokens per group; the activation buffers are shared, a group's pass uses their first B * K rows)
 static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, void* base, DecodeWS& w, bool stack = false, bool sstream = false,
-                         bool train = false, int tp = 0, bool greedy_rows = false, bool fp8 = false) {
+                         bool train = false, int tp = 0, bool greedy_rows = false, bool fp8 = false, int groups = 1) {
     const int64_t d = c.d_model, ff = c.d_ff, H = c.n_heads, L = c.n_layers, T = c.seq_len;
     // bf16 K / V storage: only when both decode attention kernels that understand it will be the ones dispatched
     w.kvdt = (c.precision && H == 8 && d == 512 && S > 8 && S <= 48 && T <= 32 && K <= 16) ? ORTK_BF16 : ORTK_F32;
@@ -1765,7 +1768,7 @@ static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, v
     if (stack) { w.kvdt = w.ckvdt = ORTK_BF16; w.xq16 = 0; }      // the stack kernel reads bf16 caches at every S
     if (train && !stack) { w.kvdt = w.ckvdt = ORTK_F32; w.xq16 = 0; }       // train-mode sampling, unfused: the generic attention kernel (fp32 rows)
     const size_t kves = ortk_esize(w.kvdt);
-    const int64_t Me = (int64_t)B * S, rows = (int64_t)B * K;
+    const int64_t Me = (int64_t)B * S, rows = (int64_t)B * K * groups;
     w.ldv = ortk_align(c.vocab, 128);
     w.adt = c.precision ? ORTK_BF16 : ORTK_F32;
     const size_t es = ortk_esize(w.adt);
@@ -1811,7 +1814,8 @@ static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, v
         for (int i = 0; i < 2; ++i) { w.bseq[i] = b.take<int32_t>(rows * T); w.blp[i] = b.take<float>(rows * T); w.kvidx[i] = b.take<int32_t>(rows * (T + 1)); }
         w.cum = b.take<float>(rows);
         w.done_seq = b.take<int32_t>(rows * T * T); w.done_lp = b.take<float>(rows * T * T);
-        w.done_p = b.take<double>(rows * T); w.done_len = b.take<int32_t>(rows * T); w.done_cnt = b.take<int32_t>(B);
+        w.done_p = b.take<double>(rows * T); w.done_len = b.take<int32_t>(rows * T); w.done_cnt = b.take<int32_t>((int64_t)B * groups);
+        if (groups > 1) { w.fin_seq = b.take<int64_t>((int64_t)B * K * T); w.fin_lp = b.take<float>((int64_t)B * K * T); w.fin_score = b.take<float>((int64_t)B * K); }
     } else {
         w.unfinished = b.take<int32_t>(rows); w.last_step = b.take<int32_t>(4);
     }
@@ -1848,9 +1852,24 @@ static int decode_K(const ortk_decode_opts* o) {
 // workgroups per group (its dropout sites, ortk_decstack.hip) or on the unfused executor; eval-mode (greedy) rows beside them
 // (`with_greedy`) only on the former.  ok = false: the option combination is not served (ORTK_EINVAL).
 struct DecodePlan { bool ok, stack, sstream; int split; bool gather = false; bool fp8 = false; };
+// diverse beam groups (ortk_decode_opts.group_size): the number of groups G (1: the plain decode), or -1 for a refused combination
+static int decode_groups(const ortk_decode_opts* o) {
+    if (o->group_size < 0) return -1;
+    if (o->group_size <= 1) return 1;                   // (diversity_lambda is not read)
+    const int G = o->group_size, b = o->beam_size;
+    if (o->num_random_sample > 0 || o->train || b < G || b > ORTK_MAX_BEAM || b % G != 0) return -1;
+    if (!(o->diversity_lambda >= 0.f) || std::isinf(o->diversity_lambda)) return -1;
+    return G;
+}
 static DecodePlan plan_decode(const ortk_config& cfg, int B, int K, const ortk_decode_opts* o) {
     DecodePlan p{true, false, false, 0};
     const int64_t rows = (int64_t)B * K;
+    if (o->group_size > 1) {
+        // every group's decoder pass is a launch sequence of the unfused executor at its own position; an executor of the stack
+        // family that the caller named is refused, not replaced (ORTK_DEC_SPLIT_SMALL alone is still the automatic choice)
+        p.ok = !(o->exec_flags & (ORTK_DEC_STACK | ORTK_DEC_SPARSE_STREAM | ORTK_DEC_STACK_RB20 | ORTK_DEC_STACK_SPLIT | ORTK_DEC_SPARSE_GATHER | ORTK_DEC_STACK_FP8));
+        return p;
+    }
     if (o->exec_flags & ORTK_DEC_STACK_FP8) {
         // the fp8 weight stream (ortk.h): the plain dense stack kernel wherever ORTK_DEC_STACK is served, and nothing else — no
         // other executor stands in for it
@@ -1876,10 +1895,12 @@ extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B,
     const int K = decode_K(o);
     if (K < 1 || decode_trunc(cfg, o) < 0) return 0;
     if (o->num_random_sample <= 0 && o->beam_size > 1 && (K > ORTK_MAX_BEAM || K > cfg->vocab)) return 0;      // (ortk_decode: ORTK_EINVAL)
+    const int G = decode_groups(o);
+    if (G < 1) return 0;
     const DecodePlan pl = plan_decode(*cfg, B, K, o);
     if (!pl.ok) return 0;
-    DecodeWS w; carve_decode(*cfg, B, S, K, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
-                             pl.split, o->with_greedy != 0, pl.fp8);
+    DecodeWS w; carve_decode(*cfg, B, S, K / G, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
+                             pl.split, o->with_greedy != 0, pl.fp8, G);
     return w.bytes;
 }
 
@@ -2020,6 +2041,67 @@ static int decoder_stack_step(const Ctx& c, const Offsets& o, const StepBufs& w,
     return gen_gemm(c, o, w, ORTK_BF16, rows);
 }
 
+// Diverse beam search (ortk_decode_opts.group_size = G > 1; CaptionModel.batch_beam_search, caption_model.py:33-52, 151-218): G beam
+// searches of width bd per image, each with its own block of B * bd decoder rows, BeamState and self-attention caches, over ONE
+// encoder memory and ONE cross-attention K/V projection (done by the caller).  The schedule is the reference's and stays staggered:
+// at global step T = 0 .. L + G - 2, group g = 0 .. G - 1 in this order does its local step t = T - g — a decoder pass of its own at
+// position t, then the grouped selection step, which counts the tokens the earlier groups hold at column t NOW (they are t + g - p
+// steps ahead and have re-ordered their histories since).  The BOS pass is repeated per group: same inputs, same launches, same bits.
+static int decode_diverse(const Ctx& c, const Offsets& o, const DecodeWS& w, const ortk_decode_opts* op, const float* att_masks, int B, int S,
+                          int bd, int G, int64_t* seq_out, float* logprob_out, float* score_out) {
+    const ortk_config* cfg = c.cfg;
+    hipStream_t s = c.s;
+    const int d = cfg->d_model, L = cfg->n_layers, V = cfg->vocab, T = cfg->seq_len, A = w.adt;
+    const int64_t grows = (int64_t)B * bd;                // rows of one group
+    const size_t kves = ortk_esize(w.kvdt);
+    BeamState bs[ORTK_MAX_BEAM];
+    for (int g = 0; g < G; ++g) {
+        BeamState& st = bs[g]; std::memset(&st, 0, sizeof(st));
+        st.B = B; st.b = bd; st.L = T; st.V = V; st.eos = cfg->eos_id; st.ldv = w.ldv;
+        for (int i = 0; i < 2; ++i) { st.seq[i] = w.bseq[i] + g * grows * T; st.tok_lp[i] = w.blp[i] + g * grows * T; st.kvidx[i] = w.kvidx[i] + g * grows * (T + 1); }
+        st.cum = w.cum + g * grows; st.it = w.it + g * grows;
+        st.done_seq = w.done_seq + g * grows * T * T; st.done_lp = w.done_lp + g * grows * T * T;
+        st.done_p = w.done_p + g * grows * T; st.done_len = w.done_len + g * grows * T; st.done_cnt = w.done_cnt + (int64_t)g * B;
+        st.decoding_constraint = op->decoding_constraint; st.length_penalty = op->length_penalty; st.length_alpha = op->length_alpha; st.tmax = T;
+        if (w.gstats && op->temperature == 1.f && !op->sparse && A == ORTK_BF16 && d % 64 == 0 && w.ldv % 128 == 0 && w.ldv / 64 <= 256) {
+            st.gstats = w.gstats; st.nblk = (int32_t)(w.ldv / 64);      // (the plain beam search's condition: group 0 equals it bit for bit)
+        }
+        TRY(fill_i64(st.it, B, cfg->bos_id, s));
+        TRY(kvidx_init(st.kvidx[0], B, bd, T, s));
+    }
+    TRY(fill_i32(w.done_cnt, (int64_t)B * G, 0, s));
+    const int32_t* const seq0[2] = {w.bseq[0], w.bseq[1]};
+    const bool fast_exp = cfg->precision == 1;
+    for (int Tg = 0; Tg < T + G - 1; ++Tg)
+        for (int g = 0; g < G; ++g) {
+            const int t = Tg - g;
+            if (t < 0 || t > T - 1) continue;
+            const bool first = t == 0;                     // one row per image (transformer.py:488), then bd per image
+            const int64_t rows = first ? B : grows;
+            StepBufs sb{bs[g].it, w.xa, w.xb, w.y, w.qkv, w.o, w.q, w.h, w.logits, w.st, w.ldv, w.ckv, att_masks};
+            sb.kvdt = w.kvdt; sb.ckvdt = w.ckvdt; sb.xq16 = w.xq16;
+            if (bs[g].gstats) { sb.gstats = w.gstats; sb.stat_ncols = V; }
+            for (int l = 0; l < L; ++l) {
+                sb.cache_k[l] = reinterpret_cast<char*>(w.cache_k[l]) + (size_t)(g * grows * T * d) * kves;
+                sb.cache_v[l] = reinterpret_cast<char*>(w.cache_v[l]) + (size_t)(g * grows * T * d) * kves;
+            }
+            TRY(decoder_step(c, o, sb, rows, B, first ? 1 : bd, first ? bd : 1, S, T, t, bs[g].kvidx[t & 1]));
+            TRY(beam_step_diverse(bs[g], w.logits, t, s, t > 0 ? 1.f / op->temperature : 1.f, fast_exp, seq0, grows * T, g, op->diversity_lambda));
+        }
+    // seq_out[n, g * bd + q]: each group's stable top-bd of its finished list, copied into its columns of the image's b rows
+    const size_t b_all = (size_t)bd * G;
+    for (int g = 0; g < G; ++g) {
+        TRY(beam_finalize(bs[g], w.fin_seq, w.fin_lp, score_out ? w.fin_score : nullptr, s));
+        if (hipMemcpy2DAsync(seq_out + (size_t)g * bd * T, b_all * T * sizeof(int64_t), w.fin_seq, (size_t)bd * T * sizeof(int64_t),
+                             (size_t)bd * T * sizeof(int64_t), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+        if (hipMemcpy2DAsync(logprob_out + (size_t)g * bd * T, b_all * T * sizeof(float), w.fin_lp, (size_t)bd * T * sizeof(float),
+                             (size_t)bd * T * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+        if (score_out && hipMemcpy2DAsync(score_out + (size_t)g * bd, b_all * sizeof(float), w.fin_score, (size_t)bd * sizeof(float),
+                                          (size_t)bd * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+    }
+    return 0;
+}
+
 extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
                            const float* att_masks, int32_t B, int32_t S, const ortk_decode_opts* op, void* ws, size_t ws_bytes,
                            int64_t* seq_out, float* logprob_out, float* score_out, ortk_stream stream) {
@@ -2036,6 +2118,8 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const bool beam = op->num_random_sample <= 0 && op->beam_size > 1;
     if (beam && (K > ORTK_MAX_BEAM || K > cfg->vocab)) return ORTK_EINVAL;
     if (op->temperature <= 0.f) return ORTK_EINVAL;
+    const int G = decode_groups(op);
+    if (G < 1) return ORTK_EINVAL;
     Offsets o; build_layout(*cfg, o, nullptr);
     // train-mode sampling (dropout on while the captions are drawn): multinomial rollouts only; with the greedy baseline as eval-mode
     // rows of the same launches when the column-split stack kernel serves the call (plan_decode)
@@ -2045,7 +2129,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const int split = pl.split;
     const bool greedy_rows = op->train && op->with_greedy;         // (=> stack)
     if (greedy_rows && (!att_feats || (!boxes && !cfg->no_box))) return ORTK_EINVAL;      // their eval-mode encoder pass runs here
-    DecodeWS w; carve_decode(*cfg, B, S, K, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows, pl.fp8);
+    DecodeWS w; carve_decode(*cfg, B, S, K / G, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows, pl.fp8, G);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
     hipStream_t s = ortk_s(stream);
     TRY(fill_i32(w.status, 64, 0, s));
@@ -2121,6 +2205,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     c.use_side = false;
     TRY(fwd_gemm(c, op->memory ? op->memory : w.mem, A, d, o.ckv_w, P + o.ckv_b, w.ckv, w.ckvdt, o.ckv_slots * o.cw, Me, (int)(o.ckv_slots * o.cw), d));
 
+    if (G > 1) return decode_diverse(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out);
     const int64_t rows_full = (int64_t)B * K;
     BeamState bs; std::memset(&bs, 0, sizeof(bs));
     SampleState ss; std::memset(&ss, 0, sizeof(ss));

@@ -572,10 +572,24 @@ class RelationTransformerModel(CaptionModelBase):
         o.decoding_constraint = int(opt.get("decoding_constraint", 0))
         o.length_penalty, o.length_alpha = self._parse_length_penalty(opt.get("length_penalty", ""))
         o.seed = int(opt.get("seed", self._next_seed())) & 0xFFFFFFFF
-        for k in ("group_size",):
-            if int(opt.get(k, 1)) != 1:
-                raise NotImplementedError("diverse beam groups (group_size > 1): the reference's own path raises AttributeError "
-                                          "(caption_model.py:50 calls an undefined self.repeat_tensor); nothing to match")
+        # diverse beam groups (CaptionModel.batch_beam_search, caption_model.py:117-123; ortk_decode_opts.group_size): the reference's
+        # defaults; group_size 1 is the plain decode whatever diversity_lambda is
+        o.group_size = int(opt.get("group_size", 1))
+        o.diversity_lambda = float(opt.get("diversity_lambda", 0.5))
+        if o.group_size < 1:
+            raise ValueError(f"group_size={o.group_size}: expected an integer >= 1")
+        if o.group_size > 1:
+            if o.num_random_sample > 0 or opt.get("train_mode", False):
+                raise ValueError(f"group_size={o.group_size}: diverse groups belong to beam decodes (num_random_sample <= 0, no train_mode)")
+            if o.beam_size > L.MAX_BEAM:
+                raise ValueError(f"beam_size={o.beam_size}: the beam search serves at most ORTK_MAX_BEAM = {L.MAX_BEAM} beams "
+                                 "(include/ortk.h)")
+            if o.group_size > o.beam_size:
+                raise ValueError(f"group_size={o.group_size} exceeds beam_size={o.beam_size}: every group needs at least one beam")
+            if o.beam_size % o.group_size:
+                raise ValueError(f"beam_size={o.beam_size} is not a multiple of group_size={o.group_size}: the groups share the beams evenly")
+            if not (o.diversity_lambda >= 0.0 and o.diversity_lambda != float("inf")):
+                raise ValueError(f"diversity_lambda={opt.get('diversity_lambda')!r}: expected a finite number >= 0")
         o.with_greedy = 1 if (o.num_random_sample > 0 and opt.get("with_greedy", False)) else 0
         # train-mode sampling (ortk_decode_opts.train): dropout on while the captions are drawn, keyed like the teacher-forced
         # pass of seed opt["drop_seed"]; default: follows model.training only when asked (opt["train_mode"])
@@ -606,7 +620,13 @@ class RelationTransformerModel(CaptionModelBase):
         # "stack_fp8" (the stack kernel on FP8-quantised decoder weights, fp8_dequantized_decoder_state) is opt-in only: never "auto"
         # ORTK_DEC_STACK=0 / 2 in the environment (read here, on the host side, per call) = "unfused" / "stack"
         ex = opt.get("executor", {"0": "unfused", "2": "stack", "3": "stack_split"}.get(os.environ.get("ORTK_DEC_STACK", ""), "auto"))
-        if ex == "auto" and getattr(self, "_sparse_stream", False):
+        if o.group_size > 1:
+            # every group's decoder pass is a launch sequence of the unfused executor at the group's own position: "auto" resolves
+            # to it, a stack-family executor the caller named is refused
+            if ex not in ("auto", "unfused"):
+                raise ValueError(f'executor="{ex}" does not serve group_size={o.group_size}: diverse beam groups decode at different '
+                                 'positions, the stack kernels take one position per launch; use "auto" or "unfused"')
+        elif ex == "auto" and getattr(self, "_sparse_stream", False):
             ex = "sparse_gather" if getattr(self, "_sparse_gather", False) else "sparse_stream"
         # "auto" lets decodes of <= 2 048 rows take the column-split stack kernel (fastest there) UNLESS another decode may run on
         # this GPU at the same time: its workgroups spin on each other and must all be resident (ortk.h: ORTK_DEC_SPLIT_SMALL).
@@ -687,6 +707,11 @@ class RelationTransformerModel(CaptionModelBase):
         greedy baseline as eval-mode rows of the same launches: the column-split stack kernel only).  No device work."""
         if int(opt.get("num_random_sample", 0)) <= 0 and int(opt.get("beam_size", 1)) > L.MAX_BEAM:
             return False                                                     # (the decode itself raises ValueError: _decode_opts)
+        if int(opt.get("group_size", 1)) != 1:
+            try:                                                             # (likewise: a refused group option or executor)
+                self._decode_opts(dict(opt, seed=opt.get("seed", 0)))
+            except ValueError:
+                return False
         o, _, ex = self._decode_opts(dict(opt, seed=opt.get("seed", 0)))      # (a probe draws no seed)
         if getattr(self, "_plans", None) is not None and self._plans[0] is not None and not ex.startswith("sparse_") and not o.train:
             o.sparse = self._plans[0].ref()
