@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 12     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 13     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -846,6 +846,40 @@ int ortk_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, floa
  * own pass over the arena: the next step's weight-gradient GEMMs accumulate into zeros). */
 int ortk_adam_clip_zero(float* p, float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                         float eps, float clip, float bc1, float bc2, ortk_stream stream);
+
+/* The reference's optimiser family (utils/optim.py:146-174: torch.optim.Adam / SGD / RMSprop / Adagrad, single-tensor rules) behind
+ * clip_grad_value_, as ONE launch over a range of the arena.  Per element, each line one fp32 operation sequence in this order:
+ *   gc = min(max(g, -clip), clip);   if (weight_decay != 0) gc = gc + weight_decay * p;
+ *   ORTK_OPT_ADAM     s1 = exp_avg, s2 = exp_avg_sq: the arithmetic of ortk_adam_clip on gc, alpha / beta = beta1 / beta2,
+ *                     bc1 / bc2 = 1 - beta^t from the host in double precision
+ *   ORTK_OPT_SGD      p -= lr * gc                                                        (no state: s1, s2 are never touched)
+ *   ORTK_OPT_SGDM     s1 = first_step ? gc : alpha * s1 + gc;   p -= lr * s1              (momentum alpha, dampening 0)
+ *   ORTK_OPT_SGDMOM   the same s1;                              p -= lr * (gc + alpha * s1)                     (Nesterov)
+ *   ORTK_OPT_RMSPROP  s1 = alpha * s1 + (1 - alpha) * gc * gc;  p -= lr * gc / (sqrt(s1) + eps)   (not centred, no momentum)
+ *   ORTK_OPT_ADAGRAD  s1 = s1 + gc * gc;                        p -= lr * gc / (sqrt(s1) + eps)          (lr_decay 0)
+ * The clip + decay line and the five non-Adam rules are evaluated without FMA contraction (one rounding per operation: gc can
+ * cancel, and a rule that divides by a root of gc^2 magnifies its last bit); the Adam rule is compiled as ortk_adam_clip's is.
+ * first_step (momentum kinds): the buffer is written without being read.  zero_grad != 0: g is cleared on the way (as
+ * ortk_adam_clip_zero).  Every instance moves only the arrays its kind needs; no atomics, so a rerun gives the same bytes.
+ * ORTK_EINVAL before any launch: NULL args / p / g or a NULL state array the kind needs, n < 0, an unknown kind, a pointer that is
+ * not 16-byte aligned, clip not > 0 (+inf: no clipping), lr / weight_decay / alpha / beta / eps not finite, bc1 <= 0 or bc2 <= 0 for
+ * ORTK_OPT_ADAM.  n == 0 returns 0 and touches nothing. */
+#define ORTK_OPT_ADAM 0
+#define ORTK_OPT_SGD 1
+#define ORTK_OPT_SGDM 2
+#define ORTK_OPT_SGDMOM 3
+#define ORTK_OPT_RMSPROP 4
+#define ORTK_OPT_ADAGRAD 5
+typedef struct ortk_optim_args {
+    float *p, *g;                         /* parameters and their gradient, n elements each */
+    float *s1, *s2;                       /* state arrays: ortk_optim_states(kind) of them are used, the rest may be NULL */
+    int64_t n;
+    int32_t kind, first_step, zero_grad;
+    float lr, weight_decay, alpha, beta, eps, clip, bc1, bc2;
+} ortk_optim_args;
+/* number of state arrays `kind` reads and writes (0, 1 or 2); -1 for an unknown kind */
+int ortk_optim_states(int32_t kind);
+int ortk_optim_step(const ortk_optim_args* a, ortk_stream stream);
 
 /* MaskMixin.get_masked_weight over the whole arena (pruning/masked_layer.py:84-110, pruning/sampler.py):
  *   mode 0: s = round(sigmoid(m))  (supermask, eval)      mode 1: s = bernoulli(sigmoid(m)) (supermask, train)

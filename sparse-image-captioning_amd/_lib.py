@@ -99,6 +99,17 @@ class MaskedAdamArgs(C.Structure):
                 ("beta1", C.c_float), ("beta2", C.c_float), ("clip", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float)]
 
 
+OPT_ADAM, OPT_SGD, OPT_SGDM, OPT_SGDMOM, OPT_RMSPROP, OPT_ADAGRAD = range(6)      # include/ortk.h: ORTK_OPT_*
+OPT_KINDS = {"adam": OPT_ADAM, "sgd": OPT_SGD, "sgdm": OPT_SGDM, "sgdmom": OPT_SGDMOM, "rmsprop": OPT_RMSPROP, "adagrad": OPT_ADAGRAD}
+
+
+class OptimArgs(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_int64),
+                ("kind", C.c_int32), ("first_step", C.c_int32), ("zero_grad", C.c_int32),
+                ("lr", C.c_float), ("weight_decay", C.c_float), ("alpha", C.c_float), ("beta", C.c_float), ("eps", C.c_float),
+                ("clip", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float)]
+
+
 class Tuning(C.Structure):
     _fields_ = [("gemm_t64", C.c_int32), ("attn_impl", C.c_int32), ("attn16_min_lq", C.c_int32),
                 ("side_stream", C.c_int32), ("row_chain", C.c_int32), ("chain_wide", C.c_int32), ("spmm_alias", C.c_int32), ("f32_split", C.c_int32), ("wgrad_wgs", C.c_int32),
@@ -239,6 +250,8 @@ SIGNATURES = {
     "ortk_sum": (_I32, [_P, _I64, _P, _P, _P]),
     "ortk_adam_clip": (_I32, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
     "ortk_adam_clip_zero": (_I32, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _F, _F, _P]),
+    "ortk_optim_states": (_I32, [_I32]),
+    "ortk_optim_step": (_I32, [C.POINTER(OptimArgs), _P]),
     "ortk_mask_apply": (_I32, [_P, _P, _P, _I64, _I32, _U32, _P]),
     "ortk_mask_bwd": (_I32, [_P, _P, _P, _P, _P, _I64, _I32, _U32, _P, _P]),
     "ortk_masked_adam_step": (_I32, [C.POINTER(MaskedAdamArgs), _P]),
@@ -258,7 +271,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 12     # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 13    # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -140,7 +140,122 @@ __global__ __launch_bounds__(256) void masked_adam_kernel(ortk_masked_adam_args 
 
 inline unsigned ew_grid(int64_t n) { return (unsigned)std::min<int64_t>(ortk_cdiv(n, 256), 4096); }
 
+// The optimiser family of ortk_optim_step (include/ortk.h): clip, optional weight decay, then the kind's rule on one element.
+// NS = state arrays of the kind; an instance loads and stores only those (plain SGD moves p and g).
+struct optim_consts {
+    float lr, wd, alpha, beta, eps, clip, step_size, sqrt_bc2;     // step_size = lr / bc1, sqrt_bc2: ORTK_OPT_ADAM only
+    int first;
+};
+template <int KIND> struct optim_kind { static constexpr int NS = KIND == ORTK_OPT_ADAM ? 2 : KIND == ORTK_OPT_SGD ? 0 : 1; };
+// Clip and decay with one rounding per operation (no contraction into an FMA): gc = clip(g) + wd * p can cancel, and the rules
+// that divide by a root of gc^2 (Adam with its small eps above all) turn a last-bit difference of a nearly cancelled gc into a
+// visible difference of the step.
+__device__ __forceinline__ float optim_clip_decay(float g, float p, const optim_consts& c) {
+#pragma clang fp contract(off)
+    float gc = fminf(fmaxf(g, -c.clip), c.clip);
+    if (c.wd != 0.f) gc = gc + c.wd * p;
+    return gc;
+}
+__device__ __forceinline__ void optim_adam1(float& p, float gc, float& s1, float& s2, const optim_consts& c) {
+    // adam_clip_kernel's statements, compiled as that kernel is, on the decayed gradient
+    s1 = s1 + (gc - s1) * (1.f - c.alpha);
+    s2 = s2 * c.beta + gc * gc * (1.f - c.beta);
+    const float denom = sqrtf(s2) / c.sqrt_bc2 + c.eps;
+    p = p - c.step_size * (s1 / denom);
+}
+template <int KIND>
+__device__ __forceinline__ void optim1(float& p, float g, float& s1, float& s2, const optim_consts& c) {
+#pragma clang fp contract(off)
+    const float gc = optim_clip_decay(g, p, c);
+    if (KIND == ORTK_OPT_ADAM) {
+        optim_adam1(p, gc, s1, s2, c);
+    } else if (KIND == ORTK_OPT_SGD) {
+        p = p - c.lr * gc;
+    } else if (KIND == ORTK_OPT_SGDM || KIND == ORTK_OPT_SGDMOM) {
+        s1 = c.first ? gc : c.alpha * s1 + gc;
+        p = p - c.lr * (KIND == ORTK_OPT_SGDM ? s1 : gc + c.alpha * s1);
+    } else if (KIND == ORTK_OPT_RMSPROP) {
+        s1 = c.alpha * s1 + (1.f - c.alpha) * gc * gc;
+        p = p - c.lr * (gc / (sqrtf(s1) + c.eps));
+    } else {                                                       // ORTK_OPT_ADAGRAD
+        s1 = s1 + gc * gc;
+        p = p - c.lr * (gc / (sqrtf(s1) + c.eps));
+    }
+}
+template <int KIND, bool ZERO>
+__global__ __launch_bounds__(256) void optim_step_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ s1,
+                                                         float* __restrict__ s2, int64_t n, optim_consts c) {
+    constexpr int NS = optim_kind<KIND>::NS;
+    // a momentum buffer is write-only on its first step
+    const bool load1 = NS >= 1 && !((KIND == ORTK_OPT_SGDM || KIND == ORTK_OPT_SGDMOM) && c.first);
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    const int64_t n4 = n >> 2;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+        float4 aa = make_float4(0.f, 0.f, 0.f, 0.f), bb = aa;
+        if (load1) aa = reinterpret_cast<float4*>(s1)[i];
+        if (NS >= 2) bb = reinterpret_cast<float4*>(s2)[i];
+        float* P = &pp.x; float* G = &gg.x; float* A = &aa.x; float* B = &bb.x;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) optim1<KIND>(P[u], G[u], A[u], B[u], c);
+        reinterpret_cast<float4*>(p)[i] = pp;
+        if (NS >= 1) reinterpret_cast<float4*>(s1)[i] = aa;
+        if (NS >= 2) reinterpret_cast<float4*>(s2)[i] = bb;
+        if (ZERO) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        float pi = p[i], a = load1 ? s1[i] : 0.f, b = NS >= 2 ? s2[i] : 0.f;
+        optim1<KIND>(pi, g[i], a, b, c);
+        p[i] = pi;
+        if (NS >= 1) s1[i] = a;
+        if (NS >= 2) s2[i] = b;
+        if (ZERO) g[i] = 0.f;
+    }
+}
+template <int KIND>
+void optim_launch(const ortk_optim_args& a, const optim_consts& c, ortk_stream stream) {
+    const dim3 grid(ew_grid(a.n / 4 + 1));
+    if (a.zero_grad) hipLaunchKernelGGL((optim_step_kernel<KIND, true>), grid, dim3(256), 0, ortk_s(stream), a.p, a.g, a.s1, a.s2, a.n, c);
+    else             hipLaunchKernelGGL((optim_step_kernel<KIND, false>), grid, dim3(256), 0, ortk_s(stream), a.p, a.g, a.s1, a.s2, a.n, c);
+}
+
 }  // namespace
+
+extern "C" int ortk_optim_states(int32_t kind) {
+    switch (kind) {
+        case ORTK_OPT_ADAM: return 2;
+        case ORTK_OPT_SGD: return 0;
+        case ORTK_OPT_SGDM: case ORTK_OPT_SGDMOM: case ORTK_OPT_RMSPROP: case ORTK_OPT_ADAGRAD: return 1;
+        default: return -1;
+    }
+}
+
+extern "C" int ortk_optim_step(const ortk_optim_args* a, ortk_stream stream) {
+    if (!a || !a->p || !a->g || a->n < 0) return ORTK_EINVAL;
+    const int ns = ortk_optim_states(a->kind);
+    if (ns < 0 || (ns >= 1 && !a->s1) || (ns >= 2 && !a->s2)) return ORTK_EINVAL;
+    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!(al(a->p) && al(a->g) && (ns < 1 || al(a->s1)) && (ns < 2 || al(a->s2)))) return ORTK_EINVAL;
+    if (!(a->clip > 0.f)) return ORTK_EINVAL;                      // (NaN included; +inf = no clipping)
+    if (!(std::isfinite(a->lr) && std::isfinite(a->weight_decay) && std::isfinite(a->alpha) && std::isfinite(a->beta) && std::isfinite(a->eps)))
+        return ORTK_EINVAL;
+    if (a->kind == ORTK_OPT_ADAM && !(a->bc1 > 0.f && a->bc2 > 0.f)) return ORTK_EINVAL;
+    if (a->n == 0) return 0;
+    optim_consts c{a->lr, a->weight_decay, a->alpha, a->beta, a->eps, a->clip, 0.f, 1.f, a->first_step != 0};
+    switch (a->kind) {
+        case ORTK_OPT_ADAM:
+            c.step_size = a->lr / a->bc1;
+            c.sqrt_bc2 = (float)sqrt((double)a->bc2);
+            optim_launch<ORTK_OPT_ADAM>(*a, c, stream); break;
+        case ORTK_OPT_SGD: optim_launch<ORTK_OPT_SGD>(*a, c, stream); break;
+        case ORTK_OPT_SGDM: optim_launch<ORTK_OPT_SGDM>(*a, c, stream); break;
+        case ORTK_OPT_SGDMOM: optim_launch<ORTK_OPT_SGDMOM>(*a, c, stream); break;
+        case ORTK_OPT_RMSPROP: optim_launch<ORTK_OPT_RMSPROP>(*a, c, stream); break;
+        default: optim_launch<ORTK_OPT_ADAGRAD>(*a, c, stream); break;
+    }
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int ortk_masked_adam_step(const ortk_masked_adam_args* a, ortk_stream stream) {
     if (!a || !a->w || !a->g || !a->mw || !a->vw || !a->ml || a->n < 0 || a->index0 < 0 || a->mode < 0 || a->mode > 2) return ORTK_EINVAL;

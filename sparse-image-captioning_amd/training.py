@@ -8,9 +8,13 @@ Everything between the batch and the updated parameters is HIP on flat arenas: `
 in the workspace), the fused criterion ``ortk_loss`` (``ortk_loss_smooth`` with label smoothing; log-probs are never materialised), ``ortk_backward`` into
 the flat gradient arena, ONE RCCL all-reduce of that arena when ``torch.distributed`` is initialised (one process
 per GPU, minibatch split by image; loss normalised by the GLOBAL mask sum), and ``ortk_adam_clip``.
+
+The update rule is Adam at the Noam rate by default; ``lr_scheduler`` / ``optim`` select the reference's other schedules (``step``,
+``cosine``) and optimisers (``sgd``, ``sgdm``, ``sgdmom``, ``rmsprop``, ``adagrad``, Adam with weight decay: ``ortk_optim_step``).
 """
 import ctypes as C
 import math
+import warnings
 
 import torch
 import torch.distributed as dist
@@ -25,10 +29,94 @@ def noam_rate(step, d_model, factor, warmup):
     return factor * (d_model ** (-0.5) * min(step ** (-0.5), step * warmup ** (-1.5)))
 
 
+ALL_SCHEDULERS = ("noam", "step", "cosine")                                       # utils/optim.py:113
+ALL_OPTIMIZERS = ("rmsprop", "adagrad", "sgd", "sgdm", "sgdmom", "adam")          # utils/optim.py:146
+# the reference's option names and defaults (utils/training.py:409-473)
+OPTIM_DEFAULTS = dict(optim="adam", lr_scheduler="noam", learning_rate=5e-4, learning_rate_min=1e-5, learning_rate_decay_start=0,
+                      learning_rate_decay_every=3, learning_rate_decay_rate=0.8, optim_alpha=0.9, optim_beta=0.999,
+                      optim_epsilon=1e-8, weight_decay=0.0)
+_noam_warned = False
+
+
+class OptimSpec:
+    """Host side of ``get_optim`` (utils/optim.py:116-174): which update rule runs, with which constants, at which rate.  Pure
+    Python (no device): the trainer builds one before it touches the GPU, so a bad option is a ValueError and nothing else.
+
+    ``noam`` ignores ``optim`` and ``weight_decay`` (one warning per process) and keeps Adam with ``betas`` / ``eps``; ``step`` and
+    ``cosine`` build ``optim``: adam takes betas (optim_alpha, optim_beta) and eps optim_epsilon, sgdm / sgdmom momentum optim_alpha,
+    rmsprop alpha optim_alpha and eps optim_epsilon, adagrad torch's eps 1e-10."""
+
+    def __init__(self, d_model, noamopt_factor=1.0, noamopt_warmup=20000, betas=(0.9, 0.98), eps=1e-9, max_train_step=1, **opts):
+        global _noam_warned
+        unknown = sorted(set(opts) - set(OPTIM_DEFAULTS))
+        if unknown:
+            raise ValueError(f"unknown optimiser option(s) {unknown}; known: {sorted(OPTIM_DEFAULTS)}")
+        o = dict(OPTIM_DEFAULTS, **opts)
+        self.scheduler, self.optim = str(o["lr_scheduler"]).lower(), str(o["optim"]).lower()
+        if self.scheduler not in ALL_SCHEDULERS:
+            raise ValueError(f"Bad option `lr_scheduler`: {o['lr_scheduler']} (one of {ALL_SCHEDULERS})")
+        if self.optim not in ALL_OPTIMIZERS:
+            raise ValueError(f"Bad option `optim`: {o['optim']} (one of {ALL_OPTIMIZERS})")
+        self.d_model, self.factor, self.warmup, self.max_train_step = d_model, noamopt_factor, noamopt_warmup, max_train_step
+        self.learning_rate, self.learning_rate_min = float(o["learning_rate"]), float(o["learning_rate_min"])
+        self.decay_start, self.decay_every = o["learning_rate_decay_start"], o["learning_rate_decay_every"]
+        self.decay_rate = o["learning_rate_decay_rate"]
+        if self.scheduler == "noam":
+            if self.optim != "adam" and not _noam_warned:
+                _noam_warned = True
+                warnings.warn(f"Noam scheduler should be used with ADAM. Ignoring optim choice: {o['optim']}")
+            self.kind, (self.alpha, self.beta), self.eps, self.weight_decay = "adam", betas, eps, 0.0
+        else:
+            if self.scheduler == "step" and self.decay_start >= 0 and not (self.decay_every > 0 and 0 < self.decay_rate < 1):
+                raise ValueError("step schedule: learning_rate_decay_every must be > 0 and 0 < learning_rate_decay_rate < 1, saw "
+                                 f"{self.decay_every}, {self.decay_rate}")
+            if self.scheduler == "cosine" and not max_train_step > 0:
+                raise ValueError(f"cosine schedule: max_train_step must be > 0, saw {max_train_step}")
+            self.kind = self.optim
+            self.alpha, self.beta = float(o["optim_alpha"]), float(o["optim_beta"])
+            self.eps = 1e-10 if self.kind == "adagrad" else float(o["optim_epsilon"])
+            self.weight_decay = float(o["weight_decay"])
+        for name in ("learning_rate", "learning_rate_min", "alpha", "beta", "eps", "weight_decay"):
+            if not math.isfinite(getattr(self, name)):
+                raise ValueError(f"{name} must be finite, saw {getattr(self, name)}")
+        self.n_states = {"adam": 2, "sgd": 0}.get(self.kind, 1)          # ortk_optim_states
+        # Adam without weight decay is the parent's kernel with the parent's arguments (ortk_adam_clip / ortk_masked_adam_step)
+        self.plain_adam = self.kind == "adam" and self.weight_decay == 0.0
+
+    def rate(self, step, epoch=0):
+        """utils/optim.py:46-49, 79-88, 105-110; `step` is the already incremented step count, `epoch` what the caller passed to
+        ``optimizer.step(epoch=...)``."""
+        if self.scheduler == "noam":
+            return noam_rate(max(step, 1), self.d_model, self.factor, self.warmup)
+        if self.scheduler == "step":
+            if epoch > self.decay_start >= 0:        # (decay_start = -1: a constant rate)
+                return self.learning_rate * self.decay_rate ** ((epoch - self.decay_start) // self.decay_every)
+            return self.learning_rate
+        s = 1.0 + math.cos(min(1.0, step / self.max_train_step) * math.pi)
+        return (self.learning_rate - self.learning_rate_min) * (s / 2) + self.learning_rate_min
+
+    @staticmethod
+    def options_from_config(config):
+        """The reference's optimiser names present in `config` (anything with ``.get``), for ``OptimSpec(**...)`` / the trainer."""
+        names = tuple(OPTIM_DEFAULTS) + ("noamopt_factor", "noamopt_warmup", "max_train_step")
+        return {k: config.get(k) for k in names if config.get(k) is not None}
+
+
 class NativeTrainer:
     def __init__(self, model, noamopt_factor=1.0, noamopt_warmup=20000, grad_clip=0.1, betas=(0.9, 0.98), eps=1e-9,
                  prune_supermask_lr=100.0, mask_eps=1e-2, sparsity_target=None, sparsity_weight=None, max_train_step=1,
-                 overlap_allreduce=None, keep_grads=False, allreduce_dtype=None, label_smoothing=0.0):
+                 overlap_allreduce=None, keep_grads=False, allreduce_dtype=None, label_smoothing=0.0,
+                 optim="adam", lr_scheduler="noam", learning_rate=5e-4, learning_rate_min=1e-5, learning_rate_decay_start=0,
+                 learning_rate_decay_every=3, learning_rate_decay_rate=0.8, optim_alpha=0.9, optim_beta=0.999, optim_epsilon=1e-8,
+                 weight_decay=0.0):
+        # the reference's get_optim (utils/optim.py:116-174), host side only: an unknown name raises before any device work
+        self.spec = OptimSpec(model.d_model, noamopt_factor, noamopt_warmup, betas, eps, max_train_step, optim=optim,
+                              lr_scheduler=lr_scheduler, learning_rate=learning_rate, learning_rate_min=learning_rate_min,
+                              learning_rate_decay_start=learning_rate_decay_start, learning_rate_decay_every=learning_rate_decay_every,
+                              learning_rate_decay_rate=learning_rate_decay_rate, optim_alpha=optim_alpha, optim_beta=optim_beta,
+                              optim_epsilon=optim_epsilon, weight_decay=weight_decay)
+        betas, eps = (self.spec.alpha, self.spec.beta), self.spec.eps
+        self.epoch = 0                     # set by the caller: the `epoch` of the reference's optimizer.step(epoch=epoch) (step schedule)
         L.require_gpu()
         # XE criterion: 0 = LanguageModelCriterion, > 0 = LabelSmoothing(smoothing=...) (scripts/train_transformer.py:33-34); the SCST
         # step keeps RewardCriterion either way
@@ -42,8 +130,10 @@ class NativeTrainer:
         self.factor, self.warmup, self.clip, self.betas, self.eps = noamopt_factor, noamopt_warmup, grad_clip, betas, eps
         n = model._n_train
         self.grads = torch.zeros(n, device=self.dev)
-        self.m = torch.zeros(n, device=self.dev)
-        self.v = torch.zeros(n, device=self.dev)
+        # optimiser state: only the arrays the kind needs (adam: exp_avg, exp_avg_sq; sgdm / sgdmom / rmsprop / adagrad: one; sgd: none)
+        ns = self.spec.n_states
+        self.m = torch.zeros(n, device=self.dev) if ns >= 1 else None
+        self.v = torch.zeros(n, device=self.dev) if ns >= 2 else None
         self.step_count = 0
         self.loss_dev = torch.zeros(1, device=self.dev)
         self.norm_dev = torch.zeros(1, device=self.dev)
@@ -54,8 +144,8 @@ class NativeTrainer:
             self.mask_lr, self.mask_eps = prune_supermask_lr, mask_eps
             if self.train_masks:
                 self.dm = torch.zeros(n, device=self.dev)
-                self.mm = torch.zeros(n, device=self.dev)
-                self.mv = torch.zeros(n, device=self.dev)
+                self.mm = torch.zeros(n, device=self.dev) if ns >= 1 else None
+                self.mv = torch.zeros(n, device=self.dev) if ns >= 2 else None
                 # Only the ACTIVE masks are in the reference's mask-logit optimizer group (train_n_prune_transformer.py:67-82:
                 # `model.active_pruning_masks()`); logits inside `prune_mask_freeze_scope` never move.  Here the group is the whole
                 # mask arena, so the gradient of every frozen position is zeroed before the exchange and the update (a zero
@@ -72,7 +162,7 @@ class NativeTrainer:
             # scripts/train_n_prune_transformer.py:306-312: weight = max(5, 1.5 / (1 - target)) unless given
             self.sparsity_weight = sparsity_weight if (sparsity_weight is not None and sparsity_weight >= 0) else (
                 max(5.0, 1.5 / (1.0 - sparsity_target)) if sparsity_target is not None else 0.0)
-            self.max_train_step = max_train_step
+        self.max_train_step = max_train_step
         # gradient exchange dtype: None = fp32 (the sum the reference's single process computes), "bf16" = half the bytes on the links
         assert allreduce_dtype in (None, "fp32", "bf16"), allreduce_dtype
         self.allreduce_dtype = "bf16" if allreduce_dtype == "bf16" else None
@@ -86,13 +176,15 @@ class NativeTrainer:
         self._pending = None
         # One process, dense model: the decoder half of the arena (64 % of the parameters) takes its Adam update on a second
         # stream as soon as the decoder half of the backward has finished, beside the encoder half (clip_grad_value_ is
-        # element-wise, so the split is exact); the gradient arena is cleared by the update itself (ortk_adam_clip_zero).
+        # element-wise, so the split is exact); the gradient arena is cleared by the update itself (ortk_adam_clip_zero).  Every
+        # optimiser kind takes this split: each rule of ortk_optim_step is element-wise too.
         self.early_adam = (self.world == 1 and not self.masked and not self.overlap and self._dec_off % 4 == 0
                            and 0 < self._dec_off < self.grads.numel())      # (never beside an exchange of that half)
         # Masked models, one process: the element-wise tail of a step — straight-through mask backward, clip + Adam on the weights, clip +
         # Adam on the mask logits — as ONE pass over the arena (ortk_masked_adam_step) unless keep_grads asks for dW / dm or an all-reduce
         # has to come between the backward and Adam: configs[2] 12.33 -> 11.92 ms (scratch/masked_tail_ab.py; the same tail split over two
-        # streams beside the encoder half of the backward gained nothing on top: the backward is bandwidth-bound itself).
+        # streams beside the encoder half of the backward gained nothing on top: the backward is bandwidth-bound itself).  The fused
+        # kernel is Adam without weight decay; any other optimiser takes the unfused tail (mask backward, frozen scopes, two updates).
         self.fused_masked_tail = True
         self._opt_stream = None
         self._grads_clean = False
@@ -195,8 +287,31 @@ class NativeTrainer:
         L.check(fn(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, b1, b2, eps, self.clip,
                    1.0 - b1 ** t, 1.0 - b2 ** t, L.stream_ptr()), "ortk_adam_clip")
 
+    def _update(self, p, g, s1, s2, lr, eps, zero=False, weight_decay=0.0):
+        """clip + the configured optimiser on one range (p, g and the kind's state arrays).  Adam without weight decay is
+        ortk_adam_clip(_zero) with the arguments it has always had; everything else is ortk_optim_step."""
+        spec = self.spec
+        if spec.kind == "adam" and weight_decay == 0.0:
+            return self._adam(p, g, s1, s2, lr, eps, zero)
+        t = self.step_count
+        k = L.OptimArgs()
+        k.p, k.g, k.n = p.data_ptr(), g.data_ptr(), p.numel()
+        k.s1 = s1.data_ptr() if spec.n_states >= 1 else None
+        k.s2 = s2.data_ptr() if spec.n_states >= 2 else None
+        k.kind, k.first_step, k.zero_grad = L.OPT_KINDS[spec.kind], int(t == 1), int(zero)
+        k.lr, k.weight_decay, k.alpha, k.beta, k.eps, k.clip = lr, weight_decay, spec.alpha, spec.beta, eps, self.clip
+        k.bc1, k.bc2 = (1.0 - spec.alpha ** t, 1.0 - spec.beta ** t) if spec.kind == "adam" else (1.0, 1.0)
+        L.check(L.lib().ortk_optim_step(C.byref(k), L.stream_ptr()), "ortk_optim_step")
+
     def rate(self):
-        return noam_rate(max(self.step_count, 1), self.model.d_model, self.factor, self.warmup)
+        return self.spec.rate(self.step_count, self.epoch)
+
+    @classmethod
+    def from_config(cls, model, config, **kw):
+        """Trainer with the reference's optimiser options read from `config` (``.get``): optim, lr_scheduler, learning_rate(_min,
+        _decay_start, _decay_every, _decay_rate), optim_alpha / _beta / _epsilon, weight_decay, max_train_step, noamopt_factor /
+        _warmup; names the config does not carry keep their defaults.  `kw` overrides and adds the trainer's own arguments."""
+        return cls(model, **dict(OptimSpec.options_from_config(config), **kw))
 
     # ------------------------------------------------------------------ steps
     def xe_step(self, data, train=True):
@@ -403,7 +518,8 @@ class NativeTrainer:
                                  L.ptr(self.norm_dev), L.stream_ptr()), "ortk_sum")
         parallel.reduce_scalar_sum(self.norm_dev)   # LanguageModelCriterion semantics over the GLOBAL batch
         batch = self._batch(data, tok_weight, rollouts)
-        lr = self.rate()
+        lr, wd = self.rate(), self.spec.weight_decay
+        cut = lambda t, a, b: None if t is None else t[a:b]        # (a state array the optimiser kind does not have)
         early = None
         if self.early_adam:
             if self._opt_stream is None:
@@ -414,7 +530,8 @@ class NativeTrainer:
                 cur = torch.cuda.current_stream()
                 self._opt_stream.wait_stream(cur)
                 with torch.cuda.stream(self._opt_stream):
-                    self._adam(m._flat[d0:m._n_train], self.grads[d0:], self.m[d0:], self.v[d0:], lr, self.eps, zero=not self.keep_grads)
+                    self._update(m._flat[d0:m._n_train], self.grads[d0:], cut(self.m, d0, None), cut(self.v, d0, None), lr, self.eps,
+                                 zero=not self.keep_grads, weight_decay=wd)
         try:
             seed = self._fwd_bwd(batch, self.norm_dev, train, seed, after_decoder_half=early, encoded=encoded, smoothing=smoothing)
         except BaseException:
@@ -425,7 +542,8 @@ class NativeTrainer:
         parallel.reduce_scalar_sum(loss)            # every rank's partial is already divided by the GLOBAL normaliser
         if early is not None:
             # (early_adam implies a dense model: no sparse-plan overflow check can raise between the two halves of the update)
-            self._adam(m._flat[:d0], self.grads[:d0], self.m[:d0], self.v[:d0], lr, self.eps, zero=not self.keep_grads)
+            self._update(m._flat[:d0], self.grads[:d0], cut(self.m, 0, d0), cut(self.v, 0, d0), lr, self.eps, zero=not self.keep_grads,
+                         weight_decay=wd)
             torch.cuda.current_stream().wait_stream(self._opt_stream)
             self._grads_clean = not self.keep_grads
             return loss
@@ -433,7 +551,8 @@ class NativeTrainer:
             m.check_sparse_overflow()
         if self.masked:
             coef = None
-            one_pass = self.world == 1 and self.fused_masked_tail and not self.keep_grads      # (no exchange between the backward and Adam)
+            # (no exchange between the backward and Adam; the fused kernel is Adam without weight decay)
+            one_pass = self.world == 1 and self.fused_masked_tail and not self.keep_grads and self.spec.plain_adam
             if self.train_masks:
                 if not one_pass:
                     self.dm.zero_()
@@ -460,9 +579,10 @@ class NativeTrainer:
             if self.train_masks and self.mask_active is not None:
                 self.dm.mul_(self.mask_active)
         self._allreduce()
-        self._adam(m._flat[:m._n_train], self.grads, self.m, self.v, lr, self.eps, zero=not self.keep_grads)
+        self._update(m._flat[:m._n_train], self.grads, self.m, self.v, lr, self.eps, zero=not self.keep_grads, weight_decay=wd)
         self._grads_clean = not self.keep_grads
         if self.masked and self.train_masks:
-            # second param group of train_n_prune_transformer.py:67-82: lr = prune_supermask_lr (not Noam), eps 1e-2
-            self._adam(m._mask_flat, self.dm, self.mm, self.mv, self.mask_lr, self.mask_eps)
+            # second param group of train_n_prune_transformer.py:67-82: the same optimiser kind, lr = prune_supermask_lr (no scheduler
+            # touches it), eps 1e-2 where the kind has one, weight_decay 0
+            self._update(m._mask_flat, self.dm, self.mm, self.mv, self.mask_lr, self.mask_eps)
         return loss
