@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 13     /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 14    /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -385,6 +385,10 @@ typedef struct ortk_tuning {
                                      out, dropout / gate as kernel instances; bf16 results of the 256 x 256 tile stored 16 bytes per lane) | bit 0: the general
                                      epilogue of rounds 2-5 everywhere (measurement: profiles/r06_gemm_epilogue.txt) | bit 1: a column count of 256 n + 128
                                      (the padded vocabulary) is NOT split into a 256 x 256-tile launch + a 128-column remainder (measurement) */
+    int32_t attn16_short;         /* 1 (default): bf16-input attention blocks of at most 32 query rows and 32 keys (the decoder's causal self-attention
+                                     of the training step) run the one-wave-per-(group, head) kernels of ortk_attn16.hip, four waves per workgroup
+                                     | 0: the one-workgroup-per-(group, head) kernels everywhere (A/B; the results are bit-identical) | 4, 8: as 1 with
+                                     that many waves per workgroup (measurement: profiles/attn16_short.txt) */
 } ortk_tuning;
 void ortk_get_tuning(ortk_tuning* out);
 int ortk_set_tuning(const ortk_tuning* t);

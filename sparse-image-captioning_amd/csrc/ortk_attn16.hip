@@ -20,6 +20,11 @@
 //     gathered by the hardware-transposing LDS read; padded k ranges (keys 36 -> 64, queries 85 -> 96, 36 -> 64) are zero
 //     rows / columns of the images.
 // The pitch of 72 bf16 (144 B) makes the 16 rows of a ds_read_b128 service group fall on 16 distinct 16-byte slots.
+//
+// Two mappings of ONE per-tile code (fwd16_tile, bwd16_tile1, bwd16_tile2; bit-identical results): the block kernels
+// (attn16_fwd_kernel / attn16_bwd_kernel: a workgroup per (group, head), a wave per 16-row query tile) for those block shapes,
+// and the short kernels (attn16s_*: a WAVE per (group, head), bf16 inputs, at most 32 query rows and 32 keys) for the decoder's
+// causal self-attention, where a workgroup's second wave owned one query row or none (ortk_tuning.attn16_short).
 #include <cstdlib>
 #include "ortk_internal.h"
 
@@ -83,12 +88,147 @@ __device__ __forceinline__ void stage_rows(__bf16* img, const __bf16* src, int64
 __device__ __forceinline__ bf16x8 ld_frag(const float* p) { return cvt8(*reinterpret_cast<const float4*>(p), *reinterpret_cast<const float4*>(p + 4)); }
 __device__ __forceinline__ bf16x8 ld_frag(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 
+// Where the row fragments [index = 16*jt + lr][k = 32*ks + 8*lq ..] of a key-indexed operand come from (K in the score product,
+// V in dP^T = V dO^T): an LDS image (the block kernels) or registers loaded straight from global memory (the short kernels).
+template <int PD> struct LdsRowFrags {
+    const __bf16* img; int lr, lq;
+    __device__ __forceinline__ bf16x8 operator()(int jt, int ks) const { return frag_row<PD>(img, 16 * jt + lr, 32 * ks + 8 * lq); }
+};
+template <int NJT, int NKS> struct RegRowFrags {
+    bf16x8 f[NJT][NKS];
+    __device__ __forceinline__ bf16x8 operator()(int jt, int ks) const { return f[jt][ks]; }
+};
+// rows [0, rows) of the group's rows, head h, as such fragments; rows past the count are zero (what stage_rows leaves in an image)
+template <int NJT, int NKS>
+__device__ __forceinline__ void ld_row_frags(RegRowFrags<NJT, NKS>& out, const __bf16* src, int64_t ld, int rows, int lane) {
+    const int lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            out.f[jt][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            if (16 * jt + lr < rows) out.f[jt][ks] = ld_frag(src + (int64_t)(16 * jt + lr) * ld + 32 * ks + 8 * lq);
+        }
+}
+// One row of a [..][Lk] fp32 tensor (bias, saved P) as this lane's 4 consecutive keys of every key tile; zero where `on` is
+// false or the key does not exist
+template <int NJT>
+__device__ __forceinline__ void ld_keys4(float4 (&out)[NJT], const float* base, bool on, int64_t prow, int Lk, int lq) {
+    const bool vec_p = (Lk & 3) == 0;               // rows start 16-byte aligned
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        const int j0 = 16 * jt + 4 * lq;
+        out[jt] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (on) {
+            if (vec_p && j0 < Lk) out[jt] = *reinterpret_cast<const float4*>(base + prow + j0);
+            else { float* q = &out[jt].x; for (int r = 0; r < 4; ++r) if (j0 + r < Lk) q[r] = base[prow + j0 + r]; }
+        }
+    }
+}
+// One wave's share of a 32-row image (the short kernels): rows [0, rows) of a bf16 matrix slice into registers, zero past the
+// count; then into the image (pitch DKT + 8).  Split in two so that the loads are issued with every other load of the wave.
+template <int DKT>
+__device__ __forceinline__ void stage32_ld(bf16x8 (&v)[DKT / 16], const __bf16* src, int64_t ld, int rows, int lane) {
+    constexpr int CPR = DKT / 8;
+#pragma unroll
+    for (int n = 0; n < DKT / 16; ++n) {
+        const int idx = lane + 64 * n, r = idx / CPR, c = (idx % CPR) * 8;
+        v[n] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        if (r < rows) v[n] = *reinterpret_cast<const bf16x8*>(src + (int64_t)r * ld + c);
+    }
+}
+template <int DKT>
+__device__ __forceinline__ void stage32_st(__bf16* img, const bf16x8 (&v)[DKT / 16], int lane) {
+    constexpr int CPR = DKT / 8;
+#pragma unroll
+    for (int n = 0; n < DKT / 16; ++n) {
+        const int idx = lane + 64 * n, r = idx / CPR, c = (idx % CPR) * 8;
+        *reinterpret_cast<bf16x8*>(img + r * (DKT + 8) + c) = v[n];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ forward
-// One workgroup per (group g, head h); one wave per 16-row query tile.  NJT = key tiles (Lk <= 16 * NJT <= 128).
+// One 16-row query tile of one (group, head), by one wave: scores, mask / causal / bias, soft-max, P store, dropout, P.V.
+// kfr = the K row fragments; sMask[j] = key mask (-1: padded key); sV = [KJ][PD] image of V, zero-padded; sP = this wave's
+// [16][PJ] image, key columns 16*NJT .. KJ-1 zero.  i = this lane's query row inside the group, iv = it exists; prow / drow =
+// first element of its P row / of the row its dropout draws are keyed by; orow = its row of O.
+template <int NJT, int DKT, int PJ, typename KF>
+__device__ __forceinline__ void fwd16_tile(const ortk_attn_args& a, const KF& kfr, const bf16x8 (&qf)[DKT / 32], const float4 (&bias4)[NJT],
+                                           const float* sMask, const __bf16* sV, __bf16* sP, int lane, int i, bool iv,
+                                           int64_t prow, int64_t drow, int64_t orow, int h, float inv_keep) {
+    constexpr int DK = DKT, PD = DKT + 8, KJ = KeyGeo<NJT>::KJ;
+    const float qscale = DKT == 64 ? 0.125f : 0.17677669529663687f;      // 1 / sqrt(dk)
+    const int lr = lane & 15, lq = lane >> 4, Lk = a.Lk;
+    const bool vec_p = (Lk & 3) == 0;               // P / bias rows start 16-byte aligned
+    // S^T[j = 16*jt + 4*lq + r][i = lr]
+    f32x4 s[NJT];
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        s[jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks) s[jt] = mma(kfr(jt, ks), qf[ks], s[jt]);
+    }
+    const int qpos = a.causal_period > 0 ? i % a.causal_period : 0;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        const int j0 = 16 * jt + 4 * lq;
+        const float bb[4] = {bias4[jt].x, bias4[jt].y, bias4[jt].z, bias4[jt].w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = j0 + r;
+            const float mk = sMask[j];
+            float x = s[jt][r] * qscale;
+            if (mk == 0.f || (a.causal_period > 0 && j > qpos)) x = -1e9f;
+            if (mk < 0.f) x = -INFINITY;                                      // padded key: not part of the row
+            else if (a.bias && iv) x = bb[r] + x;
+            s[jt][r] = x;
+            mx = fmaxf(mx, x);
+        }
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64)); mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    float sum = 0.f;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const float e = expf(s[jt][r] - mx); s[jt][r] = e; sum += e; }
+    sum += __shfl_xor(sum, 16, 64); sum += __shfl_xor(sum, 32, 64);
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        const int j0 = 16 * jt + 4 * lq;
+        float p[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) p[r] = (iv && j0 + r < Lk) ? s[jt][r] / sum : 0.f;
+        if (a.p && iv) {
+            if (vec_p && j0 < Lk) *reinterpret_cast<float4*>(a.p + prow + j0) = make_float4(p[0], p[1], p[2], p[3]);
+            else for (int r = 0; r < 4; ++r) if (j0 + r < Lk) a.p[prow + j0 + r] = p[r];
+        }
+        if (a.drop_p > 0.f) {
+            bool kp[4];
+            ortk_keep4(a.drop_seed, (uint64_t)(drow + j0), a.drop_p, kp);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = kp[r] ? p[r] * inv_keep : 0.f;
+        }
+        *reinterpret_cast<bf16x4*>(sP + lr * PJ + j0) = cvt4(make_float4(p[0], p[1], p[2], p[3]));
+    }
+    wsync();
+    // O^T[d = 16*dt + 4*lq + r][i = lr] = sum_j V[j][d] Pd[i][j]
+    bf16x8 pf[KJ / 32];
+#pragma unroll
+    for (int ks = 0; ks < KJ / 32; ++ks) pf[ks] = frag_row<PJ>(sP, lr, 32 * ks + 8 * lq);
+#pragma unroll
+    for (int dt = 0; dt < DK / 16; ++dt) {
+        f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KJ / 32; ++ks) o = mma(frag_tr<PD>(sV, 32 * ks, 16 * dt, lane), pf[ks], o);
+        if (iv) st_elem4(a.o, orow * a.ldo + h * DK + 16 * dt + 4 * lq, a.o_dtype, make_float4(o[0], o[1], o[2], o[3]));
+    }
+}
+
+// The block kernel: one workgroup per (group g, head h); one wave per 16-row query tile.  NJT = key tiles (Lk <= 16 * NJT <= 128).
 template <int NJT, typename TQ, int DKT>
 __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
     constexpr int DK = DKT, PD = DKT + 8;           // features per head; pitch of the [row][feature] images
-    const float qscale = DKT == 64 ? 0.125f : 0.17677669529663687f;      // 1 / sqrt(dk)
     const TQ* aq = reinterpret_cast<const TQ*>(a.q); const TQ* ak = reinterpret_cast<const TQ*>(a.k); const TQ* av = reinterpret_cast<const TQ*>(a.v);
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -100,7 +240,6 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
     __bf16* sP = sV + KJ * PD + wave * 16 * PJ;     // [16][PJ]       this wave's dropped P: rows = query, columns = key 0..KJ-1
     float* sMask = reinterpret_cast<float*>(sm16 + (16 * NJT + KJ) * PD + 16 * nw * PJ);   // [128]
     const int lr = lane & 15, lq = lane >> 4;
-    const bool vec_p = (Lk & 3) == 0;               // P / bias rows start 16-byte aligned
     const int nit = (Lq + 15) >> 4;
     // ragged groups (ortk_attn_args.q_off): the group's first query row and its row count; with kv_ragged its keys are those rows
     const int64_t qrow0 = a.q_off ? (int64_t)a.q_off[(int64_t)g * a.q_off_stride] : (int64_t)g * Lq;
@@ -125,15 +264,7 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
         for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = ld_frag(qp + 32 * ks);
     }
     float4 bias4[NJT];
-#pragma unroll
-    for (int jt = 0; jt < NJT; ++jt) {
-        const int j0 = 16 * jt + 4 * lq;
-        bias4[jt] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a.bias && iv) {
-            if (vec_p && j0 < Lk) bias4[jt] = *reinterpret_cast<const float4*>(a.bias + prow + j0);
-            else { float* bp = &bias4[jt].x; for (int r = 0; r < 4; ++r) if (j0 + r < Lk) bp[r] = a.bias[prow + j0 + r]; }
-        }
-    }
+    ld_keys4<NJT>(bias4, a.bias, a.bias && iv, prow, Lk, lq);
     stage_rows<DK>(sK, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, 16 * NJT, tid, blockDim.x);
     stage_rows<DK>(sV, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, KJ, tid, blockDim.x);
     for (int j = tid; j < 128; j += blockDim.x)     // all 128 entries whatever the workgroup size (one wave when Lq <= 16)
@@ -143,70 +274,82 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
         *reinterpret_cast<bf16x4*>(sP + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
     __syncthreads();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-    if (it < nit) {
-        // S^T[j = 16*jt + 4*lq + r][i = lr]
-        f32x4 s[NJT];
+    if (it < nit)
+        fwd16_tile<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sK, lr, lq}, qf, bias4, sMask, sV, sP, lane, i, iv, prow, drow, qrow0 + i, h, inv_keep);
+}
+
+// The short kernel (bf16 Q / K / V, Lq <= 32, Lk <= 32: the decoder's causal self-attention): one WAVE per (group, head), pair
+// p = blockIdx.x * W + wave, so the heads of a group sit in adjacent waves and a workgroup reads whole neighbouring lines of the
+// packed rows.  The wave runs the query tiles that hold rows of its group one after the other (captions of at most 16 rows: one).
+// K goes from global memory straight into row fragments; LDS holds, per wave, the V image (transposing reads), the P image
+// (C-layout -> operand) and the 32 key-mask entries: 6 016 B at dk = 64.  Every global load is issued before the first wait;
+// no __syncthreads(): a wave only ever touches its own LDS region.
+constexpr int KJS = 32, PJS = KJS + 8;            // key range and [query][key] image pitch of the short kernels
+template <int DKT> constexpr int fwd16s_wave_elems() { return KJS * (DKT + 8) + 16 * PJS + 64; }      // bf16 elements (64 = 32 floats)
+template <int NJT, int DKT>
+__global__ __launch_bounds__(512) void attn16s_fwd_kernel(ortk_attn_args a) {
+    static_assert(NJT <= 2, "the short kernels serve at most 32 keys");
+    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32;
+    const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
+    extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
+    const int pair = blockIdx.x * W + wave;
+    if (pair >= a.nkv * a.H) return;                // the last workgroup may be partly empty (no workgroup barrier below)
+    const int g = pair / a.H, h = pair - g * a.H;
+    const int Lk = a.Lk, Lq = a.Lq;
+    __bf16* sV = sm16 + wave * fwd16s_wave_elems<DKT>();       // [KJS][PD]  rows = key, zero-padded
+    __bf16* sP = sV + KJS * PD;                                // [16][PJS]  dropped P of the current tile
+    float* sMask = reinterpret_cast<float*>(sP + 16 * PJS);    // [32]
+    const int lr = lane & 15, lq = lane >> 4;
+    int64_t qrow0 = (int64_t)g * Lq;
+    int Lqg = Lq;
+    if (a.q_off) {                                  // both entries in one round trip
+        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
+        qrow0 = o0; Lqg = min(Lq, o1 - o0);
+    }
+    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
+    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    // ---- every global load of the wave
+    bf16x8 vreg[DKT / 16];
+    stage32_ld<DKT>(vreg, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
+    const float mk = (lane < Lkg) ? (a.kmask ? a.kmask[krow0 + lane] : 1.f) : -1.f;        // -1: padded key (Lkg <= 32: lanes 0 .. 31 are stored)
+    RegRowFrags<NJT, NKS> kf;
+    ld_row_frags<NJT, NKS>(kf, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, lane);
+    bf16x8 qf[2][NKS];
+    float4 bias4[2][NJT];
+    int64_t prow[2], drow[2];
+    bool iv[2];
 #pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-            s[jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < 2; ++it) {
+        const int i = it * 16 + lr;
+        iv[it] = i < Lqg;
+        prow[it] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
+        drow[it] = prow[it];
+        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[it])
+            drow[it] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
 #pragma unroll
-            for (int ks = 0; ks < DK / 32; ++ks) s[jt] = mma(frag_row<PD>(sK, 16 * jt + lr, 32 * ks + 8 * lq), qf[ks], s[jt]);
+        for (int ks = 0; ks < NKS; ++ks) qf[it][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        if (iv[it]) {
+            const __bf16* qp = aq + (qrow0 + i) * a.ldq + h * DK + 8 * lq;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) qf[it][ks] = ld_frag(qp + 32 * ks);
         }
-        const int qpos = a.causal_period > 0 ? i % a.causal_period : 0;
-        float mx = -INFINITY;
+        ld_keys4<NJT>(bias4[it], a.bias, a.bias && iv[it], prow[it], Lk, lq);
+    }
+    // ---- the wave's LDS region
+    stage32_st<DKT>(sV, vreg, lane);
+    if (lane < 32) sMask[lane] = mk;
+    // (key columns 16*NJT .. KJS-1 of the P image are never written by a tile)
+    for (int idx = lane; idx < 16 * (KJS / 4); idx += 64)
+        *reinterpret_cast<bf16x4*>(sP + (idx / (KJS / 4)) * PJS + (idx % (KJS / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+    wsync();
+    const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
 #pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-            const int j0 = 16 * jt + 4 * lq;
-            const float bb[4] = {bias4[jt].x, bias4[jt].y, bias4[jt].z, bias4[jt].w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = j0 + r;
-                const float mk = sMask[j];
-                float x = s[jt][r] * qscale;
-                if (mk == 0.f || (a.causal_period > 0 && j > qpos)) x = -1e9f;
-                if (mk < 0.f) x = -INFINITY;                                      // padded key: not part of the row
-                else if (a.bias && iv) x = bb[r] + x;
-                s[jt][r] = x;
-                mx = fmaxf(mx, x);
-            }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64)); mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { const float e = expf(s[jt][r] - mx); s[jt][r] = e; sum += e; }
-        sum += __shfl_xor(sum, 16, 64); sum += __shfl_xor(sum, 32, 64);
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-            const int j0 = 16 * jt + 4 * lq;
-            float p[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) p[r] = (iv && j0 + r < Lk) ? s[jt][r] / sum : 0.f;
-            if (a.p && iv) {
-                if (vec_p && j0 < Lk) *reinterpret_cast<float4*>(a.p + prow + j0) = make_float4(p[0], p[1], p[2], p[3]);
-                else for (int r = 0; r < 4; ++r) if (j0 + r < Lk) a.p[prow + j0 + r] = p[r];
-            }
-            if (a.drop_p > 0.f) {
-                bool kp[4];
-                ortk_keep4(a.drop_seed, (uint64_t)(drow + j0), a.drop_p, kp);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) p[r] = kp[r] ? p[r] * inv_keep : 0.f;
-            }
-            *reinterpret_cast<bf16x4*>(sP + lr * PJ + j0) = cvt4(make_float4(p[0], p[1], p[2], p[3]));
-        }
-        wsync();
-        // O^T[d = 16*dt + 4*lq + r][i = lr] = sum_j V[j][d] Pd[i][j]
-        bf16x8 pf[KJ / 32];
-#pragma unroll
-        for (int ks = 0; ks < KJ / 32; ++ks) pf[ks] = frag_row<PJ>(sP, lr, 32 * ks + 8 * lq);
-#pragma unroll
-        for (int dt = 0; dt < DK / 16; ++dt) {
-            f32x4 o = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KJ / 32; ++ks) o = mma(frag_tr<PD>(sV, 32 * ks, 16 * dt, lane), pf[ks], o);
-            if (iv) st_elem4(a.o, (qrow0 + i) * a.ldo + h * DK + 16 * dt + 4 * lq, a.o_dtype, make_float4(o[0], o[1], o[2], o[3]));
-        }
+    for (int it = 0; it < 2; ++it) {
+        if (it * 16 >= Lqg) break;                  // a tile with no row of the group stores nothing
+        fwd16_tile<NJT, DKT, PJS>(a, kf, qf[it], bias4[it], sMask, sV, sP, lane, it * 16 + lr, iv[it], prow[it], drow[it],
+                                  qrow0 + it * 16 + lr, h, inv_keep);
+        wsync();                                    // the next tile overwrites the P image
     }
 }
 static int key_kj(int njt) { return njt <= 2 ? 32 : njt <= 4 ? 64 : njt <= 6 ? 96 : 128; }
@@ -219,10 +362,92 @@ static size_t fwd16_lds(int njt, int nw, int dk) {
 // Phase 1 (wave = 16-row query tile): dP^T = V dO^T, dS = P (dP - rowsum(P dP)), dQ = dS K / sqrt(dk); dS / sqrt(dk) and the
 // dropped P go to workgroup-wide images.  Phase 2 (the 2 x NJT x 4 output tiles shared by the waves): dK = dS^T Q / sqrt(dk),
 // dV = Pd^T dO over all query rows of the group.  Lqp = query rows padded to a multiple of 32 (k range of phase 2).
+//
+// Phase 1 for one 16-row query tile of one (group, head), by one wave.  vfr = the V row fragments, gf = this lane's dO row
+// fragments, praw = its saved P row; sK = [KJ][PD] image of K, zero-padded; sS / sD = the [query][key] images of the group (row
+// i = this lane's query row inside the group; key columns 16*NJT .. KJ-1 zero).  prow / drow / qrow as in fwd16_tile.
+template <int NJT, int DKT, int PJ, typename VF>
+__device__ __forceinline__ void bwd16_tile1(const ortk_attn_args& a, const VF& vfr, const bf16x8 (&gf)[DKT / 32], const float4 (&praw)[NJT],
+                                            const __bf16* sK, __bf16* sS, __bf16* sD, int lane, int i, bool iv,
+                                            int64_t prow, int64_t drow, int64_t qrow, int h, float inv_keep) {
+    constexpr int DK = DKT, PD = DKT + 8, KJ = KeyGeo<NJT>::KJ;
+    const float qscale = DKT == 64 ? 0.125f : 0.17677669529663687f;
+    const int lq = lane >> 4, Lk = a.Lk;
+    const bool vec_p = (Lk & 3) == 0;
+    // dP^T[j = 16*jt + 4*lq + r][i = lr]
+    f32x4 dp[NJT], pp[NJT];
+    float dot = 0.f;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        dp[jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < DK / 32; ++ks) dp[jt] = mma(vfr(jt, ks), gf[ks], dp[jt]);
+        const int j0 = 16 * jt + 4 * lq;
+        const float pv[4] = {praw[jt].x, praw[jt].y, praw[jt].z, praw[jt].w};
+        float pd[4];
+        bool kp[4] = {true, true, true, true};
+        if (a.drop_p > 0.f) ortk_keep4(a.drop_seed, (uint64_t)(drow + j0), a.drop_p, kp);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const bool valid = iv && j0 + r < Lk;
+            const bool keep = valid && kp[r];
+            const float d = keep ? dp[jt][r] * inv_keep : 0.f;
+            pd[r] = keep ? pv[r] * inv_keep : 0.f;
+            pp[jt][r] = valid ? pv[r] : 0.f; dp[jt][r] = d; dot += pp[jt][r] * d;
+        }
+        *reinterpret_cast<bf16x4*>(sD + i * PJ + j0) = cvt4(make_float4(pd[0], pd[1], pd[2], pd[3]));
+    }
+    dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt) {
+        const int j0 = 16 * jt + 4 * lq;
+        float ds[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ds[r] = pp[jt][r] * (dp[jt][r] - dot);
+        if (a.dscore && iv) {
+            if (vec_p && j0 < Lk) *reinterpret_cast<float4*>(a.dscore + prow + j0) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+            else for (int r = 0; r < 4; ++r) if (j0 + r < Lk) a.dscore[prow + j0 + r] = ds[r];
+        }
+        *reinterpret_cast<bf16x4*>(sS + i * PJ + j0) = cvt4(make_float4(ds[0] * qscale, ds[1] * qscale, ds[2] * qscale, ds[3] * qscale));
+    }
+    wsync();
+    // dQ^T[d = 16*dt + 4*lq + r][i = lr] = sum_j K[j][d] dSs[i][j]
+    bf16x8 sf[KJ / 32];
+#pragma unroll
+    for (int ks = 0; ks < KJ / 32; ++ks) sf[ks] = frag_row<PJ>(sS, i, 32 * ks + 8 * lq);
+#pragma unroll
+    for (int dt = 0; dt < DK / 16; ++dt) {
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KJ / 32; ++ks) acc = mma(frag_tr<PD>(sK, 32 * ks, 16 * dt, lane), sf[ks], acc);
+        if (iv) st_elem4(a.dq, qrow * a.lddq + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, make_float4(acc[0], acc[1], acc[2], acc[3]));
+    }
+}
+// Phase 2, output tile t = (which, jt, dt) of one (group, head), by one wave:
+// D[d = 16*dt + 4*lq + r][j = 16*jt + lr] = sum_i B[i][d] A[i][j], (A, B) = (dS, Q) for dK and (dropped P, dO) for dV
+template <int NJT, int DKT, int PJ>
+__device__ __forceinline__ void bwd16_tile2(const ortk_attn_args& a, int t, const __bf16* sS, const __bf16* sD, const __bf16* sQ, const __bf16* sG,
+                                            int Lqp, int lane, int Lkg, int64_t krow0, int h) {
+    constexpr int DK = DKT, PD = DKT + 8, NDT = DK / 16;
+    const int lr = lane & 15, lq = lane >> 4;
+    const int which = t / (NJT * NDT), rem = t - which * NJT * NDT, jt = rem / NDT, dt = rem % NDT;
+    const __bf16* sA = which == 0 ? sS : sD;      // [query][key]
+    const __bf16* sB = which == 0 ? sQ : sG;      // [query][feature]
+    f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < Lqp; k0 += 32) acc = mma(frag_tr<PD>(sB, k0, 16 * dt, lane), frag_tr<PJ>(sA, k0, 16 * jt, lane), acc);
+    const int j = 16 * jt + lr;
+    if (j < Lkg) {
+        const int64_t row = krow0 + j;
+        const float4 v = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        if (which == 0) st_elem4(a.d_k, row * a.lddk + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, v);
+        else            st_elem4(a.dv, row * a.lddv + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, v);
+    }
+}
+
+// The block kernel: one workgroup per (group g, head h); phase 1 with one wave per query tile, phase 2 shared by the waves.
 template <int NJT, typename TQ, int DKT>
 __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int Lqp) {
     constexpr int DK = DKT, PD = DKT + 8;
-    const float qscale = DKT == 64 ? 0.125f : 0.17677669529663687f;
     const TQ* aq = reinterpret_cast<const TQ*>(a.q); const TQ* ak = reinterpret_cast<const TQ*>(a.k); const TQ* av = reinterpret_cast<const TQ*>(a.v);
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -236,7 +461,6 @@ __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int L
     __bf16* sS = sG + Lqp * PD;             // [Lqp][PJ]      dS / sqrt(dk): rows = query, columns = key 0..KJ-1
     __bf16* sD = sS + Lqp * PJ;             // [Lqp][PJ]      dropped P
     const int lr = lane & 15, lq = lane >> 4;
-    const bool vec_p = (Lk & 3) == 0;
     const int nit = (Lq + 15) >> 4;
     // ragged groups: see the forward kernel.  Query rows past the group's count are staged as ZERO rows of Q and dO (they are
     // another group's rows): they add nothing to dK / dV
@@ -252,15 +476,7 @@ __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int L
     const int64_t drow = (a.drop_rows && a.q_off && iv && a.drop_p > 0.f)
                              ? (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk : prow;
     float4 praw[NJT];
-#pragma unroll
-    for (int jt = 0; jt < NJT; ++jt) {
-        const int j0 = 16 * jt + 4 * lq;
-        praw[jt] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (iv) {
-            if (vec_p && j0 < Lk) praw[jt] = *reinterpret_cast<const float4*>(a.p + prow + j0);
-            else { float* q = &praw[jt].x; for (int r = 0; r < 4; ++r) if (j0 + r < Lk) q[r] = a.p[prow + j0 + r]; }
-        }
-    }
+    ld_keys4<NJT>(praw, a.p, iv, prow, Lk, lq);
     stage_rows<DK>(sK, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, KJ, tid, blockDim.x);
     stage_rows<DK>(sV, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, 16 * NJT, tid, blockDim.x);
     stage_rows<DK>(sQ, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, Lqp, tid, blockDim.x);
@@ -274,72 +490,93 @@ __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int L
         bf16x8 gf[DK / 32];
 #pragma unroll
         for (int ks = 0; ks < DK / 32; ++ks) gf[ks] = frag_row<PD>(sG, i, 32 * ks + 8 * lq);
-        // dP^T[j = 16*jt + 4*lq + r][i = lr]
-        f32x4 dp[NJT], pp[NJT];
-        float dot = 0.f;
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-            dp[jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < DK / 32; ++ks) dp[jt] = mma(frag_row<PD>(sV, 16 * jt + lr, 32 * ks + 8 * lq), gf[ks], dp[jt]);
-            const int j0 = 16 * jt + 4 * lq;
-            const float pv[4] = {praw[jt].x, praw[jt].y, praw[jt].z, praw[jt].w};
-            float pd[4];
-            bool kp[4] = {true, true, true, true};
-            if (a.drop_p > 0.f) ortk_keep4(a.drop_seed, (uint64_t)(drow + j0), a.drop_p, kp);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool valid = iv && j0 + r < Lk;
-                const bool keep = valid && kp[r];
-                const float d = keep ? dp[jt][r] * inv_keep : 0.f;
-                pd[r] = keep ? pv[r] * inv_keep : 0.f;
-                pp[jt][r] = valid ? pv[r] : 0.f; dp[jt][r] = d; dot += pp[jt][r] * d;
-            }
-            *reinterpret_cast<bf16x4*>(sD + i * PJ + j0) = cvt4(make_float4(pd[0], pd[1], pd[2], pd[3]));
-        }
-        dot += __shfl_xor(dot, 16, 64); dot += __shfl_xor(dot, 32, 64);
-#pragma unroll
-        for (int jt = 0; jt < NJT; ++jt) {
-            const int j0 = 16 * jt + 4 * lq;
-            float ds[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) ds[r] = pp[jt][r] * (dp[jt][r] - dot);
-            if (a.dscore && iv) {
-                if (vec_p && j0 < Lk) *reinterpret_cast<float4*>(a.dscore + prow + j0) = make_float4(ds[0], ds[1], ds[2], ds[3]);
-                else for (int r = 0; r < 4; ++r) if (j0 + r < Lk) a.dscore[prow + j0 + r] = ds[r];
-            }
-            *reinterpret_cast<bf16x4*>(sS + i * PJ + j0) = cvt4(make_float4(ds[0] * qscale, ds[1] * qscale, ds[2] * qscale, ds[3] * qscale));
-        }
-        wsync();
-        // dQ^T[d = 16*dt + 4*lq + r][i = lr] = sum_j K[j][d] dSs[i][j]
-        bf16x8 sf[KJ / 32];
-#pragma unroll
-        for (int ks = 0; ks < KJ / 32; ++ks) sf[ks] = frag_row<PJ>(sS, i, 32 * ks + 8 * lq);
-#pragma unroll
-        for (int dt = 0; dt < DK / 16; ++dt) {
-            f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < KJ / 32; ++ks) acc = mma(frag_tr<PD>(sK, 32 * ks, 16 * dt, lane), sf[ks], acc);
-            if (iv) st_elem4(a.dq, (qrow0 + i) * a.lddq + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, make_float4(acc[0], acc[1], acc[2], acc[3]));
-        }
+        bwd16_tile1<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sV, lr, lq}, gf, praw, sK, sS, sD, lane, i, iv, prow, drow, qrow0 + i, h, inv_keep);
     }
     __syncthreads();
-    // phase 2: tile t = (which, jt, dt): D[d = 16*dt + 4*lq + r][j = 16*jt + lr] = sum_i B[i][d] A[i][j]
-    constexpr int NDT = DK / 16;
-    const int ntiles = 2 * NJT * NDT;
-    for (int t = wave; t < ntiles; t += nw) {
-        const int which = t / (NJT * NDT), rem = t - which * NJT * NDT, jt = rem / NDT, dt = rem % NDT;
-        const __bf16* sA = which == 0 ? sS : sD;      // [query][key]
-        const __bf16* sB = which == 0 ? sQ : sG;      // [query][feature]
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int k0 = 0; k0 < Lqp; k0 += 32) acc = mma(frag_tr<PD>(sB, k0, 16 * dt, lane), frag_tr<PJ>(sA, k0, 16 * jt, lane), acc);
-        const int j = 16 * jt + lr;
-        if (j < Lkg) {
-            const int64_t row = krow0 + j;
-            const float4 v = make_float4(acc[0], acc[1], acc[2], acc[3]);
-            if (which == 0) st_elem4(a.d_k, row * a.lddk + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, v);
-            else            st_elem4(a.dv, row * a.lddv + h * DK + 16 * dt + 4 * lq, a.dqkv_dtype, v);
+    for (int t = wave; t < 2 * NJT * (DK / 16); t += nw) bwd16_tile2<NJT, DKT, PJ>(a, t, sS, sD, sQ, sG, Lqp, lane, Lkg, krow0, h);
+}
+
+// The short kernel: the mapping of attn16s_fwd_kernel.  One wave runs phase 1 for the query tiles that hold rows of its group,
+// then the 2 x NJT x (dk / 16) tiles of phase 2.  V and dO reach dP^T = V dO^T as row fragments straight from global memory; LDS
+// holds, per wave, the dS / P images (C-layout -> operand; 32 query rows, pitch PJS) and ONE [32][PD] image for the operand a
+// transposing read needs next: K for dQ, then Q for the dK tiles, then dO for the dV tiles (Q and dO wait in registers, where
+// their loads left them): 9 728 B at dk = 64, 16 waves per compute unit.  Key tiles past the group's keys (a caption of at most
+// 16 rows: tile 1) have no row of dK / dV to store and are skipped.
+template <int DKT> constexpr int bwd16s_wave_elems() { return 32 * (DKT + 8) + 2 * 32 * PJS; }
+template <int NJT, int DKT>
+__global__ __launch_bounds__(512) void attn16s_bwd_kernel(ortk_attn_args a) {
+    static_assert(NJT <= 2, "the short kernels serve at most 32 keys");
+    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32, LQP = 32;
+    const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
+    const __bf16* ag = reinterpret_cast<const __bf16*>(a.d_o);
+    extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
+    const int pair = blockIdx.x * W + wave;
+    if (pair >= a.nkv * a.H) return;                // the last workgroup may be partly empty (no workgroup barrier below)
+    const int g = pair / a.H, h = pair - g * a.H;
+    const int Lk = a.Lk, Lq = a.Lq;
+    __bf16* sX = sm16 + wave * bwd16s_wave_elems<DKT>();       // [32][PD]    K (rows = key), then Q, then dO (rows = query); zero-padded
+    __bf16* sS = sX + 32 * PD;                                 // [LQP][PJS]  dS / sqrt(dk)
+    __bf16* sD = sS + LQP * PJS;                               // [LQP][PJS]  dropped P
+    const int lr = lane & 15, lq = lane >> 4;
+    int64_t qrow0 = (int64_t)g * Lq;
+    int Lqg = Lq;
+    if (a.q_off) {
+        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
+        qrow0 = o0; Lqg = min(Lq, o1 - o0);
+    }
+    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
+    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    // ---- every global load of the wave: what phase 1 consumes from registers first, then the three staged images
+    RegRowFrags<NJT, NKS> vf;
+    ld_row_frags<NJT, NKS>(vf, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
+    bf16x8 gf[2][NKS];
+    float4 praw[2][NJT];
+    int64_t prow[2], drow[2];
+    bool iv[2];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int i = it * 16 + lr;
+        iv[it] = i < Lqg;
+        prow[it] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
+        drow[it] = prow[it];
+        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[it])
+            drow[it] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) gf[it][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};      // (a zero row of the dO image)
+        if (iv[it]) {
+            const __bf16* gp = ag + (qrow0 + i) * a.lddo + h * DK + 8 * lq;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) gf[it][ks] = ld_frag(gp + 32 * ks);
         }
+        ld_keys4<NJT>(praw[it], a.p, iv[it], prow[it], Lk, lq);
+    }
+    bf16x8 kreg[DKT / 16], qreg[DKT / 16], greg[DKT / 16];
+    stage32_ld<DKT>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, lane);
+    stage32_ld<DKT>(qreg, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, lane);
+    stage32_ld<DKT>(greg, ag + qrow0 * a.lddo + h * DK, a.lddo, Lqg, lane);
+    // ---- the wave's LDS region.  dS / P images: key columns 16*NJT .. KJS-1 and the rows of a tile that is not run stay zero
+    for (int idx = lane; idx < 2 * LQP * PJS / 8; idx += 64)
+        *reinterpret_cast<bf16x8*>(sS + idx * 8) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};           // sD follows sS
+    stage32_st<DKT>(sX, kreg, lane);
+    wsync();
+    const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        if (it * 16 >= Lqg) break;                  // a tile with no row of the group: zero rows of dS / P, nothing stored
+        bwd16_tile1<NJT, DKT, PJS>(a, vf, gf[it], praw[it], sX, sS, sD, lane, it * 16 + lr, iv[it], prow[it], drow[it],
+                                   qrow0 + it * 16 + lr, h, inv_keep);
+    }
+    // phase 2: tile t = (which, jt, dt); which = 0 the dK tiles (dS, Q), 1 the dV tiles (dropped P, dO)
+    constexpr int NDT = DK / 16;
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+        wsync();                                    // the image's readers (dQ; the dK tiles) are done, and dS / P are whole
+        stage32_st<DKT>(sX, which == 0 ? qreg : greg, lane);
+        wsync();
+        for (int jt = 0; jt < NJT && 16 * jt < Lkg; ++jt)
+            for (int dt = 0; dt < NDT; ++dt)
+                bwd16_tile2<NJT, DKT, PJS>(a, (which * NJT + jt) * NDT + dt, sS, sD, sX, sX, LQP, lane, Lkg, krow0, h);
     }
 }
 static size_t bwd16_lds(int njt, int Lqp, int dk) {
@@ -392,7 +629,28 @@ template <typename TQ, int DKT> static bwd16_fn pick_bwd(int njt) {
     }
 }
 
+// The short kernels (one wave per (group, head)): bf16 Q / K / V / dO, at most 32 query rows and 32 keys per group.  Returns the
+// waves per workgroup, 0 = the block kernels (ortk_tuning.attn16_short: 0 never | 1 the default width | 4, 8 that width).
+static int short_waves(const ortk_attn_args* a) {
+    const int sw = ortk::tuning().attn16_short;
+    if (!sw || a->qkv_dtype != 1 || a->Lq > 32 || a->Lk > 32) return 0;
+    return sw == 8 ? 8 : 4;
+}
+template <typename FN> static int launch_short(FN fn, size_t wave_bytes, int W, const ortk_attn_args* a, hipStream_t s) {
+    const size_t lds = wave_bytes * W;
+    const int64_t pairs = (int64_t)a->nkv * a->H;
+    if (lds > 64 * 1024) ortk::lds_attr(reinterpret_cast<const void*>(fn), 160 * 1024);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((pairs + W - 1) / W)), dim3(64 * W), lds, s, *a);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
 int attn16_fwd(const ortk_attn_args* a, hipStream_t s) {
+    if (const int W = short_waves(a)) {
+        const bool two = a->Lk > 16;
+        const fwd16_fn fn = a->dk == 64 ? (two ? attn16s_fwd_kernel<2, 64> : attn16s_fwd_kernel<1, 64>) : (two ? attn16s_fwd_kernel<2, 32> : attn16s_fwd_kernel<1, 32>);
+        return launch_short(fn, (a->dk == 64 ? fwd16s_wave_elems<64>() : fwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
+    }
     const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16;
     const fwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_fwd<__bf16, 64>(njt) : pick_fwd<float, 64>(njt))
                                     : (a->qkv_dtype ? pick_fwd<__bf16, 32>(njt) : pick_fwd<float, 32>(njt));
@@ -404,6 +662,11 @@ int attn16_fwd(const ortk_attn_args* a, hipStream_t s) {
 }
 
 int attn16_bwd(const ortk_attn_args* a, hipStream_t s) {
+    if (const int W = short_waves(a)) {
+        const bool two = a->Lk > 16;
+        const fwd16_fn fn = a->dk == 64 ? (two ? attn16s_bwd_kernel<2, 64> : attn16s_bwd_kernel<1, 64>) : (two ? attn16s_bwd_kernel<2, 32> : attn16s_bwd_kernel<1, 32>);
+        return launch_short(fn, (a->dk == 64 ? bwd16s_wave_elems<64>() : bwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
+    }
     const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16, Lqp = (int)ortk_align(a->Lq, 32);
     const bwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_bwd<__bf16, 64>(njt) : pick_bwd<float, 64>(njt))
                                     : (a->qkv_dtype ? pick_bwd<__bf16, 32>(njt) : pick_bwd<float, 32>(njt));

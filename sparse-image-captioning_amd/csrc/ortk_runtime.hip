@@ -27,6 +27,7 @@ static ortk_tuning tuning_defaults() {
     t.ln_fuse = 0;
     t.samp_epilogue = 1;
     t.gemm_epilogue = 0;
+    t.attn16_short = 1;
     return t;
 }
 static ortk_tuning g_tuning = tuning_defaults();
@@ -41,7 +42,8 @@ extern "C" int ortk_set_tuning(const ortk_tuning* t) {
     if (!in(t->attn_impl, 0, 4) || t->attn16_min_lq < 1 || !in(t->f32_split, 0, 7) || t->wgrad_wgs < 1 ||
         !in(t->wgrad_group, 0, 15) || !in(t->wgrad_group_splitk, 0, 8) || t->wgrad_group_wgs < 1 || !in(t->wgrad_group_tail, 0, 1) ||
         !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 15) || (t->ln_fuse & 2) /* bit 1: the 128-row backward panels, removed */ ||
-        !in(t->samp_epilogue, 0, 1) || !in(t->gemm_epilogue, 0, 3)) return ORTK_EINVAL;
+        !in(t->samp_epilogue, 0, 1) || !in(t->gemm_epilogue, 0, 3) ||
+        !(in(t->attn16_short, 0, 1) || t->attn16_short == 4 || t->attn16_short == 8)) return ORTK_EINVAL;
     ortk::g_tuning = *t;
     return 0;
 }
