@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 14    /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 15    /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -389,6 +389,13 @@ typedef struct ortk_tuning {
                                      of the training step) run the one-wave-per-(group, head) kernels of ortk_attn16.hip, four waves per workgroup
                                      | 0: the one-workgroup-per-(group, head) kernels everywhere (A/B; the results are bit-identical) | 4, 8: as 1 with
                                      that many waves per workgroup (measurement: profiles/attn16_short.txt) */
+    int32_t attn16_block;         /* 1 (default): bf16-input attention blocks of at most 96 query rows and 64 keys that the short kernels do not take (the
+                                     encoder's self-attention and the decoder's cross-attention of the training step) run the second mapping of the block
+                                     kernels (attn16b_*: three waves per workgroup, up to two query tiles per wave, the K image's bytes reused for the P images in
+                                     the forward, V / dO row fragments from global memory and one shared image for K, Q and dO in the backward: 16 KB and
+                                     27-41 KB of LDS per workgroup instead of 23-30 and 53-71; biased blocks of more than 48 query rows stay with the others)
+                                     | 0: the one-wave-per-query-tile kernels everywhere (A/B; the results are bit-identical; measurement:
+                                     profiles/attn16_block.txt) */
 } ortk_tuning;
 void ortk_get_tuning(ortk_tuning* out);
 int ortk_set_tuning(const ortk_tuning* t);

@@ -113,7 +113,7 @@ class OptimArgs(C.Structure):
 class Tuning(C.Structure):
     _fields_ = [("gemm_t64", C.c_int32), ("attn_impl", C.c_int32), ("attn16_min_lq", C.c_int32),
                 ("side_stream", C.c_int32), ("row_chain", C.c_int32), ("chain_wide", C.c_int32), ("spmm_alias", C.c_int32), ("f32_split", C.c_int32), ("wgrad_wgs", C.c_int32),
-                ("wgrad_group", C.c_int32), ("wgrad_group_splitk", C.c_int32), ("wgrad_group_wgs", C.c_int32), ("wgrad_group_tail", C.c_int32), ("feats_bf16", C.c_int32), ("ln_fuse", C.c_int32), ("samp_epilogue", C.c_int32), ("gemm_epilogue", C.c_int32), ("attn16_short", C.c_int32)]
+                ("wgrad_group", C.c_int32), ("wgrad_group_splitk", C.c_int32), ("wgrad_group_wgs", C.c_int32), ("wgrad_group_tail", C.c_int32), ("feats_bf16", C.c_int32), ("ln_fuse", C.c_int32), ("samp_epilogue", C.c_int32), ("gemm_epilogue", C.c_int32), ("attn16_short", C.c_int32), ("attn16_block", C.c_int32)]
 
 
 MAX_BEAM = 32      # include/ortk.h: ORTK_MAX_BEAM
@@ -271,7 +271,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 14   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 15   # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -21,9 +21,10 @@
 //     rows / columns of the images.
 // The pitch of 72 bf16 (144 B) makes the 16 rows of a ds_read_b128 service group fall on 16 distinct 16-byte slots.
 //
-// Two mappings of ONE per-tile code (fwd16_tile, bwd16_tile1, bwd16_tile2; bit-identical results): the block kernels
-// (attn16_fwd_kernel / attn16_bwd_kernel: a workgroup per (group, head), a wave per 16-row query tile) for those block shapes,
-// and the short kernels (attn16s_*: a WAVE per (group, head), bf16 inputs, at most 32 query rows and 32 keys) for the decoder's
+// Three mappings of ONE per-tile code (fwd16_tile, bwd16_tile1, bwd16_tile2; bit-identical results): the block kernels
+// (attn16_fwd_kernel / attn16_bwd_kernel: a workgroup per (group, head), a wave per 16-row query tile; every served shape and
+// fp32 inputs), their second mapping for those block shapes with bf16 inputs (attn16b_*: three waves, up to two query tiles per
+// wave, half the LDS per workgroup and so more workgroups per compute unit; ortk_tuning.attn16_block), and the short kernels (attn16s_*: a WAVE per (group, head), bf16 inputs, at most 32 query rows and 32 keys) for the decoder's
 // causal self-attention, where a workgroup's second wave owned one query row or none (ortk_tuning.attn16_short).
 #include <cstdlib>
 #include "ortk_internal.h"
@@ -358,6 +359,130 @@ static size_t fwd16_lds(int njt, int nw, int dk) {
     return ((size_t)(16 * njt + key_kj(njt)) * (dk + 8) + (size_t)16 * nw * key_pj(njt)) * sizeof(__bf16) + 128 * sizeof(float);
 }
 
+// The second mapping of the block kernels (ortk_tuning.attn16_block; bf16 Q / K / V, at most 64 keys and 96 query rows): still a
+// workgroup per (group, head), but sized by how many of them a compute unit holds side by side, not by one wave per query tile.
+// A workgroup is one latency chain (offsets -> global loads -> LDS images -> barrier -> MFMA, soft-max, MFMA -> stores); 2 048 of
+// them run in rounds, and LDS sets the round size.  Three waves whatever Lq: wave w runs query tiles w and, past 48 rows, w + 3
+// (one P image, reused behind a wsync(); a tile with no row of a ragged group is skipped).  The K image lives only until every wave
+// has taken its row fragments into registers; behind one more barrier its bytes are the three P images, so LDS holds the V image,
+// that region and the key mask: 16 384 B at 36 keys and dk = 64 (23 552 / 30 464 B in attn16_fwd_kernel).  K goes through LDS and
+// not straight into fragments (as in the short kernel) because 24 more registers in flight beside the V, Q and bias loads do not
+// fit the 80 of 6 waves per SIMD.  Every global load is issued before the first wait.
+constexpr int NWB = 3, NTB = 64 * NWB;          // waves / threads per workgroup of the attn16b kernels
+// The workgroup's share of a ROWS-row image: rows [0, rows) of a bf16 matrix slice into registers, zero past the count; then rows
+// [0, rows_st) into the image (pitch DKT + 8).  Split in two like stage32_ld / stage32_st.
+template <int DKT, int ROWS> struct StageB { static constexpr int N = (ROWS * (DKT / 8) + NTB - 1) / NTB; };      // 16-byte pieces per thread
+template <int DKT, int ROWS, int N = StageB<DKT, ROWS>::N>
+__device__ __forceinline__ void stageb_ld(bf16x8 (&v)[N], const __bf16* src, int64_t ld, int rows, int tid) {
+    constexpr int CPR = DKT / 8;
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int idx = tid + NTB * n, r = idx / CPR, c = (idx % CPR) * 8;
+        v[n] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        if (r < rows) v[n] = *reinterpret_cast<const bf16x8*>(src + ((unsigned)r * (unsigned)ld + (unsigned)c));
+    }
+}
+// ld_row_frags with the same addressing (a uniform base and a 32-bit offset per lane: one address register per load, not two)
+template <int NJT, int NKS>
+__device__ __forceinline__ void ld_row_fragsb(RegRowFrags<NJT, NKS>& out, const __bf16* src, int64_t ld, int rows, int lane) {
+    const int lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            out.f[jt][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            if (16 * jt + lr < rows) out.f[jt][ks] = ld_frag(src + ((unsigned)(16 * jt + lr) * (unsigned)ld + (unsigned)(32 * ks + 8 * lq)));
+        }
+}
+template <int DKT, int ROWS, int N = StageB<DKT, ROWS>::N>
+__device__ __forceinline__ void stageb_st(__bf16* img, const bf16x8 (&v)[N], int rows_st, int tid) {
+    constexpr int CPR = DKT / 8;
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        const int idx = tid + NTB * n, r = idx / CPR, c = (idx % CPR) * 8;
+        if (r < rows_st) *reinterpret_cast<bf16x8*>(img + r * (DKT + 8) + c) = v[n];
+    }
+}
+// (registers: 6 waves per SIMD = 8 workgroups per compute unit; 4 key tiles at dk = 64 do not fit 80 registers and get 128)
+template <int NJT, int DKT, int TPW>
+__global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(NJT * DKT > 192 ? 4 : 6))) void attn16b_fwd_kernel(ortk_attn_args a) {
+    static_assert(NJT <= 4 && TPW <= 2, "at most 64 keys and 96 query rows");
+    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32, KJ = KeyGeo<NJT>::KJ, PJ = KeyGeo<NJT>::PJ;
+    const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
+    extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
+    const int Lk = a.Lk, Lq = a.Lq;
+    constexpr int KP = 16 * NJT * PD > NWB * 16 * PJ ? 16 * NJT * PD : NWB * 16 * PJ;       // the K image, then the P images
+    __bf16* sV = sm16;                                         // [KJ][PD]      rows = key, zero-padded
+    __bf16* sK = sV + KJ * PD;                                 // [16*NJT][PD]  rows = key: on its way into every wave's row fragments
+    __bf16* sP = sK + wave * 16 * PJ;                          // [16][PJ]      then this wave's dropped P of the current tile
+    float* sMask = reinterpret_cast<float*>(sK + KP);          // [64]
+    const int lr = lane & 15, lq = lane >> 4;
+    int64_t qrow0 = (int64_t)g * Lq;
+    int Lqg = Lq;
+    if (a.q_off) {                                  // both entries in one round trip
+        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
+        qrow0 = o0; Lqg = min(Lq, o1 - o0);
+    }
+    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
+    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    // ---- every global load of the workgroup
+    bf16x8 vreg[StageB<DKT, KJ>::N];
+    stageb_ld<DKT, KJ>(vreg, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, tid);
+    float mk = -1.f;                                // -1: padded key
+    if (tid < Lkg) mk = a.kmask ? a.kmask[krow0 + tid] : 1.f;                    // (Lkg <= 64: threads 0 .. 63 are stored)
+    bf16x8 kreg[StageB<DKT, 16 * NJT>::N];
+    stageb_ld<DKT, 16 * NJT>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, tid);
+    bf16x8 qf[TPW][NKS];
+    float4 bias4[TPW][NJT];
+    int64_t prow[TPW], drow[TPW];
+    bool iv[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        const int i = (wave + NWB * t) * 16 + lr;
+        iv[t] = i < Lqg;
+        prow[t] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
+        drow[t] = prow[t];
+        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[t])
+            drow[t] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        if (iv[t]) {
+            const __bf16* qp = aq + qrow0 * a.ldq + h * DK + ((unsigned)i * (unsigned)a.ldq + (unsigned)(8 * lq));
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = ld_frag(qp + 32 * ks);
+        }
+        ld_keys4<NJT>(bias4[t], a.bias, TPW == 1 && a.bias && iv[t], prow[t], Lk, lq);      // (two tiles per wave: no bias, see block_b)
+    }
+    // ---- the images
+    stageb_st<DKT, KJ>(sV, vreg, KJ, tid);
+    stageb_st<DKT, 16 * NJT>(sK, kreg, 16 * NJT, tid);
+    if (tid < 64) sMask[tid] = mk;
+    __syncthreads();
+    // every wave takes the whole of K as row fragments (what LdsRowFrags would read tile by tile), then the image's bytes are the P images
+    RegRowFrags<NJT, NKS> kf;
+#pragma unroll
+    for (int jt = 0; jt < NJT; ++jt)
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) kf.f[jt][ks] = frag_row<PD>(sK, 16 * jt + lr, 32 * ks + 8 * lq);
+    __syncthreads();
+    // (key columns 16*NJT .. KJ-1 of the P image are never written by a tile)
+    for (int idx = lane; idx < 16 * (KJ / 4); idx += 64)
+        *reinterpret_cast<bf16x4*>(sP + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+    const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        const int i0 = (wave + NWB * t) * 16;
+        if (i0 >= Lqg) break;                       // a tile with no row of the group stores nothing
+        if (t) wsync();                             // this tile overwrites the P image
+        fwd16_tile<NJT, DKT, PJ>(a, kf, qf[t], bias4[t], sMask, sV, sP, lane, i0 + lr, iv[t], prow[t], drow[t], qrow0 + i0 + lr, h, inv_keep);
+    }
+}
+static size_t fwd16b_lds(int njt, int dk) {
+    return ((size_t)key_kj(njt) * (dk + 8) + std::max((size_t)16 * njt * (dk + 8), (size_t)16 * NWB * key_pj(njt))) * sizeof(__bf16) + 64 * sizeof(float);
+}
+
 // ------------------------------------------------------------------------------------------------ backward
 // Phase 1 (wave = 16-row query tile): dP^T = V dO^T, dS = P (dP - rowsum(P dP)), dQ = dS K / sqrt(dk); dS / sqrt(dk) and the
 // dropped P go to workgroup-wide images.  Phase 2 (the 2 x NJT x 4 output tiles shared by the waves): dK = dS^T Q / sqrt(dk),
@@ -583,6 +708,90 @@ static size_t bwd16_lds(int njt, int Lqp, int dk) {
     return ((size_t)(key_kj(njt) + 16 * njt + 2 * Lqp) * (dk + 8) + (size_t)2 * Lqp * key_pj(njt)) * sizeof(__bf16);
 }
 
+// The second mapping of the block backward (see attn16b_fwd_kernel): the layout of attn16s_bwd_kernel, workgroup-wide.  V and dO
+// reach dP^T = V dO^T as row fragments straight from global memory; LDS holds the dS / P images of the group and ONE
+// [max(KJ, Lqp)][PD] image for the operand a transposing read needs next: K for dQ, then Q for the dK tiles, then dO for the dV
+// tiles (Q and dO wait in the registers their loads filled; the hand-overs are workgroup barriers): 27 648 B for 36 x 36 and
+// 41 472 B for 85 x 36 at dk = 64 (52 992 / 71 424 B in attn16_bwd_kernel).  Phase 2 stops its k loop at the last 32-row block
+// that holds a row of the group (zero rows add +0 to an accumulator that started at +0: the same bits).
+template <int NJT, int DKT, int TPW>
+__global__ __launch_bounds__(NTB) void attn16b_bwd_kernel(ortk_attn_args a, int Lqp) {
+    static_assert(NJT <= 4 && TPW <= 2, "at most 64 keys and 96 query rows");
+    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32, KJ = KeyGeo<NJT>::KJ, PJ = KeyGeo<NJT>::PJ;
+    constexpr int LQM = TPW == 1 ? 64 : 96;         // Lqp of the instance's longest query block (48 | 96 rows)
+    const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
+    const __bf16* ag = reinterpret_cast<const __bf16*>(a.d_o);
+    extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
+    const int Lk = a.Lk, Lq = a.Lq;
+    __bf16* sX = sm16;                              // [max(KJ, Lqp)][PD]  K (rows = key), then Q, then dO (rows = query); zero-padded
+    __bf16* sS = sX + max(KJ, Lqp) * PD;            // [Lqp][PJ]           dS / sqrt(dk)
+    __bf16* sD = sS + Lqp * PJ;                     // [Lqp][PJ]           dropped P
+    const int lr = lane & 15, lq = lane >> 4;
+    int64_t qrow0 = (int64_t)g * Lq;
+    int Lqg = Lq;
+    if (a.q_off) {
+        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
+        qrow0 = o0; Lqg = min(Lq, o1 - o0);
+    }
+    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
+    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    // ---- every global load of the workgroup: what phase 1 consumes from registers first, then the three staged images
+    RegRowFrags<NJT, NKS> vf;
+    ld_row_fragsb<NJT, NKS>(vf, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
+    bf16x8 gf[TPW][NKS];
+    float4 praw[TPW][NJT];
+    int64_t prow[TPW], drow[TPW];
+    bool iv[TPW];
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        const int i = (wave + NWB * t) * 16 + lr;
+        iv[t] = i < Lqg;
+        prow[t] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
+        drow[t] = prow[t];
+        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[t])
+            drow[t] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) gf[t][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};        // (a zero row of the dO image)
+        if (iv[t]) {
+            const __bf16* gp = ag + qrow0 * a.lddo + h * DK + ((unsigned)i * (unsigned)a.lddo + (unsigned)(8 * lq));
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) gf[t][ks] = ld_frag(gp + 32 * ks);
+        }
+        ld_keys4<NJT>(praw[t], a.p, iv[t], prow[t], Lk, lq);
+    }
+    bf16x8 kreg[StageB<DKT, KJ>::N], qreg[StageB<DKT, LQM>::N], greg[StageB<DKT, LQM>::N];
+    stageb_ld<DKT, KJ>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, tid);
+    stageb_ld<DKT, LQM>(qreg, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, tid);
+    stageb_ld<DKT, LQM>(greg, ag + qrow0 * a.lddo + h * DK, a.lddo, Lqg, tid);
+    // ---- the images.  dS / P: key columns 16*NJT .. KJ-1 and the rows of a tile that is not run stay zero
+    for (int idx = tid; idx < 2 * Lqp * PJ / 8; idx += NTB)
+        *reinterpret_cast<bf16x8*>(sS + idx * 8) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};           // sD follows sS
+    stageb_st<DKT, KJ>(sX, kreg, KJ, tid);
+    __syncthreads();
+    const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
+#pragma unroll
+    for (int t = 0; t < TPW; ++t) {
+        const int i0 = (wave + NWB * t) * 16;
+        if (i0 >= Lqg) break;                       // a tile with no row of the group: zero rows of dS / P, nothing stored
+        bwd16_tile1<NJT, DKT, PJ>(a, vf, gf[t], praw[t], sX, sS, sD, lane, i0 + lr, iv[t], prow[t], drow[t], qrow0 + i0 + lr, h, inv_keep);
+    }
+    // phase 2: tile (which, jt, dt); which = 0 the dK tiles (dS, Q), 1 the dV tiles (dropped P, dO), shared by the waves
+    constexpr int NT2 = NJT * (DK / 16);
+    const int Lq2 = min(Lqp, (Lqg + 31) & ~31);
+#pragma unroll
+    for (int which = 0; which < 2; ++which) {
+        __syncthreads();                            // the image's readers (dQ; the dK tiles) are done, and dS / P are whole
+        stageb_st<DKT, LQM>(sX, which == 0 ? qreg : greg, Lqp, tid);
+        __syncthreads();
+        for (int t = wave; t < NT2; t += NWB) bwd16_tile2<NJT, DKT, PJ>(a, which * NT2 + t, sS, sD, sX, sX, Lq2, lane, Lkg, krow0, h);
+    }
+}
+static size_t bwd16b_lds(int njt, int Lqp, int dk) {
+    return ((size_t)std::max(key_kj(njt), Lqp) * (dk + 8) + (size_t)2 * Lqp * key_pj(njt)) * sizeof(__bf16);
+}
+
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -636,6 +845,24 @@ static int short_waves(const ortk_attn_args* a) {
     if (!sw || a->qkv_dtype != 1 || a->Lq > 32 || a->Lk > 32) return 0;
     return sw == 8 ? 8 : 4;
 }
+// The second mapping of the block kernels (attn16b_*): bf16 Q / K / V / dO, at most 64 keys and 96 query rows, where the short
+// kernels do not apply (ortk_tuning.attn16_block: 1 | 0 the one-wave-per-query-tile kernels).  A biased block of more than 48 query
+// rows stays with those too: the two bias rows of a wave that runs two tiles do not fit its registers, and the step has no such block.
+static bool block_b(const ortk_attn_args* a) {
+    return ortk::tuning().attn16_block && a->qkv_dtype == 1 && a->Lk <= 64 && a->Lq <= 16 * NWB * 2 && (a->Lq <= 16 * NWB || !a->bias);
+}
+template <int DKT, int TPW> static fwd16_fn pick_fwd_b(int njt) {
+    switch (njt) {
+        case 1: return attn16b_fwd_kernel<1, DKT, TPW>; case 2: return attn16b_fwd_kernel<2, DKT, TPW>;
+        case 3: return attn16b_fwd_kernel<3, DKT, TPW>; default: return attn16b_fwd_kernel<4, DKT, TPW>;
+    }
+}
+template <int DKT, int TPW> static bwd16_fn pick_bwd_b(int njt) {
+    switch (njt) {
+        case 1: return attn16b_bwd_kernel<1, DKT, TPW>; case 2: return attn16b_bwd_kernel<2, DKT, TPW>;
+        case 3: return attn16b_bwd_kernel<3, DKT, TPW>; default: return attn16b_bwd_kernel<4, DKT, TPW>;
+    }
+}
 template <typename FN> static int launch_short(FN fn, size_t wave_bytes, int W, const ortk_attn_args* a, hipStream_t s) {
     const size_t lds = wave_bytes * W;
     const int64_t pairs = (int64_t)a->nkv * a->H;
@@ -652,6 +879,12 @@ int attn16_fwd(const ortk_attn_args* a, hipStream_t s) {
         return launch_short(fn, (a->dk == 64 ? fwd16s_wave_elems<64>() : fwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
     }
     const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16;
+    if (block_b(a)) {                               // nw query tiles on NWB waves: one each, or two
+        const fwd16_fn fn = a->dk == 64 ? (nw <= NWB ? pick_fwd_b<64, 1>(njt) : pick_fwd_b<64, 2>(njt)) : (nw <= NWB ? pick_fwd_b<32, 1>(njt) : pick_fwd_b<32, 2>(njt));
+        hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(NTB), fwd16b_lds(njt, a->dk), s, *a);
+        ORTK_CHECK_LAUNCH();
+        return 0;
+    }
     const fwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_fwd<__bf16, 64>(njt) : pick_fwd<float, 64>(njt))
                                     : (a->qkv_dtype ? pick_fwd<__bf16, 32>(njt) : pick_fwd<float, 32>(njt));
     const size_t lds = fwd16_lds(njt, nw, a->dk);
@@ -668,6 +901,12 @@ int attn16_bwd(const ortk_attn_args* a, hipStream_t s) {
         return launch_short(fn, (a->dk == 64 ? bwd16s_wave_elems<64>() : bwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
     }
     const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16, Lqp = (int)ortk_align(a->Lq, 32);
+    if (block_b(a)) {
+        const bwd16_fn fn = a->dk == 64 ? (nw <= NWB ? pick_bwd_b<64, 1>(njt) : pick_bwd_b<64, 2>(njt)) : (nw <= NWB ? pick_bwd_b<32, 1>(njt) : pick_bwd_b<32, 2>(njt));
+        hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(NTB), bwd16b_lds(njt, Lqp, a->dk), s, *a, Lqp);
+        ORTK_CHECK_LAUNCH();
+        return 0;
+    }
     const bwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_bwd<__bf16, 64>(njt) : pick_bwd<float, 64>(njt))
                                     : (a->qkv_dtype ? pick_bwd<__bf16, 32>(njt) : pick_bwd<float, 32>(njt));
     const size_t lds = bwd16_lds(njt, Lqp, a->dk);

@@ -28,6 +28,7 @@ static ortk_tuning tuning_defaults() {
     t.samp_epilogue = 1;
     t.gemm_epilogue = 0;
     t.attn16_short = 1;
+    t.attn16_block = 1;
     return t;
 }
 static ortk_tuning g_tuning = tuning_defaults();
@@ -43,7 +44,7 @@ extern "C" int ortk_set_tuning(const ortk_tuning* t) {
         !in(t->wgrad_group, 0, 15) || !in(t->wgrad_group_splitk, 0, 8) || t->wgrad_group_wgs < 1 || !in(t->wgrad_group_tail, 0, 1) ||
         !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 15) || (t->ln_fuse & 2) /* bit 1: the 128-row backward panels, removed */ ||
         !in(t->samp_epilogue, 0, 1) || !in(t->gemm_epilogue, 0, 3) ||
-        !(in(t->attn16_short, 0, 1) || t->attn16_short == 4 || t->attn16_short == 8)) return ORTK_EINVAL;
+        !(in(t->attn16_short, 0, 1) || t->attn16_short == 4 || t->attn16_short == 8) || !in(t->attn16_block, 0, 1)) return ORTK_EINVAL;
     ortk::g_tuning = *t;
     return 0;
 }
