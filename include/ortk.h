@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 15    /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 16   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -761,6 +761,15 @@ typedef struct ortk_attn_args {
 } ortk_attn_args;
 int ortk_attention_fwd(const ortk_attn_args* a, ortk_stream stream);
 int ortk_attention_bwd(const ortk_attn_args* a, ortk_stream stream);
+/* Which kernels ortk_attention_fwd(a) (bwd = 0) or ortk_attention_bwd(a) (bwd != 0) would launch: launches nothing, returns the code
+ * the operator would return for these arguments (ORTK_EINVAL included) and on success writes to buf (buf_bytes with the terminator)
+ * the launches in stream order.  Two codes of its own, for arguments the operator accepts: ORTK_EINVAL for a NULL buf or
+ * buf_bytes <= 0, ORTK_ENOSPC for a buf too short (left untouched).  The launches are separated by ';': each is the kernel's family
+ * (the name without attn_ / _kernel) and template instance (element types as f32 / bf16), its workgroup size and its dynamic LDS
+ * bytes, e.g. "kv_append:wg=256:lds=0;small_fwd<1,3,bf16>:wg=256:lds=0" or "attn16b_fwd<3,64,1>:wg=192:lds=16384".  An empty
+ * string: nothing is launched (nkv = 0, or bwd_part = 2 where part 1 did everything).  Built by the code that builds the operator's
+ * own plan, under the ortk_tuning values of the moment; pointers are tested for alignment only, never dereferenced (no device needed). */
+int ortk_attention_plan(const ortk_attn_args* a, int32_t bwd, char* buf, int32_t buf_bytes);
 
 /* InputEmbedding + PositionalEncoding (transformer.py:383-401): out[r*T+t] = lut[tok]*sqrt(d) + pe[t0+t], dropout.
  * Also emits keymask[r*T+t] = (tok != pad). */

@@ -227,6 +227,7 @@ SIGNATURES = {
     "ortk_box_embedding": (_I32, [_P, C.POINTER(_F), _P, _I32, _I32, _P]),
     "ortk_attention_fwd": (_I32, [C.POINTER(AttnArgs), _P]),
     "ortk_attention_bwd": (_I32, [C.POINTER(AttnArgs), _P]),
+    "ortk_attention_plan": (_I32, [C.POINTER(AttnArgs), _I32, C.c_char_p, _I32]),
     "ortk_valid_position_tables": (_I32, [_P, _I32, _I32, _P, _P, _P]),
     "ortk_embed_fwd": (_I32, [_P, _I64, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _F, _U32, _P]),
     "ortk_embed_bwd": (_I32, [_P, _I64, _P, _P, _I64, _I32, _I32, _F, _U32, _P]),
@@ -271,7 +272,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 15   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 16   # include/ortk.h: ORTK_VERSION
 
 
 def lib():
@@ -313,6 +314,15 @@ def gemm_plan(args):
     OrtkError where ortk_gemm would refuse the arguments.  Launches nothing and needs no device."""
     buf = C.create_string_buffer(256)
     check(lib().ortk_gemm_plan(C.byref(args), buf, len(buf)), "ortk_gemm_plan")
+    return [k for k in buf.value.decode().split(";") if k]
+
+
+def attention_plan(args, bwd=False):
+    """The launches ortk_attention_fwd(args) — bwd: ortk_attention_bwd(args) — would make, as a list of strings
+    ``family<instance>:wg=<workgroup size>:lds=<dynamic LDS bytes>`` (include/ortk.h: ortk_attention_plan); raises OrtkError where the
+    operator would refuse the arguments.  Launches nothing and needs no device."""
+    buf = C.create_string_buffer(256)
+    check(lib().ortk_attention_plan(C.byref(args), int(bool(bwd)), buf, len(buf)), "ortk_attention_plan")
     return [k for k in buf.value.decode().split(";") if k]
 
 

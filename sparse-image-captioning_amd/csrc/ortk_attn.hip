@@ -11,7 +11,9 @@
 // cross attention that is all captions of one image (5 x 17 rows), so the encoder memory's K/V are read once
 // per image instead of once per caption (the reference repeats them, relation_transformer.py:63-66), and in
 // the backward dK/dV of an image are complete inside one workgroup (no atomics to global memory).
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "ortk_internal.h"
 
 namespace {
@@ -1093,22 +1095,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(ortk_attn_args a) {
     }
 }
 
-int check(const ortk_attn_args* a) {
-    if (!a || !a->q || !a->k || !a->v) return ORTK_EINVAL;
-    if (a->Lk < 1 || a->Lk > MAXK || a->dk < 1 || a->dk > MAXD || a->Lq < 1 || a->H < 1 || a->nkv < 0) return ORTK_EINVAL;
-    if (a->drop_p < 0.f || a->drop_p >= 1.f) return ORTK_EINVAL;
-    return 0;
-}
-
-// the register-only kernels: training-time short sequences (decode steps with 1-8 query rows keep their own kernels)
-bool small_ok(const ortk_attn_args* a) {
-    return a->dk == 64 && a->Lq <= 32 && a->Lk <= 32 && a->Lq >= 9 && !a->kv_index;
-}
-// forward only: also the decode-time cross-attention (1-8 beams of an image x 36 regions: up to 3 key tiles)
-bool small_fwd_ok(const ortk_attn_args* a) {
-    return a->dk == 64 && a->Lq <= 32 && a->Lk <= 48 && !a->kv_index && (a->Lq >= 9 || a->Lk > 8);
-}
-
 }  // namespace
 
 // cache append for the kernels that do not do it themselves (k_new / v_new): one thread per element of the new rows
@@ -1124,167 +1110,186 @@ __global__ void attn_kv_append_kernel(ortk_attn_args a) {
     }
 }
 
-// bf16 K / V storage (kv_dtype = 1) is served by the two decode-time kernels only; ortk_attention_kv16_ok tells the
-// executor whether a shape qualifies before it lays its caches out as bf16
-static bool kv16_ok(const ortk_attn_args* a) {
-    const bool rowdec = a->Lq == 1 && a->H == 8 && a->dk == 64 && a->Lk <= 32 && a->causal_period == 0 && a->drop_p == 0.f && !a->bias;
-    const bool small = a->dk == 64 && a->Lq <= 16 && a->Lk <= 48 && !a->kv_index && (a->Lq >= 9 || a->Lk > 8) && !rowdec;
-    return (rowdec || small) && a->ldk % 8 == 0 && a->ldv % 8 == 0 && attn_impl() == 0;
+// ------------------------------------------------------------------------------------------------ host side: validate -> plan -> launch
+namespace {
+using ortk::aligned16; using ortk::ld_multiple; using ortk::AttnInst; using ortk::AttnPlan;
+typedef float f32; typedef __bf16 bf16;      // element types as the instance names spell them
+#define INST(...) ORTK_ATTN_INST(attn_, __VA_ARGS__)
+#define INST0(family) ORTK_ATTN_INST0(attn_, family)
+
+constexpr size_t LDS_MAX = 160 * 1024;
+constexpr size_t wave_lds(int Lk, int extra) { return sizeof(float) * 4 * ((size_t)2 * Lk * KP + extra); }      // the wave kernels: 4 pairs
+
+// The instances a runtime index picks.  (attn_bwd_wave_kernel<32> fits the default dynamic-LDS limit.)
+const AttnInst ROWDEC[4][2] = {{INST(rowdec, 8,f32), INST(rowdec, 8,bf16)}, {INST(rowdec, 16,f32), INST(rowdec, 16,bf16)},       // [(Lk - 1) / 8][kv_dtype]
+                               {INST(rowdec, 24,f32), INST(rowdec, 24,bf16)}, {INST(rowdec, 32,f32), INST(rowdec, 32,bf16)}};
+const AttnInst SMALL_FWD[3][3] = {{INST(small_fwd, 1,1,f32), INST(small_fwd, 1,2,f32), INST(small_fwd, 1,3,f32)},                // [query tiles - 1, or 2: bf16 K / V][key tiles - 1]
+                                  {INST(small_fwd, 2,1,f32), INST(small_fwd, 2,2,f32), INST(small_fwd, 2,3,f32)},
+                                  {INST(small_fwd, 1,1,bf16), INST(small_fwd, 1,2,bf16), INST(small_fwd, 1,3,bf16)}};
+const AttnInst SMALL_BWD[2][2] = {{INST(small_bwd, 1,1), INST(small_bwd, 1,2)}, {INST(small_bwd, 2,1), INST(small_bwd, 2,2)}};    // [query tiles - 1][key tiles - 1]
+const struct { AttnInst k; size_t lds_limit; } BWD_WAVE[3] = {{INST(bwd_wave, 32), 0}, {INST(bwd_wave, 48), wave_lds(48, 192)}, {INST(bwd_wave, 64), wave_lds(64, 192)}};
+AttnInst fwd_mfma_inst(int Lkp, int DKP) {
+    if (DKP == 64 && Lkp == 48) return INST(fwd_mfma, 48,64);
+    if (DKP == 64 && Lkp == 32) return INST(fwd_mfma, 32,64);
+    if (DKP == 64 && Lkp == 64) return INST(fwd_mfma, 64,64);
+    return INST(fwd_mfma, 0,0);
+}
+AttnInst bwd_mfma_inst(int Lkp, int DKP, int Lqp, int part) {
+    const bool k48 = DKP == 64 && Lkp == 48;
+    if (part == 1) return k48 && Lqp == 96 ? INST(bwd_mfma, 48,64,96,1) : INST(bwd_mfma, 0,0,0,1);
+    if (part == 2) return k48 && Lqp == 96 ? INST(bwd_mfma, 48,64,96,2) : INST(bwd_mfma, 0,0,0,2);
+    if (k48 && Lqp == 48) return INST(bwd_mfma, 48,64,48,0);
+    if (k48 && Lqp == 96) return INST(bwd_mfma, 48,64,96,0);
+    if (DKP == 64 && Lkp == 32 && Lqp == 32) return INST(bwd_mfma, 32,64,32,0);
+    return INST(bwd_mfma, 0,0,0,0);
 }
 
-extern "C" int ortk_attention_fwd(const ortk_attn_args* a_in, ortk_stream stream) {
-    if (int e = check(a_in)) return e;
-    if (!a_in->o) return ORTK_EINVAL;
-    if (a_in->nkv == 0) return 0;
-    if (a_in->kv_dtype != 0 && (a_in->kv_dtype != 1 || !kv16_ok(a_in))) return ORTK_EINVAL;
-    ortk_attn_args a_local = *a_in;
-    ortk_attn_args* a = &a_local;
-    if ((a->k_new != nullptr) != (a->v_new != nullptr)) return ORTK_EINVAL;
-    if (a->k_new && (a->Lq != 1 || a->ld_new < (int64_t)a->H * a->dk)) return ORTK_EINVAL;
-    if (a->k_new) {
-        const bool rowdec = a->H == 8 && a->dk == 64 && a->Lk <= 32 && a->causal_period == 0 && a->drop_p == 0.f && !a->bias &&
-                            a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->ldo % 4 == 0 && a->ld_new % 4 == 0 && attn_impl() == 0 &&
-                            ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-                              reinterpret_cast<uintptr_t>(a->o) | reinterpret_cast<uintptr_t>(a->k_new) | reinterpret_cast<uintptr_t>(a->v_new)) & 15) == 0;
-        if (!rowdec) {       // every other kernel: append first, then attend to the cache as usual
-            const int64_t n = (int64_t)a->nkv * a->H * a->dk;
-            hipLaunchKernelGGL(attn_kv_append_kernel, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(ortk_cdiv(n, 256), 2048))), dim3(256), 0,
-                               ortk_s(stream), *a);
-            ORTK_CHECK_LAUNCH();
-            a->k_new = a->v_new = nullptr;
-        }
+// ---- the predicates, each written once (shape, tuning switch, and the operands whose vector accesses need alignment)
+// Dispatch measured on the path's three shapes (scratch/attn_bench.py, us fwd/bwd): 36x36 MFMA 81/132 vs 82/147,
+// 85x36 MFMA 101/218 vs 170/293, 17x17 (10 240 tiny pairs) MFMA 200/526 vs 138/196 for the per-lane kernels.
+bool use_mfma(const ortk_attn_args& a) { return attn_impl() == 0 ? a.Lq > 32 : attn_impl() == 3; }
+// the cached self-attention of a decode step: one query row; also the only kernel that appends k_new / v_new itself.  One of the
+// two kernels that understand bf16 K / V (kv_dtype = 1), the other being attn_small_fwd_kernel.
+bool rowdec_ok(const ortk_attn_args& a) {
+    return a.Lq == 1 && a.H == 8 && a.dk == 64 && a.Lk <= 32 && a.causal_period == 0 && a.drop_p == 0.f && !a.bias && attn_impl() == 0 &&
+           ld_multiple(4, a.ldq, a.ldk, a.ldv, a.ldo) && aligned16(a.q, a.k, a.v, a.o) && (!a.kv_dtype || ld_multiple(8, a.ldk, a.ldv)) &&
+           (!a.k_new || (ld_multiple(4, a.ld_new) && aligned16(a.k_new, a.v_new)));
+}
+// the register-only kernels: training-time short sequences (decode steps with 1-8 query rows keep their own kernels) ...
+bool small_bwd_ok(const ortk_attn_args& a) {
+    return a.dk == 64 && a.Lq <= 32 && a.Lk <= 32 && a.Lq >= 9 && !a.kv_index && attn_impl() == 0 && ld_multiple(4, a.ldv, a.lddo) && aligned16(a.v, a.d_o);
+}
+// ... forward only: also the decode-time cross-attention (1-8 beams of an image x 36 regions: up to 3 key tiles); bf16 K / V for
+// the decode-time shapes (at most 16 query rows)
+bool small_fwd_ok(const ortk_attn_args& a) {
+    return a.dk == 64 && a.Lq <= 32 && a.Lk <= 48 && !a.kv_index && (a.Lq >= 9 || a.Lk > 8) && attn_impl() == 0 &&
+           ld_multiple(4, a.ldq, a.ldk, a.ldv) && aligned16(a.q, a.k, a.v) &&
+           (!a.kv_dtype || (a.Lq <= 16 && ld_multiple(8, a.ldk, a.ldv) && aligned16(a.o)));
+}
+
+int plan_fwd(const ortk_attn_args& a_in, AttnPlan& pl) {
+    if (!a_in.o) return ORTK_EINVAL;
+    if (a_in.nkv == 0) return 0;
+    if (a_in.kv_dtype != 0 && a_in.kv_dtype != 1) return ORTK_EINVAL;
+    if ((a_in.k_new != nullptr) != (a_in.v_new != nullptr)) return ORTK_EINVAL;
+    if (a_in.k_new && (a_in.Lq != 1 || a_in.ld_new < (int64_t)a_in.H * a_in.dk)) return ORTK_EINVAL;
+    ortk_attn_args a = a_in;
+    const int64_t pairs = (int64_t)a.nkv * a.H;
+    if (a.k_new && !rowdec_ok(a)) {       // every other kernel: append first, then attend to the cache as usual
+        pl.add(INST0(kv_append), std::max<int64_t>(1, std::min<int64_t>(ortk_cdiv(pairs * a.dk, 256), 2048)), 256, 0);
+        a.k_new = a.v_new = nullptr;
     }
-    if ((attn_impl() == 0 || a->qkv_dtype) && ortk::attn16_ok(a, false)) return ortk::attn16_fwd(a, ortk_s(stream));   // mixed precision
-    if (a->qkv_dtype || a->q_off) return ORTK_EINVAL;   // bf16 Q / K / V and ragged groups are only understood by the bf16-operand kernels
-    ortk::lds_attr(reinterpret_cast<const void*>(attn_fwd_kernel), fwd_lds_bytes(MAXK));
-    ortk::lds_attr(reinterpret_cast<const void*>(attn_fwd_wave_kernel), sizeof(float) * 4 * (2 * 64 * KP + 128));
-    if (a->drop_tf_T > 0) {      // teacher-forced dropout geometry (train-mode decode step): the generic kernel
-        if (a->kv_dtype || a->qkv_dtype || a->Lk > MAXK || a->dk > MAXD) return ORTK_EINVAL;
-        hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)(a->nkv * a->H)), dim3(256), fwd_lds_bytes(a->Lk), ortk_s(stream), *a);
-        ORTK_CHECK_LAUNCH();
+    if ((attn_impl() == 0 || a.qkv_dtype) && ortk::attn16_plan(a, false, pl)) return 0;      // mixed precision
+    if (a.qkv_dtype || a.q_off) return ORTK_EINVAL;   // bf16 Q / K / V and ragged groups are only understood by the bf16-operand kernels
+    if (a.drop_tf_T > 0) {      // teacher-forced dropout geometry (train-mode decode step): the generic kernel
+        if (a.kv_dtype) return ORTK_EINVAL;
+        pl.add(INST0(fwd), pairs, 256, fwd_lds_bytes(a.Lk), fwd_lds_bytes(MAXK));
         return 0;
     }
-    // Dispatch measured on the path's three shapes (scratch/attn_bench.py, us fwd/bwd): 36x36 MFMA 81/132 vs 82/147,
-    // 85x36 MFMA 101/218 vs 170/293, 17x17 (10 240 tiny pairs) MFMA 200/526 vs 138/196 for the per-lane kernels.
-    const bool use_mfma = attn_impl() == 0 ? a->Lq > 32 : attn_impl() == 3;
-    const bool vec_kq = (a->ldk % 4 == 0) && (a->ldq % 4 == 0) && (a->dk % 4 == 0) &&
-                        ((reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->q)) & 15) == 0;
-    const bool al16 = ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-                        reinterpret_cast<uintptr_t>(a->o)) & 15) == 0;
-    if (a->kv_dtype && !al16) return ORTK_EINVAL;
-    if (a->Lq == 1 && a->H == 8 && a->dk == 64 && a->Lk <= 32 && a->causal_period == 0 && a->drop_p == 0.f && !a->bias && al16 &&
-        a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->ldo % 4 == 0 && attn_impl() == 0) {
-        const dim3 rgrid((unsigned)ortk_cdiv(a->nkv, 4));
-#define ORTK_ROWDEC(LK) do { if (a->kv_dtype) hipLaunchKernelGGL((attn_rowdec_kernel<LK, __bf16>), rgrid, dim3(256), 0, ortk_s(stream), *a); \
-                             else             hipLaunchKernelGGL((attn_rowdec_kernel<LK, float>), rgrid, dim3(256), 0, ortk_s(stream), *a); } while (0)
-        if (a->Lk <= 8) ORTK_ROWDEC(8); else if (a->Lk <= 16) ORTK_ROWDEC(16); else if (a->Lk <= 24) ORTK_ROWDEC(24); else ORTK_ROWDEC(32);
-#undef ORTK_ROWDEC
-        ORTK_CHECK_LAUNCH();
+    if (rowdec_ok(a)) {
+        pl.add(ROWDEC[(a.Lk - 1) / 8][a.kv_dtype], ortk_cdiv(a.nkv, 4), 256, 0);
         return 0;
     }
-    // from here on only the register-only MFMA kernel understands bf16 K / V
-    if (a->kv_dtype && !(small_fwd_ok(a) && attn_impl() == 0 && a->ldv % 8 == 0 && a->ldq % 4 == 0 && a->ldk % 8 == 0 && al16))
-        return ORTK_EINVAL;
+    if (a.kv_dtype && !small_fwd_ok(a)) return ORTK_EINVAL;      // bf16 K / V: a call that neither of its two kernels serves is refused
+    const bool vec_kq = a.dk % 4 == 0 && ld_multiple(4, a.ldk, a.ldq) && aligned16(a.k, a.q);
     // measured on the 1024-image beam-5 decode: 95-105 us per call vs 75 us for the block kernel -> opt-in only (impl 4)
-    if (a->Lq <= 8 && a->Lk <= 64 && a->causal_period == 0 && a->drop_p == 0.f && vec_kq && attn_impl() == 4) {
-        const dim3 dgrid((unsigned)ortk_cdiv((int64_t)a->nkv * a->H, 4));
-        if (a->Lk <= 32) hipLaunchKernelGGL(attn_decode_kernel<32>, dgrid, dim3(256), 0, ortk_s(stream), *a);
-        else             hipLaunchKernelGGL(attn_decode_kernel<64>, dgrid, dim3(256), 0, ortk_s(stream), *a);
-    } else if (small_fwd_ok(a) && attn_impl() == 0 && a->ldv % 4 == 0 && a->ldq % 4 == 0 && a->ldk % 4 == 0 &&
-               ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v)) & 15) == 0) {
-        const dim3 sgrid((unsigned)ortk_cdiv((int64_t)a->nkv * a->H, 4));
-        const int nit = a->Lq > 16 ? 2 : 1, njt = (a->Lk + 15) / 16;
-#define ORTK_SMALL_FWD(NI, NJ, KT) hipLaunchKernelGGL((attn_small_fwd_kernel<NI, NJ, KT>), sgrid, dim3(256), 0, ortk_s(stream), *a)
-        if (a->kv_dtype) {   // bf16 K / V: decode-time shapes (at most 16 query rows)
-            if (nit != 1) return ORTK_EINVAL;
-            if (njt == 3) ORTK_SMALL_FWD(1, 3, __bf16); else if (njt == 2) ORTK_SMALL_FWD(1, 2, __bf16); else ORTK_SMALL_FWD(1, 1, __bf16);
-        } else if (nit == 2) { if (njt == 3) ORTK_SMALL_FWD(2, 3, float); else if (njt == 2) ORTK_SMALL_FWD(2, 2, float); else ORTK_SMALL_FWD(2, 1, float); }
-        else                 { if (njt == 3) ORTK_SMALL_FWD(1, 3, float); else if (njt == 2) ORTK_SMALL_FWD(1, 2, float); else ORTK_SMALL_FWD(1, 1, float); }
-#undef ORTK_SMALL_FWD
-    } else if (a->Lk <= 64 && use_mfma && vec_kq && a->ldv % 4 == 0 && (reinterpret_cast<uintptr_t>(a->v) & 15) == 0) {
+    if (a.Lq <= 8 && a.Lk <= 64 && a.causal_period == 0 && a.drop_p == 0.f && vec_kq && attn_impl() == 4) {
+        pl.add(a.Lk <= 32 ? INST(decode, 32) : INST(decode, 64), ortk_cdiv(pairs, 4), 256, 0);
+    } else if (small_fwd_ok(a)) {
+        pl.add(SMALL_FWD[a.kv_dtype ? 2 : a.Lq > 16][(a.Lk - 1) / 16], ortk_cdiv(pairs, 4), 256, 0);
+    } else if (a.Lk <= 64 && use_mfma(a) && vec_kq && ld_multiple(4, a.ldv) && aligned16(a.v)) {
         // MFMA form: one workgroup per pair, one wave per 16 query rows (at most 8 waves)
-        const int Lkp = (int)ortk_align(a->Lk, 16), DKP = (int)ortk_align(a->dk, 16);
-        const int nw = (int)std::min<int64_t>(8, ortk_cdiv(a->Lq, 16));
+        const int Lkp = (int)ortk_align(a.Lk, 16), DKP = (int)ortk_align(a.dk, 16);
+        const int nw = (int)std::min<int64_t>(8, ortk_cdiv(a.Lq, 16));
         const size_t lds = sizeof(float) * ((size_t)Lkp * (PK_ + PN_) + 64 + (size_t)nw * 16 * PK_ * 2);
-        ortk::lds_attr(reinterpret_cast<const void*>(attn_fwd_mfma_kernel<0, 0>), 160 * 1024);
-        ortk::lds_attr(reinterpret_cast<const void*>(attn_fwd_mfma_kernel<64, 64>), 160 * 1024);
-        const dim3 mgrid((unsigned)(a->nkv * a->H)), mblock(64 * nw);
-        if (DKP == 64 && Lkp == 48)      hipLaunchKernelGGL((attn_fwd_mfma_kernel<48, 64>), mgrid, mblock, lds, ortk_s(stream), *a, Lkp, DKP);
-        else if (DKP == 64 && Lkp == 32) hipLaunchKernelGGL((attn_fwd_mfma_kernel<32, 64>), mgrid, mblock, lds, ortk_s(stream), *a, Lkp, DKP);
-        else if (DKP == 64 && Lkp == 64) hipLaunchKernelGGL((attn_fwd_mfma_kernel<64, 64>), mgrid, mblock, lds, ortk_s(stream), *a, Lkp, DKP);
-        else                             hipLaunchKernelGGL((attn_fwd_mfma_kernel<0, 0>), mgrid, mblock, lds, ortk_s(stream), *a, Lkp, DKP);
-    } else if (a->Lk <= 64 && attn_impl() == 1) {
-        const int pairs = a->nkv * a->H;
-        hipLaunchKernelGGL(attn_fwd_wave_kernel, dim3((unsigned)ortk_cdiv(pairs, 4)), dim3(256),
-                           sizeof(float) * 4 * ((size_t)2 * a->Lk * KP + 128), ortk_s(stream), *a);
+        const bool big = !(DKP == 64 && (Lkp == 32 || Lkp == 48));      // the <64,64> and <0,0> instances can pass the default limit
+        pl.add(fwd_mfma_inst(Lkp, DKP), pairs, 64 * nw, lds, big ? LDS_MAX : 0, Lkp, DKP);
+    } else if (a.Lk <= 64 && attn_impl() == 1) {
+        pl.add(INST0(fwd_wave), ortk_cdiv(pairs, 4), 256, wave_lds(a.Lk, 128), wave_lds(64, 128));
     } else {
-        hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)(a->nkv * a->H)), dim3(256), fwd_lds_bytes(a->Lk), ortk_s(stream), *a);
+        pl.add(INST0(fwd), pairs, 256, fwd_lds_bytes(a.Lk), fwd_lds_bytes(MAXK));
     }
-    ORTK_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int ortk_attention_bwd(const ortk_attn_args* a, ortk_stream stream) {
-    if (int e = check(a)) return e;
-    if (a->kv_dtype != 0 || a->bwd_part < 0 || a->bwd_part > 2) return ORTK_EINVAL;
-    if (!a->p || !a->d_o || !a->dq || !a->d_k || !a->dv || a->kv_index || a->kv_group_stride) return ORTK_EINVAL;
-    if (a->nkv == 0) return 0;
-    if ((attn_impl() == 0 || a->qkv_dtype) && ortk::attn16_ok(a, true))     // mixed precision: one kernel does both parts
-        return a->bwd_part == 2 ? 0 : ortk::attn16_bwd(a, ortk_s(stream));
-    if (a->qkv_dtype || a->q_off) return ORTK_EINVAL;
-    ortk::lds_attr(reinterpret_cast<const void*>(attn_bwd_kernel), bwd_lds_bytes(MAXK));
-    ortk::lds_attr(reinterpret_cast<const void*>(attn_bwd_wave_kernel<64>), sizeof(float) * 4 * (2 * 64 * KP + 192));
-    ortk::lds_attr(reinterpret_cast<const void*>(attn_bwd_wave_kernel<48>), sizeof(float) * 4 * (2 * 48 * KP + 192));
-    const int pairs = a->nkv * a->H;
-    if (small_ok(a) && attn_impl() == 0 && a->ldv % 4 == 0 && a->lddo % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(a->v) | reinterpret_cast<uintptr_t>(a->d_o)) & 15) == 0) {
-        const dim3 sgrid((unsigned)ortk_cdiv(pairs, 4));
-        const int nit = a->Lq > 16 ? 2 : 1, njt = a->Lk > 16 ? 2 : 1;
-        if (nit == 2 && njt == 2)      hipLaunchKernelGGL((attn_small_bwd_kernel<2, 2>), sgrid, dim3(256), 0, ortk_s(stream), *a);
-        else if (nit == 2)             hipLaunchKernelGGL((attn_small_bwd_kernel<2, 1>), sgrid, dim3(256), 0, ortk_s(stream), *a);
-        else if (njt == 2)             hipLaunchKernelGGL((attn_small_bwd_kernel<1, 2>), sgrid, dim3(256), 0, ortk_s(stream), *a);
-        else                           hipLaunchKernelGGL((attn_small_bwd_kernel<1, 1>), sgrid, dim3(256), 0, ortk_s(stream), *a);
-        ORTK_CHECK_LAUNCH();
+int plan_bwd(const ortk_attn_args& a, AttnPlan& pl) {
+    if (a.kv_dtype != 0 || a.bwd_part < 0 || a.bwd_part > 2) return ORTK_EINVAL;
+    if (!a.p || !a.d_o || !a.dq || !a.d_k || !a.dv || a.kv_index || a.kv_group_stride) return ORTK_EINVAL;
+    if (a.nkv == 0) return 0;
+    if ((attn_impl() == 0 || a.qkv_dtype) && ortk::attn16_plan(a, true, pl)) {      // mixed precision: one kernel does both parts
+        if (a.bwd_part == 2) pl.n = 0;
         return 0;
     }
-    {
-        const int Lkp = (int)ortk_align(a->Lk, 16), DKP = (int)ortk_align(a->dk, 16), Lqp = (int)ortk_align(a->Lq, 16);
-        const size_t lds = sizeof(float) * ((size_t)Lkp * (PK_ + PN_) + (size_t)Lqp * (PN_ + 3 * PK_));
-        const bool use_mfma = attn_impl() == 0 ? a->Lq > 32 : attn_impl() == 3;
-        const bool vec = a->dk % 4 == 0 && a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->lddo % 4 == 0 &&
-                         ((reinterpret_cast<uintptr_t>(a->q) | reinterpret_cast<uintptr_t>(a->k) | reinterpret_cast<uintptr_t>(a->v) |
-                           reinterpret_cast<uintptr_t>(a->d_o)) & 15) == 0;
-        if (a->Lk <= 64 && vec && lds <= 160 * 1024 && use_mfma) {
-            const int nw = (int)std::min<int64_t>(8, ortk_cdiv(a->Lq, 16));
-            const dim3 mgrid((unsigned)pairs), mblock(64 * nw);
-            const size_t lds1 = sizeof(float) * ((size_t)Lkp * (PN_ + PK_) + (size_t)Lqp * 2 * PK_);    // PART 1: no Q / dropped-P images
-            typedef void (*bwd_fn)(ortk_attn_args, int, int, int);
-            bwd_fn fn; size_t bytes = lds;
-            if (a->bwd_part == 1 && DKP == 64 && Lkp == 48 && Lqp == 96)      { fn = attn_bwd_mfma_kernel<48, 64, 96, 1>; bytes = lds1; }
-            else if (a->bwd_part == 2 && DKP == 64 && Lkp == 48 && Lqp == 96) fn = attn_bwd_mfma_kernel<48, 64, 96, 2>;
-            else if (a->bwd_part == 1)                                        { fn = attn_bwd_mfma_kernel<0, 0, 0, 1>; bytes = lds1; }
-            else if (a->bwd_part == 2)                                        fn = attn_bwd_mfma_kernel<0, 0, 0, 2>;
-            else if (DKP == 64 && Lkp == 48 && Lqp == 48)                     fn = attn_bwd_mfma_kernel<48, 64, 48, 0>;
-            else if (DKP == 64 && Lkp == 48 && Lqp == 96)                     fn = attn_bwd_mfma_kernel<48, 64, 96, 0>;
-            else if (DKP == 64 && Lkp == 32 && Lqp == 32)                     fn = attn_bwd_mfma_kernel<32, 64, 32, 0>;
-            else                                                              fn = attn_bwd_mfma_kernel<0, 0, 0, 0>;
-            ortk::lds_attr(reinterpret_cast<const void*>(fn), 160 * 1024);
-            hipLaunchKernelGGL(fn, mgrid, mblock, bytes, ortk_s(stream), *a, Lkp, DKP, Lqp);
-            ORTK_CHECK_LAUNCH();
-            return 0;
-        }
+    if (a.qkv_dtype || a.q_off) return ORTK_EINVAL;
+    const int64_t pairs = (int64_t)a.nkv * a.H;
+    if (small_bwd_ok(a)) {
+        pl.add(SMALL_BWD[a.Lq > 16][a.Lk > 16], ortk_cdiv(pairs, 4), 256, 0);
+        return 0;
     }
-    if (a->bwd_part == 2) return 0;     // the kernels below compute everything in one go: part 1 already did
-    const dim3 wgrid((unsigned)ortk_cdiv(pairs, 4)), block(256);
-    const size_t wave_lds = sizeof(float) * 4 * ((size_t)2 * a->Lk * KP + 192);
-    if (a->Lk <= 32)
-        hipLaunchKernelGGL(attn_bwd_wave_kernel<32>, wgrid, block, wave_lds, ortk_s(stream), *a);
-    else if (a->Lk <= 48)
-        hipLaunchKernelGGL(attn_bwd_wave_kernel<48>, wgrid, block, wave_lds, ortk_s(stream), *a);
-    else if (a->Lk <= 64)
-        hipLaunchKernelGGL(attn_bwd_wave_kernel<64>, wgrid, block, wave_lds, ortk_s(stream), *a);
-    else
-        hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)pairs), block, bwd_lds_bytes(a->Lk), ortk_s(stream), *a);
-    ORTK_CHECK_LAUNCH();
+    const int Lkp = (int)ortk_align(a.Lk, 16), DKP = (int)ortk_align(a.dk, 16), Lqp = (int)ortk_align(a.Lq, 16);
+    const size_t lds = sizeof(float) * ((size_t)Lkp * (PK_ + PN_) + (size_t)Lqp * (PN_ + 3 * PK_));
+    const size_t lds1 = sizeof(float) * ((size_t)Lkp * (PN_ + PK_) + (size_t)Lqp * 2 * PK_);    // PART 1: no Q / dropped-P images
+    if (a.Lk <= 64 && lds <= LDS_MAX && use_mfma(a) && a.dk % 4 == 0 && ld_multiple(4, a.ldq, a.ldk, a.ldv, a.lddo) && aligned16(a.q, a.k, a.v, a.d_o)) {
+        const int nw = (int)std::min<int64_t>(8, ortk_cdiv(a.Lq, 16));
+        pl.add(bwd_mfma_inst(Lkp, DKP, Lqp, a.bwd_part), pairs, 64 * nw, a.bwd_part == 1 ? lds1 : lds, LDS_MAX, Lkp, DKP, Lqp);
+        return 0;
+    }
+    if (a.bwd_part == 2) return 0;     // the kernels below compute everything in one go: part 1 already did
+    if (a.Lk <= 64) {
+        const auto& w = BWD_WAVE[a.Lk <= 32 ? 0 : a.Lk <= 48 ? 1 : 2];
+        pl.add(w.k, ortk_cdiv(pairs, 4), 256, wave_lds(a.Lk, 192), w.lds_limit);
+    } else {
+        pl.add(INST0(bwd), pairs, 256, bwd_lds_bytes(a.Lk), bwd_lds_bytes(MAXK));
+    }
+    return 0;
+}
+#undef INST
+#undef INST0
+
+// The one plan builder, for ortk_attention_fwd / ortk_attention_bwd and ortk_attention_plan alike: the only place that decides a
+// kernel.  Returns the code the operator returns; 0 with an empty plan: nothing to launch.
+int plan_attention(const ortk_attn_args& a, bool bwd, AttnPlan& pl) {
+    if (!a.q || !a.k || !a.v) return ORTK_EINVAL;
+    if (a.Lk < 1 || a.Lk > MAXK || a.dk < 1 || a.dk > MAXD || a.Lq < 1 || a.H < 1 || a.nkv < 0) return ORTK_EINVAL;
+    if (a.drop_p < 0.f || a.drop_p >= 1.f) return ORTK_EINVAL;
+    return bwd ? plan_bwd(a, pl) : plan_fwd(a, pl);
+}
+
+// The one launch tail: no allocation, no formatting
+int attn_launch(const ortk_attn_args& a, const AttnPlan& pl, hipStream_t s) {
+    ortk_attn_args p = a;
+    for (int i = 0; i < pl.n; ++i) {
+        ortk::AttnLaunch l = pl.l[i];
+        if (l.lds_limit && ortk::lds_attr(l.fn, l.lds_limit)) return ORTK_EINVAL;
+        void* args[] = {&p, &l.a0, &l.a1, &l.a2};
+        (void)hipLaunchKernel(l.fn, dim3(l.grid), dim3(l.block), args, l.lds, s);     // (its error: ORTK_CHECK_LAUNCH below)
+        ORTK_CHECK_LAUNCH();
+        p.k_new = p.v_new = nullptr;      // (a second launch follows the append: it attends to the cache as usual)
+    }
+    return 0;
+}
+
+int attention(const ortk_attn_args* a, bool bwd, ortk_stream stream) {
+    AttnPlan pl;
+    if (!a) return ORTK_EINVAL;
+    if (int e = plan_attention(*a, bwd, pl)) return e;
+    return attn_launch(*a, pl, ortk_s(stream));
+}
+
+}  // namespace
+
+extern "C" int ortk_attention_fwd(const ortk_attn_args* a, ortk_stream stream) { return attention(a, false, stream); }
+extern "C" int ortk_attention_bwd(const ortk_attn_args* a, ortk_stream stream) { return attention(a, true, stream); }
+
+extern "C" int ortk_attention_plan(const ortk_attn_args* a, int32_t bwd, char* buf, int32_t buf_bytes) {
+    AttnPlan pl;
+    if (!a) return ORTK_EINVAL;
+    if (int e = plan_attention(*a, bwd != 0, pl)) return e;
+    if (!buf || buf_bytes <= 0) return ORTK_EINVAL;
+    char text[2 * 96] = ""; int len = 0;
+    for (int i = 0; i < pl.n; ++i)
+        len += snprintf(text + len, sizeof(text) - len, "%s%s:wg=%u:lds=%zu", i ? ";" : "", pl.l[i].name, pl.l[i].block, pl.l[i].lds);
+    if ((size_t)len + 1 > (size_t)buf_bytes) return ORTK_ENOSPC;
+    memcpy(buf, text, (size_t)len + 1);
     return 0;
 }

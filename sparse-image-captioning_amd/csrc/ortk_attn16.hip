@@ -21,12 +21,20 @@
 //     rows / columns of the images.
 // The pitch of 72 bf16 (144 B) makes the 16 rows of a ds_read_b128 service group fall on 16 distinct 16-byte slots.
 //
-// Three mappings of ONE per-tile code (fwd16_tile, bwd16_tile1, bwd16_tile2; bit-identical results): the block kernels
-// (attn16_fwd_kernel / attn16_bwd_kernel: a workgroup per (group, head), a wave per 16-row query tile; every served shape and
-// fp32 inputs), their second mapping for those block shapes with bf16 inputs (attn16b_*: three waves, up to two query tiles per
-// wave, half the LDS per workgroup and so more workgroups per compute unit; ortk_tuning.attn16_block), and the short kernels (attn16s_*: a WAVE per (group, head), bf16 inputs, at most 32 query rows and 32 keys) for the decoder's
-// causal self-attention, where a workgroup's second wave owned one query row or none (ortk_tuning.attn16_short).
+// Three mappings of ONE per-tile code (fwd16_tile, bwd16_tile1, bwd16_tile2; bit-identical results), forward and backward:
+//   * attn16_*_kernel, the wave-per-tile kernels: a workgroup per (group, head), a wave per 16-row query tile, K / V / Q / dO
+//     through LDS images (stage_rows).  Every served shape, and the only mapping for fp32 inputs.
+//   * attn16b_*_kernel, the block kernels (ortk_tuning.attn16_block): bf16 inputs, at most 64 keys and 96 query rows.  Three
+//     waves whatever Lq, up to two query tiles per wave, half the LDS per workgroup and so more workgroups per compute unit.
+//   * attn16s_*_kernel, the short kernels (ortk_tuning.attn16_short): bf16 inputs, at most 32 query rows and 32 keys (the
+//     decoder's causal self-attention).  A WAVE per (group, head), no workgroup barrier.
+// What the six kernels share besides the tile code: the ragged-group geometry (group_geo), the per-tile row setup (tile_rows),
+// the register stager of the block and short kernels (stage_ld / stage_st), the row-fragment loads (ld_row_frags), the image
+// clear (zero_cols), and one LDS layout per kernel (*Lds) that gives the kernel its pointers and attn16_plan its byte count.
+// Two exceptions, both for registers (profiles/attention_refactor.txt): attn16b_bwd_kernel spells its prologue out, and so do the
+// instances of attn16b_fwd_kernel that run two query tiles per wave.
 #include <cstdlib>
+#include <type_traits>
 #include "ortk_internal.h"
 
 namespace {
@@ -35,12 +43,46 @@ constexpr int P16 = 72;                 // bf16 elements per row of an image wit
 
 __device__ __forceinline__ void wsync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
-// Key-indexed geometry for NJT key tiles (Lk <= 16 * NJT <= 128): KJ = key range as a k dimension (multiple of 32, zero-
+// Key-indexed geometry for njt key tiles (Lk <= 16 * njt <= 128): KJ = key range as a k dimension (multiple of 32, zero-
 // padded), PJ = pitch of the [query][key] images (KJ + 8: the same 16-distinct-slots property as P16 for its row length).
-template <int NJT> struct KeyGeo {
-    static constexpr int KJ = NJT <= 2 ? 32 : NJT <= 4 ? 64 : NJT <= 6 ? 96 : 128;
-    static constexpr int PJ = NJT <= 4 ? P16 : 136;
+__host__ __device__ constexpr int key_kj(int njt) { return njt <= 2 ? 32 : njt <= 4 ? 64 : njt <= 6 ? 96 : 128; }
+__host__ __device__ constexpr int key_pj(int njt) { return njt <= 4 ? P16 : 136; }
+template <int NJT> struct KeyGeo { static constexpr int KJ = key_kj(NJT), PJ = key_pj(NJT); };
+constexpr int KJS = 32, PJS = KJS + 8;            // key range and [query][key] image pitch of the short kernels
+constexpr int NWB = 3, NTB = 64 * NWB;            // waves / threads per workgroup of the block (attn16b) kernels
+
+// The LDS layout of each kernel, declared once: the offsets (bf16 elements into sm16[]) its images start at, and the dynamic-LDS
+// bytes its launch asks for.  (dk = features per head, image pitch dk + 8; nw = waves; Lqp = query rows padded to 32.)
+__host__ __device__ constexpr int imax(int a, int b) { return a > b ? a : b; }
+struct Fwd16Lds {      // attn16_fwd_kernel: K [16 njt][PD], V [KJ][PD], a P image [16][PJ] per wave, the key mask [128] floats
+    int V, P, mask, end;
+    __host__ __device__ constexpr Fwd16Lds(int njt, int dk, int nw)
+        : V(16 * njt * (dk + 8)), P(V + key_kj(njt) * (dk + 8)), mask(P + 16 * nw * key_pj(njt)), end(mask + 2 * 128) {}
 };
+struct Fwd16sLds {     // attn16s_fwd_kernel, per wave: V [KJS][PD], P [16][PJS], the key mask [32] floats
+    int P, mask, end;
+    __host__ __device__ constexpr Fwd16sLds(int dk) : P(KJS * (dk + 8)), mask(P + 16 * PJS), end(mask + 2 * 32) {}
+};
+struct Fwd16bLds {     // attn16b_fwd_kernel: V [KJ][PD], then K [16 njt][PD] whose bytes become the NWB P images [16][PJ], the key mask [64] floats
+    int K, mask, end;
+    __host__ __device__ constexpr Fwd16bLds(int njt, int dk)
+        : K(key_kj(njt) * (dk + 8)), mask(K + imax(16 * njt * (dk + 8), NWB * 16 * key_pj(njt))), end(mask + 2 * 64) {}
+};
+struct Bwd16Lds {      // attn16_bwd_kernel: K [KJ][PD], V [16 njt][PD], Q and dO [Lqp][PD], dS and dropped P [Lqp][PJ]
+    int V, Q, G, S, D, end;
+    __host__ __device__ constexpr Bwd16Lds(int njt, int dk, int Lqp)
+        : V(key_kj(njt) * (dk + 8)), Q(V + 16 * njt * (dk + 8)), G(Q + Lqp * (dk + 8)), S(G + Lqp * (dk + 8)), D(S + Lqp * key_pj(njt)), end(D + Lqp * key_pj(njt)) {}
+};
+struct Bwd16sLds {     // attn16s_bwd_kernel, per wave: X [32][PD] (K, then Q, then dO), dS and dropped P [32][PJS]
+    int S, D, end;
+    __host__ __device__ constexpr Bwd16sLds(int dk) : S(32 * (dk + 8)), D(S + 32 * PJS), end(D + 32 * PJS) {}
+};
+struct Bwd16bLds {     // attn16b_bwd_kernel: X [max(KJ, Lqp)][PD] (K, then Q, then dO), dS and dropped P [Lqp][PJ]
+    int S, D, end;
+    __host__ __device__ constexpr Bwd16bLds(int njt, int dk, int Lqp)
+        : S(imax(key_kj(njt), Lqp) * (dk + 8)), D(S + Lqp * key_pj(njt)), end(D + Lqp * key_pj(njt)) {}
+};
+template <typename L> constexpr size_t lds_bytes(const L& l) { return (size_t)l.end * sizeof(__bf16); }
 
 // [index = row][k = k0 .. k0+7]: 8 consecutive elements of an image row
 template <int PITCH = P16>
@@ -99,8 +141,14 @@ template <int NJT, int NKS> struct RegRowFrags {
     bf16x8 f[NJT][NKS];
     __device__ __forceinline__ bf16x8 operator()(int jt, int ks) const { return f[jt][ks]; }
 };
+// Element (r, c) of a matrix slice behind a uniform base.  OFF32 (the block kernels): a 32-bit offset per lane, so that a load
+// holds one address register and not two (their register budget: attn16b_fwd_kernel); otherwise 64-bit.
+template <bool OFF32> __device__ __forceinline__ int64_t row_off(int r, int64_t ld, int c) {
+    if constexpr (OFF32) return (unsigned)r * (unsigned)ld + (unsigned)c;
+    else return (int64_t)r * ld + c;
+}
 // rows [0, rows) of the group's rows, head h, as such fragments; rows past the count are zero (what stage_rows leaves in an image)
-template <int NJT, int NKS>
+template <bool OFF32, int NJT, int NKS>
 __device__ __forceinline__ void ld_row_frags(RegRowFrags<NJT, NKS>& out, const __bf16* src, int64_t ld, int rows, int lane) {
     const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
@@ -108,7 +156,7 @@ __device__ __forceinline__ void ld_row_frags(RegRowFrags<NJT, NKS>& out, const _
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {
             out.f[jt][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            if (16 * jt + lr < rows) out.f[jt][ks] = ld_frag(src + (int64_t)(16 * jt + lr) * ld + 32 * ks + 8 * lq);
+            if (16 * jt + lr < rows) out.f[jt][ks] = ld_frag(src + row_off<OFF32>(16 * jt + lr, ld, 32 * ks + 8 * lq));
         }
 }
 // One row of a [..][Lk] fp32 tensor (bias, saved P) as this lane's 4 consecutive keys of every key tile; zero where `on` is
@@ -126,26 +174,81 @@ __device__ __forceinline__ void ld_keys4(float4 (&out)[NJT], const float* base, 
         }
     }
 }
-// One wave's share of a 32-row image (the short kernels): rows [0, rows) of a bf16 matrix slice into registers, zero past the
-// count; then into the image (pitch DKT + 8).  Split in two so that the loads are issued with every other load of the wave.
-template <int DKT>
-__device__ __forceinline__ void stage32_ld(bf16x8 (&v)[DKT / 16], const __bf16* src, int64_t ld, int rows, int lane) {
+// The register stager of the short kernels (NT = 64: one wave, ROWS = 32) and of the block kernels (NT = NTB): thread tid's share
+// of a ROWS-row image.  stage_ld: rows [0, rows) of a bf16 matrix slice into registers, zero past the count; stage_st: rows
+// [0, rows_st) into the image (pitch DKT + 8).  Split in two so that the loads are issued with every other load of the workgroup.
+template <int DKT, int ROWS, int NT> struct Stage { static constexpr int N = (ROWS * (DKT / 8) + NT - 1) / NT; };      // 16-byte pieces per thread
+template <int DKT, int ROWS, int NT, int N = Stage<DKT, ROWS, NT>::N>
+__device__ __forceinline__ void stage_ld(bf16x8 (&v)[N], const __bf16* src, int64_t ld, int rows, int tid) {
     constexpr int CPR = DKT / 8;
 #pragma unroll
-    for (int n = 0; n < DKT / 16; ++n) {
-        const int idx = lane + 64 * n, r = idx / CPR, c = (idx % CPR) * 8;
+    for (int n = 0; n < N; ++n) {
+        const int idx = tid + NT * n, r = idx / CPR, c = (idx % CPR) * 8;
         v[n] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        if (r < rows) v[n] = *reinterpret_cast<const bf16x8*>(src + (int64_t)r * ld + c);
+        if (r < rows) v[n] = *reinterpret_cast<const bf16x8*>(src + row_off<NT != 64>(r, ld, c));
     }
 }
-template <int DKT>
-__device__ __forceinline__ void stage32_st(__bf16* img, const bf16x8 (&v)[DKT / 16], int lane) {
+template <int DKT, int ROWS, int NT, int N = Stage<DKT, ROWS, NT>::N>
+__device__ __forceinline__ void stage_st(__bf16* img, const bf16x8 (&v)[N], int rows_st, int tid) {
     constexpr int CPR = DKT / 8;
 #pragma unroll
-    for (int n = 0; n < DKT / 16; ++n) {
-        const int idx = lane + 64 * n, r = idx / CPR, c = (idx % CPR) * 8;
-        *reinterpret_cast<bf16x8*>(img + r * (DKT + 8) + c) = v[n];
+    for (int n = 0; n < N; ++n) {
+        const int idx = tid + NT * n, r = idx / CPR, c = (idx % CPR) * 8;
+        if (r < rows_st) *reinterpret_cast<bf16x8*>(img + r * (DKT + 8) + c) = v[n];
     }
+}
+// Columns [0, COLS) of `rows` rows of a [query][key] image (pitch PJ) to zero: the key columns 16 * NJT .. KJ - 1, and the rows of a
+// tile that is not run, are never written by a tile.  COLS = PJ: the image is contiguous (16-byte stores, the padding included).
+template <int PJ, int COLS>
+__device__ __forceinline__ void zero_cols(__bf16* img, int rows, int tid, int nthr) {
+    constexpr int VN = COLS == PJ ? 8 : 4, CPR = COLS / VN;
+    for (int idx = tid; idx < rows * CPR; idx += nthr) {
+        __bf16* p = COLS == PJ ? img + idx * VN : img + (idx / CPR) * PJ + (idx % CPR) * VN;
+        if constexpr (VN == 8) *reinterpret_cast<bf16x8*>(p) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+        else *reinterpret_cast<bf16x4*>(p) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+    }
+}
+
+// Ragged groups (ortk_attn_args.q_off): group g's first query row and its row count; with kv_ragged its keys are those rows.
+struct GroupGeo { int64_t qrow0; int Lqg; int64_t krow0; int Lkg; };
+__device__ __forceinline__ GroupGeo group_geo(const ortk_attn_args& a, int g) {
+    int64_t qrow0 = (int64_t)g * a.Lq;
+    int Lqg = a.Lq;
+    if (a.q_off) {                                  // both entries in one round trip
+        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
+        qrow0 = o0; Lqg = min(a.Lq, o1 - o0);
+    }
+    const bool kr = a.q_off && a.kv_ragged;
+    return GroupGeo{qrow0, Lqg, kr ? qrow0 : (int64_t)g * a.Lk, kr ? min(a.Lk, Lqg) : a.Lk};
+}
+// The rows of one 16-row query tile (first row i0 of group g, head h) as a kernel's prologue needs them: i = this lane's row inside
+// the group (operand row and output row), iv = the group has it; prow = first element of its row of P / bias / dscore, drow = of
+// the row its dropout draws are keyed by (a ragged group draws like the unragged layout: ortk_attn_args.drop_rows); f = its row
+// fragments of `src` (Q in the forward, dO in the backward; a void pointer: the kernel takes them from an image) and k4 = its row of `keys`
+// (bias; saved P), both zero for a row the group does not have.  Every load is only requested here.
+template <int NJT, int NKS> struct TileRows { bool iv; int64_t prow, drow; bf16x8 f[NKS]; float4 k4[NJT]; };
+template <bool OFF32, int NJT, int NKS, typename TQ>
+__device__ __forceinline__ TileRows<NJT, NKS> tile_rows(const ortk_attn_args& a, const GroupGeo& gg, int g, int h, int i0, int lane,
+                                                        const TQ* src, int64_t ld, const float* keys, bool keys_on) {
+    TileRows<NJT, NKS> t;
+    const int lr = lane & 15, lq = lane >> 4, Lq = a.Lq, Lk = a.Lk;
+    const int i = i0 + lr;
+    t.iv = i < gg.Lqg;
+    t.prow = (((int64_t)g * a.H + h) * Lq + i) * Lk;
+    t.drow = t.prow;
+    if (a.drop_p > 0.f && a.drop_rows && a.q_off && t.iv)
+        t.drow = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[gg.qrow0 + i] - (int64_t)g * Lq)) * Lk;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) t.f[ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (!std::is_void<TQ>::value) {
+        if (t.iv) {                                 // (OFF32: see row_off)
+            const TQ* p = OFF32 ? src + gg.qrow0 * ld + h * (32 * NKS) + row_off<true>(i, ld, 8 * lq) : src + (gg.qrow0 + i) * ld + h * (32 * NKS) + 8 * lq;
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) t.f[ks] = ld_frag(p + 32 * ks);
+        }
+    }
+    ld_keys4<NJT>(t.k4, keys, keys_on && t.iv, t.prow, Lk, lq);
+    return t;
 }
 
 // ------------------------------------------------------------------------------------------------ forward
@@ -226,7 +329,7 @@ __device__ __forceinline__ void fwd16_tile(const ortk_attn_args& a, const KF& kf
     }
 }
 
-// The block kernel: one workgroup per (group g, head h); one wave per 16-row query tile.  NJT = key tiles (Lk <= 16 * NJT <= 128).
+// The wave-per-tile kernel: one workgroup per (group g, head h); one wave per 16-row query tile.  NJT = key tiles (Lk <= 16 * NJT <= 128).
 template <int NJT, typename TQ, int DKT>
 __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
     constexpr int DK = DKT, PD = DKT + 8;           // features per head; pitch of the [row][feature] images
@@ -234,49 +337,27 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
     const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
-    const int Lk = a.Lk, Lq = a.Lq;
     constexpr int KJ = KeyGeo<NJT>::KJ, PJ = KeyGeo<NJT>::PJ;
+    const Fwd16Lds L(NJT, DKT, nw);
     __bf16* sK = sm16;                              // [16*NJT][PD]   rows = key            (row fragments)
-    __bf16* sV = sK + 16 * NJT * PD;                // [KJ][PD]       rows = key, zero-padded (k of P.V: transposing reads)
-    __bf16* sP = sV + KJ * PD + wave * 16 * PJ;     // [16][PJ]       this wave's dropped P: rows = query, columns = key 0..KJ-1
-    float* sMask = reinterpret_cast<float*>(sm16 + (16 * NJT + KJ) * PD + 16 * nw * PJ);   // [128]
+    __bf16* sV = sm16 + L.V;                        // [KJ][PD]       rows = key, zero-padded (k of P.V: transposing reads)
+    __bf16* sP = sm16 + L.P + wave * 16 * PJ;       // [16][PJ]       this wave's dropped P: rows = query, columns = key 0..KJ-1
+    float* sMask = reinterpret_cast<float*>(sm16 + L.mask);   // [128]
     const int lr = lane & 15, lq = lane >> 4;
-    const int nit = (Lq + 15) >> 4;
-    // ragged groups (ortk_attn_args.q_off): the group's first query row and its row count; with kv_ragged its keys are those rows
-    const int64_t qrow0 = a.q_off ? (int64_t)a.q_off[(int64_t)g * a.q_off_stride] : (int64_t)g * Lq;
-    const int Lqg = a.q_off ? min(Lq, (int)(a.q_off[(int64_t)(g + 1) * a.q_off_stride] - qrow0)) : Lq;
-    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
-    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
-    // The launcher gives every 16-row query tile its own wave (nw = nit).  This wave's Q fragments and bias rows are
-    // requested BEFORE the K / V staging and its barrier, so that the workgroup pays one global round trip, not two.
-    const int it = wave;
-    const int i = it * 16 + lr;                     // this lane's query (operand row and output row)
-    const bool iv = it < nit && i < Lqg;
-    const int64_t prow = (((int64_t)g * a.H + h) * Lq + i) * Lk;
-    // dropout draws of a ragged group keyed like the unragged layout's (ortk_attn_args.drop_rows): query i -> drop_rows[.] - g Lq
-    const int64_t drow = (a.drop_rows && a.q_off && iv && a.drop_p > 0.f)
-                             ? (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk : prow;
-    bf16x8 qf[DK / 32];
-#pragma unroll
-    for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-    if (iv) {
-        const TQ* qp = aq + (qrow0 + i) * a.ldq + h * DK + 8 * lq;
-#pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) qf[ks] = ld_frag(qp + 32 * ks);
-    }
-    float4 bias4[NJT];
-    ld_keys4<NJT>(bias4, a.bias, a.bias && iv, prow, Lk, lq);
-    stage_rows<DK>(sK, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, 16 * NJT, tid, blockDim.x);
-    stage_rows<DK>(sV, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, KJ, tid, blockDim.x);
+    const GroupGeo gg = group_geo(a, g);
+    // The launcher gives every 16-row query tile its own wave.  This wave's Q fragments and bias rows are requested BEFORE
+    // the K / V staging and its barrier, so that the workgroup pays one global round trip, not two.
+    const int i = wave * 16 + lr;                   // this lane's query row inside the group (operand row and output row)
+    const TileRows<NJT, DK / 32> t = tile_rows<false, NJT, DK / 32>(a, gg, g, h, wave * 16, lane, aq, a.ldq, a.bias, a.bias != nullptr);
+    stage_rows<DK>(sK, ak + gg.krow0 * a.ldk + h * DK, a.ldk, gg.Lkg, 16 * NJT, tid, blockDim.x);
+    stage_rows<DK>(sV, av + gg.krow0 * a.ldv + h * DK, a.ldv, gg.Lkg, KJ, tid, blockDim.x);
     for (int j = tid; j < 128; j += blockDim.x)     // all 128 entries whatever the workgroup size (one wave when Lq <= 16)
-        sMask[j] = (j < Lkg) ? (a.kmask ? a.kmask[krow0 + j] : 1.f) : -1.f;                    // -1: padded key
-    // key columns 16*NJT .. KJ-1 of the P image are never written below: zero the image once
-    for (int idx = lane; idx < 16 * (KJ / 4); idx += 64)
-        *reinterpret_cast<bf16x4*>(sP + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+        sMask[j] = (j < gg.Lkg) ? (a.kmask ? a.kmask[gg.krow0 + j] : 1.f) : -1.f;              // -1: padded key
+    zero_cols<PJ, KJ>(sP, 16, lane, 64);
     __syncthreads();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-    if (it < nit)
-        fwd16_tile<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sK, lr, lq}, qf, bias4, sMask, sV, sP, lane, i, iv, prow, drow, qrow0 + i, h, inv_keep);
+    if (wave * 16 < a.Lq)
+        fwd16_tile<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sK, lr, lq}, t.f, t.k4, sMask, sV, sP, lane, i, t.iv, t.prow, t.drow, gg.qrow0 + i, h, inv_keep);
 }
 
 // The short kernel (bf16 Q / K / V, Lq <= 32, Lk <= 32: the decoder's causal self-attention): one WAVE per (group, head), pair
@@ -285,78 +366,44 @@ __global__ __launch_bounds__(512) void attn16_fwd_kernel(ortk_attn_args a) {
 // K goes from global memory straight into row fragments; LDS holds, per wave, the V image (transposing reads), the P image
 // (C-layout -> operand) and the 32 key-mask entries: 6 016 B at dk = 64.  Every global load is issued before the first wait;
 // no __syncthreads(): a wave only ever touches its own LDS region.
-constexpr int KJS = 32, PJS = KJS + 8;            // key range and [query][key] image pitch of the short kernels
-template <int DKT> constexpr int fwd16s_wave_elems() { return KJS * (DKT + 8) + 16 * PJS + 64; }      // bf16 elements (64 = 32 floats)
 template <int NJT, int DKT>
 __global__ __launch_bounds__(512) void attn16s_fwd_kernel(ortk_attn_args a) {
     static_assert(NJT <= 2, "the short kernels serve at most 32 keys");
-    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32;
+    constexpr int DK = DKT, NKS = DKT / 32;
     const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), W = blockDim.x >> 6;
     const int pair = blockIdx.x * W + wave;
     if (pair >= a.nkv * a.H) return;                // the last workgroup may be partly empty (no workgroup barrier below)
     const int g = pair / a.H, h = pair - g * a.H;
-    const int Lk = a.Lk, Lq = a.Lq;
-    __bf16* sV = sm16 + wave * fwd16s_wave_elems<DKT>();       // [KJS][PD]  rows = key, zero-padded
-    __bf16* sP = sV + KJS * PD;                                // [16][PJS]  dropped P of the current tile
-    float* sMask = reinterpret_cast<float*>(sP + 16 * PJS);    // [32]
-    const int lr = lane & 15, lq = lane >> 4;
-    int64_t qrow0 = (int64_t)g * Lq;
-    int Lqg = Lq;
-    if (a.q_off) {                                  // both entries in one round trip
-        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
-        qrow0 = o0; Lqg = min(Lq, o1 - o0);
-    }
-    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
-    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    constexpr Fwd16sLds L(DKT);
+    __bf16* sV = sm16 + wave * L.end;                          // [KJS][PD]  rows = key, zero-padded
+    __bf16* sP = sV + L.P;                                     // [16][PJS]  dropped P of the current tile
+    float* sMask = reinterpret_cast<float*>(sV + L.mask);      // [32]
+    const int lr = lane & 15;
+    const GroupGeo gg = group_geo(a, g);
     // ---- every global load of the wave
-    bf16x8 vreg[DKT / 16];
-    stage32_ld<DKT>(vreg, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
-    const float mk = (lane < Lkg) ? (a.kmask ? a.kmask[krow0 + lane] : 1.f) : -1.f;        // -1: padded key (Lkg <= 32: lanes 0 .. 31 are stored)
+    bf16x8 vreg[Stage<DKT, KJS, 64>::N];
+    stage_ld<DKT, KJS, 64>(vreg, av + gg.krow0 * a.ldv + h * DK, a.ldv, gg.Lkg, lane);
+    const float mk = (lane < gg.Lkg) ? (a.kmask ? a.kmask[gg.krow0 + lane] : 1.f) : -1.f;  // -1: padded key (Lkg <= 32: lanes 0 .. 31 are stored)
     RegRowFrags<NJT, NKS> kf;
-    ld_row_frags<NJT, NKS>(kf, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, lane);
-    bf16x8 qf[2][NKS];
-    float4 bias4[2][NJT];
-    int64_t prow[2], drow[2];
-    bool iv[2];
+    ld_row_frags<false>(kf, ak + gg.krow0 * a.ldk + h * DK, a.ldk, gg.Lkg, lane);
+    TileRows<NJT, NKS> t[2];
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int i = it * 16 + lr;
-        iv[it] = i < Lqg;
-        prow[it] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
-        drow[it] = prow[it];
-        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[it])
-            drow[it] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[it][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        if (iv[it]) {
-            const __bf16* qp = aq + (qrow0 + i) * a.ldq + h * DK + 8 * lq;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[it][ks] = ld_frag(qp + 32 * ks);
-        }
-        ld_keys4<NJT>(bias4[it], a.bias, a.bias && iv[it], prow[it], Lk, lq);
-    }
+    for (int it = 0; it < 2; ++it) t[it] = tile_rows<false, NJT, NKS>(a, gg, g, h, it * 16, lane, aq, a.ldq, a.bias, a.bias != nullptr);
     // ---- the wave's LDS region
-    stage32_st<DKT>(sV, vreg, lane);
+    stage_st<DKT, KJS, 64>(sV, vreg, KJS, lane);
     if (lane < 32) sMask[lane] = mk;
-    // (key columns 16*NJT .. KJS-1 of the P image are never written by a tile)
-    for (int idx = lane; idx < 16 * (KJS / 4); idx += 64)
-        *reinterpret_cast<bf16x4*>(sP + (idx / (KJS / 4)) * PJS + (idx % (KJS / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+    zero_cols<PJS, KJS>(sP, 16, lane, 64);
     wsync();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-        if (it * 16 >= Lqg) break;                  // a tile with no row of the group stores nothing
-        fwd16_tile<NJT, DKT, PJS>(a, kf, qf[it], bias4[it], sMask, sV, sP, lane, it * 16 + lr, iv[it], prow[it], drow[it],
-                                  qrow0 + it * 16 + lr, h, inv_keep);
+        if (it * 16 >= gg.Lqg) break;               // a tile with no row of the group stores nothing
+        fwd16_tile<NJT, DKT, PJS>(a, kf, t[it].f, t[it].k4, sMask, sV, sP, lane, it * 16 + lr, t[it].iv, t[it].prow, t[it].drow,
+                                  gg.qrow0 + it * 16 + lr, h, inv_keep);
         wsync();                                    // the next tile overwrites the P image
     }
-}
-static int key_kj(int njt) { return njt <= 2 ? 32 : njt <= 4 ? 64 : njt <= 6 ? 96 : 128; }
-static int key_pj(int njt) { return njt <= 4 ? P16 : 136; }
-static size_t fwd16_lds(int njt, int nw, int dk) {
-    return ((size_t)(16 * njt + key_kj(njt)) * (dk + 8) + (size_t)16 * nw * key_pj(njt)) * sizeof(__bf16) + 128 * sizeof(float);
 }
 
 // The second mapping of the block kernels (ortk_tuning.attn16_block; bf16 Q / K / V, at most 64 keys and 96 query rows): still a
@@ -368,41 +415,6 @@ static size_t fwd16_lds(int njt, int nw, int dk) {
 // that region and the key mask: 16 384 B at 36 keys and dk = 64 (23 552 / 30 464 B in attn16_fwd_kernel).  K goes through LDS and
 // not straight into fragments (as in the short kernel) because 24 more registers in flight beside the V, Q and bias loads do not
 // fit the 80 of 6 waves per SIMD.  Every global load is issued before the first wait.
-constexpr int NWB = 3, NTB = 64 * NWB;          // waves / threads per workgroup of the attn16b kernels
-// The workgroup's share of a ROWS-row image: rows [0, rows) of a bf16 matrix slice into registers, zero past the count; then rows
-// [0, rows_st) into the image (pitch DKT + 8).  Split in two like stage32_ld / stage32_st.
-template <int DKT, int ROWS> struct StageB { static constexpr int N = (ROWS * (DKT / 8) + NTB - 1) / NTB; };      // 16-byte pieces per thread
-template <int DKT, int ROWS, int N = StageB<DKT, ROWS>::N>
-__device__ __forceinline__ void stageb_ld(bf16x8 (&v)[N], const __bf16* src, int64_t ld, int rows, int tid) {
-    constexpr int CPR = DKT / 8;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int idx = tid + NTB * n, r = idx / CPR, c = (idx % CPR) * 8;
-        v[n] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        if (r < rows) v[n] = *reinterpret_cast<const bf16x8*>(src + ((unsigned)r * (unsigned)ld + (unsigned)c));
-    }
-}
-// ld_row_frags with the same addressing (a uniform base and a 32-bit offset per lane: one address register per load, not two)
-template <int NJT, int NKS>
-__device__ __forceinline__ void ld_row_fragsb(RegRowFrags<NJT, NKS>& out, const __bf16* src, int64_t ld, int rows, int lane) {
-    const int lr = lane & 15, lq = lane >> 4;
-#pragma unroll
-    for (int jt = 0; jt < NJT; ++jt)
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            out.f[jt][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-            if (16 * jt + lr < rows) out.f[jt][ks] = ld_frag(src + ((unsigned)(16 * jt + lr) * (unsigned)ld + (unsigned)(32 * ks + 8 * lq)));
-        }
-}
-template <int DKT, int ROWS, int N = StageB<DKT, ROWS>::N>
-__device__ __forceinline__ void stageb_st(__bf16* img, const bf16x8 (&v)[N], int rows_st, int tid) {
-    constexpr int CPR = DKT / 8;
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        const int idx = tid + NTB * n, r = idx / CPR, c = (idx % CPR) * 8;
-        if (r < rows_st) *reinterpret_cast<bf16x8*>(img + r * (DKT + 8) + c) = v[n];
-    }
-}
 // (registers: 6 waves per SIMD = 8 workgroups per compute unit; 4 key tiles at dk = 64 do not fit 80 registers and get 128)
 template <int NJT, int DKT, int TPW>
 __global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(NJT * DKT > 192 ? 4 : 6))) void attn16b_fwd_kernel(ortk_attn_args a) {
@@ -412,52 +424,47 @@ __global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(NJT * DKT >
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
-    const int Lk = a.Lk, Lq = a.Lq;
-    constexpr int KP = 16 * NJT * PD > NWB * 16 * PJ ? 16 * NJT * PD : NWB * 16 * PJ;       // the K image, then the P images
+    constexpr Fwd16bLds L(NJT, DKT);
     __bf16* sV = sm16;                                         // [KJ][PD]      rows = key, zero-padded
-    __bf16* sK = sV + KJ * PD;                                 // [16*NJT][PD]  rows = key: on its way into every wave's row fragments
+    __bf16* sK = sm16 + L.K;                                   // [16*NJT][PD]  rows = key: on its way into every wave's row fragments
     __bf16* sP = sK + wave * 16 * PJ;                          // [16][PJ]      then this wave's dropped P of the current tile
-    float* sMask = reinterpret_cast<float*>(sK + KP);          // [64]
+    float* sMask = reinterpret_cast<float*>(sm16 + L.mask);    // [64]
     const int lr = lane & 15, lq = lane >> 4;
-    int64_t qrow0 = (int64_t)g * Lq;
-    int Lqg = Lq;
-    if (a.q_off) {                                  // both entries in one round trip
-        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
-        qrow0 = o0; Lqg = min(Lq, o1 - o0);
-    }
-    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
-    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    const GroupGeo gg = group_geo(a, g);
     // ---- every global load of the workgroup
-    bf16x8 vreg[StageB<DKT, KJ>::N];
-    stageb_ld<DKT, KJ>(vreg, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, tid);
+    bf16x8 vreg[Stage<DKT, KJ, NTB>::N];
+    stage_ld<DKT, KJ, NTB>(vreg, av + gg.krow0 * a.ldv + h * DK, a.ldv, gg.Lkg, tid);
     float mk = -1.f;                                // -1: padded key
-    if (tid < Lkg) mk = a.kmask ? a.kmask[krow0 + tid] : 1.f;                    // (Lkg <= 64: threads 0 .. 63 are stored)
-    bf16x8 kreg[StageB<DKT, 16 * NJT>::N];
-    stageb_ld<DKT, 16 * NJT>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, tid);
-    bf16x8 qf[TPW][NKS];
-    float4 bias4[TPW][NJT];
-    int64_t prow[TPW], drow[TPW];
-    bool iv[TPW];
+    if (tid < gg.Lkg) mk = a.kmask ? a.kmask[gg.krow0 + tid] : 1.f;              // (Lkg <= 64: threads 0 .. 63 are stored)
+    bf16x8 kreg[Stage<DKT, 16 * NJT, NTB>::N];
+    stage_ld<DKT, 16 * NJT, NTB>(kreg, ak + gg.krow0 * a.ldk + h * DK, a.ldk, gg.Lkg, tid);
+    TileRows<NJT, NKS> t[TPW];
+    if constexpr (TPW == 1) {
+        t[0] = tile_rows<true, NJT, NKS>(a, gg, g, h, wave * 16, lane, aq, a.ldq, a.bias, a.bias != nullptr);
+    } else {
+        // tile_rows written out: through the shared function the two-tile instances <3,64,2> and <4,32,2> spill 12 and 20 bytes
+        // (profiles/attention_refactor.txt); a wave that runs two tiles loads no bias (see attn16_plan)
 #pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-        const int i = (wave + NWB * t) * 16 + lr;
-        iv[t] = i < Lqg;
-        prow[t] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
-        drow[t] = prow[t];
-        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[t])
-            drow[t] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
+        for (int k = 0; k < TPW; ++k) {
+            const int i = (wave + NWB * k) * 16 + lr, lq = lane >> 4;
+            t[k].iv = i < gg.Lqg;
+            t[k].prow = (((int64_t)g * a.H + h) * a.Lq + i) * a.Lk;
+            t[k].drow = t[k].prow;
+            if (a.drop_p > 0.f && a.drop_rows && a.q_off && t[k].iv)
+                t[k].drow = (((int64_t)g * a.H + h) * a.Lq + ((int64_t)a.drop_rows[gg.qrow0 + i] - (int64_t)g * a.Lq)) * a.Lk;
 #pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
-        if (iv[t]) {
-            const __bf16* qp = aq + qrow0 * a.ldq + h * DK + ((unsigned)i * (unsigned)a.ldq + (unsigned)(8 * lq));
+            for (int ks = 0; ks < NKS; ++ks) t[k].f[ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+            if (t[k].iv) {
+                const __bf16* p = aq + gg.qrow0 * a.ldq + h * DK + row_off<true>(i, a.ldq, 8 * lq);
 #pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) qf[t][ks] = ld_frag(qp + 32 * ks);
+                for (int ks = 0; ks < NKS; ++ks) t[k].f[ks] = ld_frag(p + 32 * ks);
+            }
+            ld_keys4<NJT>(t[k].k4, a.bias, false && t[k].iv, t[k].prow, a.Lk, lq);
         }
-        ld_keys4<NJT>(bias4[t], a.bias, TPW == 1 && a.bias && iv[t], prow[t], Lk, lq);      // (two tiles per wave: no bias, see block_b)
     }
     // ---- the images
-    stageb_st<DKT, KJ>(sV, vreg, KJ, tid);
-    stageb_st<DKT, 16 * NJT>(sK, kreg, 16 * NJT, tid);
+    stage_st<DKT, KJ, NTB>(sV, vreg, KJ, tid);
+    stage_st<DKT, 16 * NJT, NTB>(sK, kreg, 16 * NJT, tid);
     if (tid < 64) sMask[tid] = mk;
     __syncthreads();
     // every wave takes the whole of K as row fragments (what LdsRowFrags would read tile by tile), then the image's bytes are the P images
@@ -467,20 +474,15 @@ __global__ __launch_bounds__(NTB) __attribute__((amdgpu_waves_per_eu(NJT * DKT >
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) kf.f[jt][ks] = frag_row<PD>(sK, 16 * jt + lr, 32 * ks + 8 * lq);
     __syncthreads();
-    // (key columns 16*NJT .. KJ-1 of the P image are never written by a tile)
-    for (int idx = lane; idx < 16 * (KJ / 4); idx += 64)
-        *reinterpret_cast<bf16x4*>(sP + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));
+    zero_cols<PJ, KJ>(sP, 16, lane, 64);
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
 #pragma unroll
-    for (int t = 0; t < TPW; ++t) {
-        const int i0 = (wave + NWB * t) * 16;
-        if (i0 >= Lqg) break;                       // a tile with no row of the group stores nothing
-        if (t) wsync();                             // this tile overwrites the P image
-        fwd16_tile<NJT, DKT, PJ>(a, kf, qf[t], bias4[t], sMask, sV, sP, lane, i0 + lr, iv[t], prow[t], drow[t], qrow0 + i0 + lr, h, inv_keep);
+    for (int k = 0; k < TPW; ++k) {
+        const int i0 = (wave + NWB * k) * 16;
+        if (i0 >= gg.Lqg) break;                    // a tile with no row of the group stores nothing
+        if (k) wsync();                             // this tile overwrites the P image
+        fwd16_tile<NJT, DKT, PJ>(a, kf, t[k].f, t[k].k4, sMask, sV, sP, lane, i0 + lr, t[k].iv, t[k].prow, t[k].drow, gg.qrow0 + i0 + lr, h, inv_keep);
     }
-}
-static size_t fwd16b_lds(int njt, int dk) {
-    return ((size_t)key_kj(njt) * (dk + 8) + std::max((size_t)16 * njt * (dk + 8), (size_t)16 * NWB * key_pj(njt))) * sizeof(__bf16) + 64 * sizeof(float);
 }
 
 // ------------------------------------------------------------------------------------------------ backward
@@ -569,7 +571,7 @@ __device__ __forceinline__ void bwd16_tile2(const ortk_attn_args& a, int t, cons
     }
 }
 
-// The block kernel: one workgroup per (group g, head h); phase 1 with one wave per query tile, phase 2 shared by the waves.
+// The wave-per-tile kernel: one workgroup per (group g, head h); phase 1 with one wave per query tile, phase 2 shared by the waves.
 template <int NJT, typename TQ, int DKT>
 __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int Lqp) {
     constexpr int DK = DKT, PD = DKT + 8;
@@ -577,48 +579,36 @@ __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int L
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
     const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
-    const int Lk = a.Lk, Lq = a.Lq;
     constexpr int KJ = KeyGeo<NJT>::KJ, PJ = KeyGeo<NJT>::PJ;
+    const Bwd16Lds L(NJT, DKT, Lqp);
     __bf16* sK = sm16;                      // [KJ][PD]       rows = key, zero-padded   (k of dS.K: transposing reads)
-    __bf16* sV = sK + KJ * PD;              // [16*NJT][PD]   rows = key                (row fragments of dP^T = V dO^T)
-    __bf16* sQ = sV + 16 * NJT * PD;        // [Lqp][PD]      rows = query              (k of dS^T Q: transposing reads)
-    __bf16* sG = sQ + Lqp * PD;             // [Lqp][PD]      dO: row fragments in phase 1, transposing reads in phase 2
-    __bf16* sS = sG + Lqp * PD;             // [Lqp][PJ]      dS / sqrt(dk): rows = query, columns = key 0..KJ-1
-    __bf16* sD = sS + Lqp * PJ;             // [Lqp][PJ]      dropped P
+    __bf16* sV = sm16 + L.V;                // [16*NJT][PD]   rows = key                (row fragments of dP^T = V dO^T)
+    __bf16* sQ = sm16 + L.Q;                // [Lqp][PD]      rows = query              (k of dS^T Q: transposing reads)
+    __bf16* sG = sm16 + L.G;                // [Lqp][PD]      dO: row fragments in phase 1, transposing reads in phase 2
+    __bf16* sS = sm16 + L.S;                // [Lqp][PJ]      dS / sqrt(dk): rows = query, columns = key 0..KJ-1
+    __bf16* sD = sm16 + L.D;                // [Lqp][PJ]      dropped P (follows sS)
     const int lr = lane & 15, lq = lane >> 4;
-    const int nit = (Lq + 15) >> 4;
-    // ragged groups: see the forward kernel.  Query rows past the group's count are staged as ZERO rows of Q and dO (they are
-    // another group's rows): they add nothing to dK / dV
-    const int64_t qrow0 = a.q_off ? (int64_t)a.q_off[(int64_t)g * a.q_off_stride] : (int64_t)g * Lq;
-    const int Lqg = a.q_off ? min(Lq, (int)(a.q_off[(int64_t)(g + 1) * a.q_off_stride] - qrow0)) : Lq;
-    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
-    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
-    // one 16-row query tile per wave (nw = nit); its saved probabilities are requested before the staging barrier
-    const int it = wave;
-    const int i0 = it * 16, i = i0 + lr;
-    const bool iv = it < nit && i < Lqg;
-    const int64_t prow = (((int64_t)g * a.H + h) * Lq + i) * Lk;
-    const int64_t drow = (a.drop_rows && a.q_off && iv && a.drop_p > 0.f)
-                             ? (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk : prow;
-    float4 praw[NJT];
-    ld_keys4<NJT>(praw, a.p, iv, prow, Lk, lq);
-    stage_rows<DK>(sK, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, KJ, tid, blockDim.x);
-    stage_rows<DK>(sV, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, 16 * NJT, tid, blockDim.x);
-    stage_rows<DK>(sQ, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, Lqp, tid, blockDim.x);
-    stage_rows<DK>(sG, reinterpret_cast<const TQ*>(a.d_o) + qrow0 * a.lddo + h * DK, a.lddo, Lqg, Lqp, tid, blockDim.x);
-    // dS / P images: the key columns 16*NJT .. 63 and the query rows past the last wave tile are never written below
-    for (int idx = tid; idx < 2 * Lqp * (KJ / 4); idx += blockDim.x)
-        *reinterpret_cast<bf16x4*>(sS + (idx / (KJ / 4)) * PJ + (idx % (KJ / 4)) * 4) = cvt4(make_float4(0.f, 0.f, 0.f, 0.f));   // sD follows sS
+    // Query rows past a ragged group's count are staged as ZERO rows of Q and dO (they are another group's rows): they add
+    // nothing to dK / dV
+    const GroupGeo gg = group_geo(a, g);
+    // one 16-row query tile per wave; its saved probabilities are requested before the staging barrier (its dO fragments come
+    // from the image: the inputs may be fp32)
+    const int i = wave * 16 + lr;                   // this lane's query row inside the group (operand row and output row)
+    TileRows<NJT, DK / 32> t = tile_rows<false, NJT, DK / 32>(a, gg, g, h, wave * 16, lane, (const void*)nullptr, 0, a.p, true);
+    stage_rows<DK>(sK, ak + gg.krow0 * a.ldk + h * DK, a.ldk, gg.Lkg, KJ, tid, blockDim.x);
+    stage_rows<DK>(sV, av + gg.krow0 * a.ldv + h * DK, a.ldv, gg.Lkg, 16 * NJT, tid, blockDim.x);
+    stage_rows<DK>(sQ, aq + gg.qrow0 * a.ldq + h * DK, a.ldq, gg.Lqg, Lqp, tid, blockDim.x);
+    stage_rows<DK>(sG, reinterpret_cast<const TQ*>(a.d_o) + gg.qrow0 * a.lddo + h * DK, a.lddo, gg.Lqg, Lqp, tid, blockDim.x);
+    zero_cols<PJ, KJ>(sS, 2 * Lqp, tid, blockDim.x);      // (both images: also the query rows past the last wave tile)
     __syncthreads();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
-    if (it < nit) {
-        bf16x8 gf[DK / 32];
+    if (wave * 16 < a.Lq) {
 #pragma unroll
-        for (int ks = 0; ks < DK / 32; ++ks) gf[ks] = frag_row<PD>(sG, i, 32 * ks + 8 * lq);
-        bwd16_tile1<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sV, lr, lq}, gf, praw, sK, sS, sD, lane, i, iv, prow, drow, qrow0 + i, h, inv_keep);
+        for (int ks = 0; ks < DK / 32; ++ks) t.f[ks] = frag_row<PD>(sG, i, 32 * ks + 8 * lq);
+        bwd16_tile1<NJT, DKT, PJ>(a, LdsRowFrags<PD>{sV, lr, lq}, t.f, t.k4, sK, sS, sD, lane, i, t.iv, t.prow, t.drow, gg.qrow0 + i, h, inv_keep);
     }
     __syncthreads();
-    for (int t = wave; t < 2 * NJT * (DK / 16); t += nw) bwd16_tile2<NJT, DKT, PJ>(a, t, sS, sD, sQ, sG, Lqp, lane, Lkg, krow0, h);
+    for (int k = wave; k < 2 * NJT * (DK / 16); k += nw) bwd16_tile2<NJT, DKT, PJ>(a, k, sS, sD, sQ, sG, Lqp, lane, gg.Lkg, gg.krow0, h);
 }
 
 // The short kernel: the mapping of attn16s_fwd_kernel.  One wave runs phase 1 for the query tiles that hold rows of its group,
@@ -627,11 +617,10 @@ __global__ __launch_bounds__(512) void attn16_bwd_kernel(ortk_attn_args a, int L
 // transposing read needs next: K for dQ, then Q for the dK tiles, then dO for the dV tiles (Q and dO wait in registers, where
 // their loads left them): 9 728 B at dk = 64, 16 waves per compute unit.  Key tiles past the group's keys (a caption of at most
 // 16 rows: tile 1) have no row of dK / dV to store and are skipped.
-template <int DKT> constexpr int bwd16s_wave_elems() { return 32 * (DKT + 8) + 2 * 32 * PJS; }
 template <int NJT, int DKT>
 __global__ __launch_bounds__(512) void attn16s_bwd_kernel(ortk_attn_args a) {
     static_assert(NJT <= 2, "the short kernels serve at most 32 keys");
-    constexpr int DK = DKT, PD = DKT + 8, NKS = DKT / 32, LQP = 32;
+    constexpr int DK = DKT, NKS = DKT / 32, LQP = 32;
     const __bf16* aq = reinterpret_cast<const __bf16*>(a.q); const __bf16* ak = reinterpret_cast<const __bf16*>(a.k); const __bf16* av = reinterpret_cast<const __bf16*>(a.v);
     const __bf16* ag = reinterpret_cast<const __bf16*>(a.d_o);
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
@@ -639,73 +628,44 @@ __global__ __launch_bounds__(512) void attn16s_bwd_kernel(ortk_attn_args a) {
     const int pair = blockIdx.x * W + wave;
     if (pair >= a.nkv * a.H) return;                // the last workgroup may be partly empty (no workgroup barrier below)
     const int g = pair / a.H, h = pair - g * a.H;
-    const int Lk = a.Lk, Lq = a.Lq;
-    __bf16* sX = sm16 + wave * bwd16s_wave_elems<DKT>();       // [32][PD]    K (rows = key), then Q, then dO (rows = query); zero-padded
-    __bf16* sS = sX + 32 * PD;                                 // [LQP][PJS]  dS / sqrt(dk)
-    __bf16* sD = sS + LQP * PJS;                               // [LQP][PJS]  dropped P
-    const int lr = lane & 15, lq = lane >> 4;
-    int64_t qrow0 = (int64_t)g * Lq;
-    int Lqg = Lq;
-    if (a.q_off) {
-        const int o0 = a.q_off[(int64_t)g * a.q_off_stride], o1 = a.q_off[(int64_t)(g + 1) * a.q_off_stride];
-        qrow0 = o0; Lqg = min(Lq, o1 - o0);
-    }
-    const int64_t krow0 = (a.q_off && a.kv_ragged) ? qrow0 : (int64_t)g * Lk;
-    const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
+    constexpr Bwd16sLds L(DKT);
+    __bf16* sX = sm16 + wave * L.end;                          // [32][PD]    K (rows = key), then Q, then dO (rows = query); zero-padded
+    __bf16* sS = sX + L.S;                                     // [LQP][PJS]  dS / sqrt(dk)
+    __bf16* sD = sX + L.D;                                     // [LQP][PJS]  dropped P (follows sS)
+    const int lr = lane & 15;
+    const GroupGeo gg = group_geo(a, g);
     // ---- every global load of the wave: what phase 1 consumes from registers first, then the three staged images
     RegRowFrags<NJT, NKS> vf;
-    ld_row_frags<NJT, NKS>(vf, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
-    bf16x8 gf[2][NKS];
-    float4 praw[2][NJT];
-    int64_t prow[2], drow[2];
-    bool iv[2];
+    ld_row_frags<false>(vf, av + gg.krow0 * a.ldv + h * DK, a.ldv, gg.Lkg, lane);
+    TileRows<NJT, NKS> t[2];
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int i = it * 16 + lr;
-        iv[it] = i < Lqg;
-        prow[it] = (((int64_t)g * a.H + h) * Lq + i) * Lk;
-        drow[it] = prow[it];
-        if (a.drop_p > 0.f && a.drop_rows && a.q_off && iv[it])
-            drow[it] = (((int64_t)g * a.H + h) * Lq + ((int64_t)a.drop_rows[qrow0 + i] - (int64_t)g * Lq)) * Lk;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) gf[it][ks] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};      // (a zero row of the dO image)
-        if (iv[it]) {
-            const __bf16* gp = ag + (qrow0 + i) * a.lddo + h * DK + 8 * lq;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) gf[it][ks] = ld_frag(gp + 32 * ks);
-        }
-        ld_keys4<NJT>(praw[it], a.p, iv[it], prow[it], Lk, lq);
-    }
-    bf16x8 kreg[DKT / 16], qreg[DKT / 16], greg[DKT / 16];
-    stage32_ld<DKT>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, lane);
-    stage32_ld<DKT>(qreg, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, lane);
-    stage32_ld<DKT>(greg, ag + qrow0 * a.lddo + h * DK, a.lddo, Lqg, lane);
-    // ---- the wave's LDS region.  dS / P images: key columns 16*NJT .. KJS-1 and the rows of a tile that is not run stay zero
-    for (int idx = lane; idx < 2 * LQP * PJS / 8; idx += 64)
-        *reinterpret_cast<bf16x8*>(sS + idx * 8) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};           // sD follows sS
-    stage32_st<DKT>(sX, kreg, lane);
+    for (int it = 0; it < 2; ++it) t[it] = tile_rows<false, NJT, NKS>(a, gg, g, h, it * 16, lane, ag, a.lddo, a.p, true);
+    bf16x8 kreg[Stage<DKT, 32, 64>::N], qreg[Stage<DKT, 32, 64>::N], greg[Stage<DKT, 32, 64>::N];
+    stage_ld<DKT, 32, 64>(kreg, ak + gg.krow0 * a.ldk + h * DK, a.ldk, gg.Lkg, lane);
+    stage_ld<DKT, 32, 64>(qreg, aq + gg.qrow0 * a.ldq + h * DK, a.ldq, gg.Lqg, lane);
+    stage_ld<DKT, 32, 64>(greg, ag + gg.qrow0 * a.lddo + h * DK, a.lddo, gg.Lqg, lane);
+    // ---- the wave's LDS region
+    zero_cols<PJS, PJS>(sS, 2 * LQP, lane, 64);
+    stage_st<DKT, 32, 64>(sX, kreg, 32, lane);
     wsync();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
-        if (it * 16 >= Lqg) break;                  // a tile with no row of the group: zero rows of dS / P, nothing stored
-        bwd16_tile1<NJT, DKT, PJS>(a, vf, gf[it], praw[it], sX, sS, sD, lane, it * 16 + lr, iv[it], prow[it], drow[it],
-                                   qrow0 + it * 16 + lr, h, inv_keep);
+        if (it * 16 >= gg.Lqg) break;               // a tile with no row of the group: zero rows of dS / P, nothing stored
+        bwd16_tile1<NJT, DKT, PJS>(a, vf, t[it].f, t[it].k4, sX, sS, sD, lane, it * 16 + lr, t[it].iv, t[it].prow, t[it].drow,
+                                   gg.qrow0 + it * 16 + lr, h, inv_keep);
     }
     // phase 2: tile t = (which, jt, dt); which = 0 the dK tiles (dS, Q), 1 the dV tiles (dropped P, dO)
     constexpr int NDT = DK / 16;
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         wsync();                                    // the image's readers (dQ; the dK tiles) are done, and dS / P are whole
-        stage32_st<DKT>(sX, which == 0 ? qreg : greg, lane);
+        stage_st<DKT, 32, 64>(sX, which == 0 ? qreg : greg, 32, lane);
         wsync();
-        for (int jt = 0; jt < NJT && 16 * jt < Lkg; ++jt)
+        for (int jt = 0; jt < NJT && 16 * jt < gg.Lkg; ++jt)
             for (int dt = 0; dt < NDT; ++dt)
-                bwd16_tile2<NJT, DKT, PJS>(a, (which * NJT + jt) * NDT + dt, sS, sD, sX, sX, LQP, lane, Lkg, krow0, h);
+                bwd16_tile2<NJT, DKT, PJS>(a, (which * NJT + jt) * NDT + dt, sS, sD, sX, sX, LQP, lane, gg.Lkg, gg.krow0, h);
     }
-}
-static size_t bwd16_lds(int njt, int Lqp, int dk) {
-    return ((size_t)(key_kj(njt) + 16 * njt + 2 * Lqp) * (dk + 8) + (size_t)2 * Lqp * key_pj(njt)) * sizeof(__bf16);
 }
 
 // The second mapping of the block backward (see attn16b_fwd_kernel): the layout of attn16s_bwd_kernel, workgroup-wide.  V and dO
@@ -724,6 +684,9 @@ __global__ __launch_bounds__(NTB) void attn16b_bwd_kernel(ortk_attn_args a, int 
     extern __shared__ __attribute__((aligned(16))) __bf16 sm16[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
+    // This kernel keeps its own spelling of the geometry (group_geo), the row setup (tile_rows), the image clear (zero_cols) and the
+    // carve (Bwd16bLds, which attn16_plan sizes the launch by): with the shared pieces its instance <1,32,2> went from 74 to 78
+    // registers and from 6 to 5 waves per SIMD, whichever of them was tried alone (profiles/attention_refactor.txt).
     const int Lk = a.Lk, Lq = a.Lq;
     __bf16* sX = sm16;                              // [max(KJ, Lqp)][PD]  K (rows = key), then Q, then dO (rows = query); zero-padded
     __bf16* sS = sX + max(KJ, Lqp) * PD;            // [Lqp][PJ]           dS / sqrt(dk)
@@ -739,7 +702,7 @@ __global__ __launch_bounds__(NTB) void attn16b_bwd_kernel(ortk_attn_args a, int 
     const int Lkg = (a.q_off && a.kv_ragged) ? min(Lk, Lqg) : Lk;
     // ---- every global load of the workgroup: what phase 1 consumes from registers first, then the three staged images
     RegRowFrags<NJT, NKS> vf;
-    ld_row_fragsb<NJT, NKS>(vf, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
+    ld_row_frags<true>(vf, av + krow0 * a.ldv + h * DK, a.ldv, Lkg, lane);
     bf16x8 gf[TPW][NKS];
     float4 praw[TPW][NJT];
     int64_t prow[TPW], drow[TPW];
@@ -761,14 +724,14 @@ __global__ __launch_bounds__(NTB) void attn16b_bwd_kernel(ortk_attn_args a, int 
         }
         ld_keys4<NJT>(praw[t], a.p, iv[t], prow[t], Lk, lq);
     }
-    bf16x8 kreg[StageB<DKT, KJ>::N], qreg[StageB<DKT, LQM>::N], greg[StageB<DKT, LQM>::N];
-    stageb_ld<DKT, KJ>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, tid);
-    stageb_ld<DKT, LQM>(qreg, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, tid);
-    stageb_ld<DKT, LQM>(greg, ag + qrow0 * a.lddo + h * DK, a.lddo, Lqg, tid);
+    bf16x8 kreg[Stage<DKT, KJ, NTB>::N], qreg[Stage<DKT, LQM, NTB>::N], greg[Stage<DKT, LQM, NTB>::N];
+    stage_ld<DKT, KJ, NTB>(kreg, ak + krow0 * a.ldk + h * DK, a.ldk, Lkg, tid);
+    stage_ld<DKT, LQM, NTB>(qreg, aq + qrow0 * a.ldq + h * DK, a.ldq, Lqg, tid);
+    stage_ld<DKT, LQM, NTB>(greg, ag + qrow0 * a.lddo + h * DK, a.lddo, Lqg, tid);
     // ---- the images.  dS / P: key columns 16*NJT .. KJ-1 and the rows of a tile that is not run stay zero
     for (int idx = tid; idx < 2 * Lqp * PJ / 8; idx += NTB)
         *reinterpret_cast<bf16x8*>(sS + idx * 8) = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};           // sD follows sS
-    stageb_st<DKT, KJ>(sX, kreg, KJ, tid);
+    stage_st<DKT, KJ, NTB>(sX, kreg, KJ, tid);
     __syncthreads();
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
 #pragma unroll
@@ -783,138 +746,73 @@ __global__ __launch_bounds__(NTB) void attn16b_bwd_kernel(ortk_attn_args a, int 
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         __syncthreads();                            // the image's readers (dQ; the dK tiles) are done, and dS / P are whole
-        stageb_st<DKT, LQM>(sX, which == 0 ? qreg : greg, Lqp, tid);
+        stage_st<DKT, LQM, NTB>(sX, which == 0 ? qreg : greg, Lqp, tid);
         __syncthreads();
         for (int t = wave; t < NT2; t += NWB) bwd16_tile2<NJT, DKT, PJ>(a, which * NT2 + t, sS, sD, sX, sX, Lq2, lane, Lkg, krow0, h);
     }
 }
-static size_t bwd16b_lds(int njt, int Lqp, int dk) {
-    return ((size_t)std::max(key_kj(njt), Lqp) * (dk + 8) + (size_t)2 * Lqp * key_pj(njt)) * sizeof(__bf16);
-}
+// ------------------------------------------------------------------------------------------------ host side: this family's part of the plan
+using ortk::aligned; using ortk::aligned16; using ortk::ld_multiple; using ortk::AttnInst;
+typedef float f32; typedef __bf16 bf16;      // element types as the instance names spell them
+#define INST(...) ORTK_ATTN_INST(, __VA_ARGS__)
+#define ROW8(family, TQ, DK) {INST(family, 1,TQ,DK), INST(family, 2,TQ,DK), INST(family, 3,TQ,DK), INST(family, 4,TQ,DK), \
+                              INST(family, 5,TQ,DK), INST(family, 6,TQ,DK), INST(family, 7,TQ,DK), INST(family, 8,TQ,DK)}
+#define ROW4(family, DK, TPW) {INST(family, 1,DK,TPW), INST(family, 2,DK,TPW), INST(family, 3,DK,TPW), INST(family, 4,DK,TPW)}
+// every instance, [backward][dk == 32]...[key tiles - 1]
+const AttnInst WAVE_TILE[2][2][2][8] = {{{ROW8(attn16_fwd, f32,64), ROW8(attn16_fwd, bf16,64)}, {ROW8(attn16_fwd, f32,32), ROW8(attn16_fwd, bf16,32)}},      // [qkv_dtype]
+                                        {{ROW8(attn16_bwd, f32,64), ROW8(attn16_bwd, bf16,64)}, {ROW8(attn16_bwd, f32,32), ROW8(attn16_bwd, bf16,32)}}};
+const AttnInst BLOCK[2][2][2][4] = {{{ROW4(attn16b_fwd, 64,1), ROW4(attn16b_fwd, 64,2)}, {ROW4(attn16b_fwd, 32,1), ROW4(attn16b_fwd, 32,2)}},                // [tiles per wave - 1]
+                                    {{ROW4(attn16b_bwd, 64,1), ROW4(attn16b_bwd, 64,2)}, {ROW4(attn16b_bwd, 32,1), ROW4(attn16b_bwd, 32,2)}}};
+const AttnInst SHORT[2][2][2] = {{{INST(attn16s_fwd, 1,64), INST(attn16s_fwd, 2,64)}, {INST(attn16s_fwd, 1,32), INST(attn16s_fwd, 2,32)}},
+                                 {{INST(attn16s_bwd, 1,64), INST(attn16s_bwd, 2,64)}, {INST(attn16s_bwd, 1,32), INST(attn16s_bwd, 2,32)}}};
+#undef ROW4
+#undef ROW8
+#undef INST
+static_assert(lds_bytes(Bwd16Lds(8, 64, 128)) <= 160 * 1024, "every served shape fits the LDS of a compute unit");
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// layouts these kernels serve (everything else stays with the fp32-MFMA family)
+bool attn16_ok(const ortk_attn_args& a, bool bwd) {
+    // fp32 inputs: only the block shapes (the register-only kernels keep the short ones); bf16 inputs: every served shape
+    // (short query blocks over at most 48 keys stay with the register-only kernels; past 48 keys those do not apply)
+    if (a.precision != 1 || !ortk::attn16_shape_ok(a.Lq, a.Lk, a.dk) || (a.qkv_dtype == 0 && a.Lq < ortk::tuning().attn16_min_lq && a.Lk <= 48)) return false;
+    if (a.kv_index || a.kv_group_stride > 0 || a.kv_dtype != 0 || a.k_new || a.v_new) return false;
+    if (a.q_off && (a.qkv_dtype != 1 || a.q_off_stride < 1)) return false;
+    const int in_ld = a.qkv_dtype ? 8 : 4;          // input rows (Q, K, V, dO) start 16-byte aligned
+    if (!ld_multiple(in_ld, a.ldq, a.ldk, a.ldv) || !aligned16(a.q, a.k, a.v)) return false;
+    if (!bwd) return ld_multiple(4, a.ldo) && aligned(a.o, a.o_dtype == ORTK_BF16 ? 8 : 16) && aligned16(a.p, a.bias);
+    if (!a.p || !a.d_o || !a.dq || !a.d_k || !a.dv) return false;
+    const size_t eg4 = a.dqkv_dtype == ORTK_BF16 ? 8 : 16;
+    return ld_multiple(in_ld, a.lddo) && ld_multiple(4, a.lddq, a.lddk, a.lddv) && aligned16(a.d_o, a.p, a.dscore) &&
+           aligned(a.dq, eg4) && aligned(a.d_k, eg4) && aligned(a.dv, eg4);
+}
 
 }  // namespace
 
 namespace ortk {
 
-// shapes / layouts these kernels serve (everything else stays with the fp32-MFMA family)
+// shapes these kernels serve
 bool attn16_shape_ok(int Lq, int Lk, int dk) { return (dk == 64 || dk == 32) && Lk >= 1 && Lk <= 128 && Lq >= 1 && Lq <= 128; }
 
-bool attn16_ok(const ortk_attn_args* a, bool bwd) {
-    // fp32 inputs: only the block shapes (the register-only kernels keep the short ones); bf16 inputs: every served shape
-    const int min_lq = ortk::tuning().attn16_min_lq;
-    // (short query blocks over at most 48 keys stay with the register-only kernels; past 48 keys those do not apply)
-    if (a->precision != 1 || !attn16_shape_ok(a->Lq, a->Lk, a->dk) || (a->qkv_dtype == 0 && a->Lq < min_lq && a->Lk <= 48)) return false;
-    if (a->kv_index || a->kv_group_stride > 0 || a->kv_dtype != 0 || a->k_new || a->v_new) return false;
-    if (a->q_off && (a->qkv_dtype != 1 || a->q_off_stride < 1)) return false;
-    if ((a->ldq | a->ldk | a->ldv) % (a->qkv_dtype ? 8 : 4) || !al16(a->q) || !al16(a->k) || !al16(a->v)) return false;
-    if (!bwd) {
-        const int64_t eo = a->o_dtype == ORTK_BF16 ? 2 : 4;
-        if (a->ldo % 4 || (reinterpret_cast<uintptr_t>(a->o) % (4 * eo)) || (a->p && !al16(a->p)) || (a->bias && !al16(a->bias))) return false;
+bool attn16_plan(const ortk_attn_args& a, bool bwd, AttnPlan& pl) {
+    if (!attn16_ok(a, bwd)) return false;
+    const int njt = (a.Lk + 15) / 16, nw = (a.Lq + 15) / 16, Lqp = (int)ortk_align(a.Lq, 32), d32 = a.dk == 32, sw = tuning().attn16_short;
+    const int64_t pairs = (int64_t)a.nkv * a.H;
+    auto add = [&](AttnInst k, int64_t grid, int block, size_t lds) { pl.add(k, grid, block, lds, lds > 64 * 1024 ? 160 * 1024 : 0, Lqp); };
+    if (sw && a.qkv_dtype == 1 && a.Lq <= 32 && a.Lk <= 32) {
+        // The short kernels (one wave per (group, head)): bf16 Q / K / V / dO, at most 32 query rows and 32 keys per group
+        // (ortk_tuning.attn16_short: 0 never | 1 the default width of 4 waves per workgroup | 4, 8 that width)
+        const int W = sw == 8 ? 8 : 4;
+        add(SHORT[bwd][d32][njt - 1], ortk_cdiv(pairs, W), 64 * W, W * (bwd ? lds_bytes(Bwd16sLds(a.dk)) : lds_bytes(Fwd16sLds(a.dk))));
+    } else if (tuning().attn16_block && a.qkv_dtype == 1 && a.Lk <= 64 && a.Lq <= 16 * NWB * 2 && (a.Lq <= 16 * NWB || !a.bias)) {
+        // The block kernels (ortk_tuning.attn16_block: 1 | 0 never): bf16 Q / K / V / dO, at most 64 keys and 96 query rows: nw
+        // query tiles on NWB waves, one each or two.  A biased block of more than 48 query rows stays with the wave-per-tile kernels:
+        // the two bias rows of a wave that runs two tiles do not fit its registers, and the step has no such block.
+        add(BLOCK[bwd][d32][nw > NWB][njt - 1], pairs, NTB, bwd ? lds_bytes(Bwd16bLds(njt, a.dk, Lqp)) : lds_bytes(Fwd16bLds(njt, a.dk)));
     } else {
-        const int64_t eg = a->dqkv_dtype == ORTK_BF16 ? 2 : 4;
-        if (!a->p || !a->d_o || !a->dq || !a->d_k || !a->dv) return false;
-        if ((a->lddo % (a->qkv_dtype ? 8 : 4)) || (a->lddq | a->lddk | a->lddv) % 4 || !al16(a->d_o) || !al16(a->p) || (a->dscore && !al16(a->dscore))) return false;
-        if ((reinterpret_cast<uintptr_t>(a->dq) | reinterpret_cast<uintptr_t>(a->d_k) | reinterpret_cast<uintptr_t>(a->dv)) % (4 * eg)) return false;
+        add(WAVE_TILE[bwd][d32][a.qkv_dtype != 0][njt - 1], pairs, 64 * nw, bwd ? lds_bytes(Bwd16Lds(njt, a.dk, Lqp)) : lds_bytes(Fwd16Lds(njt, a.dk, nw)));
     }
     return true;
 }
 
-typedef void (*fwd16_fn)(ortk_attn_args);
-typedef void (*bwd16_fn)(ortk_attn_args, int);
-template <typename TQ, int DKT> static fwd16_fn pick_fwd(int njt) {
-    switch (njt) {
-        case 1: return attn16_fwd_kernel<1, TQ, DKT>; case 2: return attn16_fwd_kernel<2, TQ, DKT>; case 3: return attn16_fwd_kernel<3, TQ, DKT>;
-        case 4: return attn16_fwd_kernel<4, TQ, DKT>; case 5: return attn16_fwd_kernel<5, TQ, DKT>; case 6: return attn16_fwd_kernel<6, TQ, DKT>;
-        case 7: return attn16_fwd_kernel<7, TQ, DKT>; default: return attn16_fwd_kernel<8, TQ, DKT>;
-    }
-}
-template <typename TQ, int DKT> static bwd16_fn pick_bwd(int njt) {
-    switch (njt) {
-        case 1: return attn16_bwd_kernel<1, TQ, DKT>; case 2: return attn16_bwd_kernel<2, TQ, DKT>; case 3: return attn16_bwd_kernel<3, TQ, DKT>;
-        case 4: return attn16_bwd_kernel<4, TQ, DKT>; case 5: return attn16_bwd_kernel<5, TQ, DKT>; case 6: return attn16_bwd_kernel<6, TQ, DKT>;
-        case 7: return attn16_bwd_kernel<7, TQ, DKT>; default: return attn16_bwd_kernel<8, TQ, DKT>;
-    }
-}
-
-// The short kernels (one wave per (group, head)): bf16 Q / K / V / dO, at most 32 query rows and 32 keys per group.  Returns the
-// waves per workgroup, 0 = the block kernels (ortk_tuning.attn16_short: 0 never | 1 the default width | 4, 8 that width).
-static int short_waves(const ortk_attn_args* a) {
-    const int sw = ortk::tuning().attn16_short;
-    if (!sw || a->qkv_dtype != 1 || a->Lq > 32 || a->Lk > 32) return 0;
-    return sw == 8 ? 8 : 4;
-}
-// The second mapping of the block kernels (attn16b_*): bf16 Q / K / V / dO, at most 64 keys and 96 query rows, where the short
-// kernels do not apply (ortk_tuning.attn16_block: 1 | 0 the one-wave-per-query-tile kernels).  A biased block of more than 48 query
-// rows stays with those too: the two bias rows of a wave that runs two tiles do not fit its registers, and the step has no such block.
-static bool block_b(const ortk_attn_args* a) {
-    return ortk::tuning().attn16_block && a->qkv_dtype == 1 && a->Lk <= 64 && a->Lq <= 16 * NWB * 2 && (a->Lq <= 16 * NWB || !a->bias);
-}
-template <int DKT, int TPW> static fwd16_fn pick_fwd_b(int njt) {
-    switch (njt) {
-        case 1: return attn16b_fwd_kernel<1, DKT, TPW>; case 2: return attn16b_fwd_kernel<2, DKT, TPW>;
-        case 3: return attn16b_fwd_kernel<3, DKT, TPW>; default: return attn16b_fwd_kernel<4, DKT, TPW>;
-    }
-}
-template <int DKT, int TPW> static bwd16_fn pick_bwd_b(int njt) {
-    switch (njt) {
-        case 1: return attn16b_bwd_kernel<1, DKT, TPW>; case 2: return attn16b_bwd_kernel<2, DKT, TPW>;
-        case 3: return attn16b_bwd_kernel<3, DKT, TPW>; default: return attn16b_bwd_kernel<4, DKT, TPW>;
-    }
-}
-template <typename FN> static int launch_short(FN fn, size_t wave_bytes, int W, const ortk_attn_args* a, hipStream_t s) {
-    const size_t lds = wave_bytes * W;
-    const int64_t pairs = (int64_t)a->nkv * a->H;
-    if (lds > 64 * 1024) ortk::lds_attr(reinterpret_cast<const void*>(fn), 160 * 1024);
-    hipLaunchKernelGGL(fn, dim3((unsigned)((pairs + W - 1) / W)), dim3(64 * W), lds, s, *a);
-    ORTK_CHECK_LAUNCH();
-    return 0;
-}
-
-int attn16_fwd(const ortk_attn_args* a, hipStream_t s) {
-    if (const int W = short_waves(a)) {
-        const bool two = a->Lk > 16;
-        const fwd16_fn fn = a->dk == 64 ? (two ? attn16s_fwd_kernel<2, 64> : attn16s_fwd_kernel<1, 64>) : (two ? attn16s_fwd_kernel<2, 32> : attn16s_fwd_kernel<1, 32>);
-        return launch_short(fn, (a->dk == 64 ? fwd16s_wave_elems<64>() : fwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
-    }
-    const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16;
-    if (block_b(a)) {                               // nw query tiles on NWB waves: one each, or two
-        const fwd16_fn fn = a->dk == 64 ? (nw <= NWB ? pick_fwd_b<64, 1>(njt) : pick_fwd_b<64, 2>(njt)) : (nw <= NWB ? pick_fwd_b<32, 1>(njt) : pick_fwd_b<32, 2>(njt));
-        hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(NTB), fwd16b_lds(njt, a->dk), s, *a);
-        ORTK_CHECK_LAUNCH();
-        return 0;
-    }
-    const fwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_fwd<__bf16, 64>(njt) : pick_fwd<float, 64>(njt))
-                                    : (a->qkv_dtype ? pick_fwd<__bf16, 32>(njt) : pick_fwd<float, 32>(njt));
-    const size_t lds = fwd16_lds(njt, nw, a->dk);
-    if (lds > 64 * 1024) ortk::lds_attr(reinterpret_cast<const void*>(fn), 160 * 1024);
-    hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(64 * nw), lds, s, *a);
-    ORTK_CHECK_LAUNCH();
-    return 0;
-}
-
-int attn16_bwd(const ortk_attn_args* a, hipStream_t s) {
-    if (const int W = short_waves(a)) {
-        const bool two = a->Lk > 16;
-        const fwd16_fn fn = a->dk == 64 ? (two ? attn16s_bwd_kernel<2, 64> : attn16s_bwd_kernel<1, 64>) : (two ? attn16s_bwd_kernel<2, 32> : attn16s_bwd_kernel<1, 32>);
-        return launch_short(fn, (a->dk == 64 ? bwd16s_wave_elems<64>() : bwd16s_wave_elems<32>()) * sizeof(__bf16), W, a, s);
-    }
-    const int njt = (a->Lk + 15) / 16, nw = (a->Lq + 15) / 16, Lqp = (int)ortk_align(a->Lq, 32);
-    if (block_b(a)) {
-        const bwd16_fn fn = a->dk == 64 ? (nw <= NWB ? pick_bwd_b<64, 1>(njt) : pick_bwd_b<64, 2>(njt)) : (nw <= NWB ? pick_bwd_b<32, 1>(njt) : pick_bwd_b<32, 2>(njt));
-        hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(NTB), bwd16b_lds(njt, Lqp, a->dk), s, *a, Lqp);
-        ORTK_CHECK_LAUNCH();
-        return 0;
-    }
-    const bwd16_fn fn = a->dk == 64 ? (a->qkv_dtype ? pick_bwd<__bf16, 64>(njt) : pick_bwd<float, 64>(njt))
-                                    : (a->qkv_dtype ? pick_bwd<__bf16, 32>(njt) : pick_bwd<float, 32>(njt));
-    const size_t lds = bwd16_lds(njt, Lqp, a->dk);
-    if (lds > 160 * 1024) return ORTK_EINVAL;
-    if (lds > 64 * 1024) ortk::lds_attr(reinterpret_cast<const void*>(fn), 160 * 1024);
-    hipLaunchKernelGGL(fn, dim3((unsigned)(a->nkv * a->H)), dim3(64 * nw), lds, s, *a, Lqp);
-    ORTK_CHECK_LAUNCH();
-    return 0;
-}
-
 }  // namespace ortk
+

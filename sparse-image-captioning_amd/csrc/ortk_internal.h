@@ -31,11 +31,32 @@ unsigned long long* prof_slot(int* index);
 int kv_append(const float* qkv, void* cache_k, void* cache_v, int32_t kv_dtype, int64_t rows, int32_t d, int32_t row_mult, int32_t tmax,
               int32_t t, hipStream_t s);
 
-// bf16-MFMA attention (ortk_attn16.hip): whether the call's shapes / layouts are served, and the launchers
+// The attention operator's dispatch plan (ortk_attn.hip: plan_attention builds it, attn_launch runs it, ortk_attention_plan prints it).
+// A launch is what the launch tail needs and nothing else: every attention kernel takes (ortk_attn_args, up to three ints), and
+// hipLaunchKernel reads as many as the kernel has parameters.  lds_limit: the dynamic-LDS limit the function needs raised (0: none).
+struct AttnLaunch { const void* fn; const char* name; unsigned grid, block; size_t lds, lds_limit; int a0, a1, a2; };
+// A kernel instance and the name the plan reports for it: the family without its attn_ / _kernel affixes and the template arguments
+// (element types as f32 / bf16), both formed from ONE text so that they cannot drift apart: ORTK_ATTN_INST(attn_, small_fwd, 1,3,bf16)
+// is attn_small_fwd_kernel<1,3,bf16> under the name "small_fwd<1,3,bf16>".  (The arguments are written without spaces.)
+struct AttnInst { const void* fn; const char* name; };
+#define ORTK_ATTN_INST(prefix, family, ...) \
+    ortk::AttnInst{reinterpret_cast<const void*>(prefix##family##_kernel<__VA_ARGS__>), #family "<" #__VA_ARGS__ ">"}
+#define ORTK_ATTN_INST0(prefix, family) ortk::AttnInst{reinterpret_cast<const void*>(prefix##family##_kernel), #family}
+struct AttnPlan {
+    AttnLaunch l[2]; int n = 0;      // two launches: attn_kv_append_kernel, then the attention kernel (which then sees no k_new / v_new)
+    void add(AttnInst k, int64_t grid, int block, size_t lds, size_t lds_limit = 0, int a0 = 0, int a1 = 0, int a2 = 0) {
+        l[n++] = AttnLaunch{k.fn, k.name, (unsigned)grid, (unsigned)block, lds, lds_limit, a0, a1, a2};
+    }
+};
+// The alignment and stride predicates of the attention kernels' vector accesses: every pointer a multiple of 16 bytes (NULL counts
+// as aligned); one pointer a multiple of `bytes`; every leading dimension a multiple of m elements (m a power of two)
+template <typename... P> inline bool aligned16(const P*... p) { return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0; }
+inline bool aligned(const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+template <typename... L> inline bool ld_multiple(int m, L... ld) { return ((int64_t)(ld | ...) & (m - 1)) == 0; }
+// bf16-MFMA attention (ortk_attn16.hip): the shapes it serves, and its part of plan_attention — false: the call is not served
+// (shape, layout, alignment or tuning), nothing added
 bool attn16_shape_ok(int Lq, int Lk, int dk);
-bool attn16_ok(const ortk_attn_args* a, bool bwd);
-int attn16_fwd(const ortk_attn_args* a, hipStream_t s);
-int attn16_bwd(const ortk_attn_args* a, hipStream_t s);
+bool attn16_plan(const ortk_attn_args& a, bool bwd, AttnPlan& pl);
 
 // bf16 TRANSPOSED copies of weight blocks: block i is an (N, K) row-major fp32 matrix at x + off; yt + off receives it as
 // (K, N) row-major bf16 (the data-gradient GEMM dX = dY W then runs in the forward operand layout, on the LDS-DMA kernels)

@@ -145,12 +145,14 @@ def run_case(L, nkv, H, Lq, Lk, dk, causal=0, use_bias=False, kmask=None, precis
     assert torch.isnan(oc[Mq:].float()).all(), "O: rows past the last group were written"
     for g in range(nkv):
         nq, nk = len(qrows[g]), len(krows[g])
+        assert torch.isnan(pc[g, :, nq:, :]).all(), f"P[{g}]: rows past the group's count were written"
+        if nq == 0:         # (a ragged group without rows: nothing else to compare)
+            continue
         blk = pc[g, :, :nq, :]
         close(blk[:, :, :nk], ref["p"][g], precision, atol=1e-5, what=f"P[{g}]")
         assert (blk[:, :, :nk][ref["masked"][g][None].expand(H, -1, -1)] == 0).all(), f"P[{g}]: a masked or causal-future key has P != 0"
         assert (blk[:, :, nk:] == 0).all(), f"P[{g}]: a key the group does not own has P != 0"
         assert (blk.double().sum(-1) - 1).abs().max().item() < 1e-5, f"P[{g}]: rows do not sum to 1"
-        assert torch.isnan(pc[g, :, nq:, :]).all(), f"P[{g}]: rows past the group's count were written"
     out = {"o": oc[:Mq], "p": pc, "ref": ref, "keep": keep_all, "args": a, "hold": hold}
     if not bwd:
         return out
@@ -172,10 +174,18 @@ def run_case(L, nkv, H, Lq, Lk, dk, causal=0, use_bias=False, kmask=None, precis
     dsc = ds.cpu()
     for g in range(nkv):
         nq, nk = len(qrows[g]), len(krows[g])
+        if nq == 0:
+            continue
         close(dsc[g, :, :nq, :nk], ref["ds"][g], precision, what=f"dscore[{g}]")
         assert (dsc[g, :, :nq, nk:] == 0).all(), f"dscore[{g}]: a key the group does not own has a gradient"
     out.update(dq=dq.cpu()[:Mq], dk=dk_.cpu()[:Mk], dv=dv.cpu()[:Mk], ds=dsc)
     return out
+
+
+def families(L, out, bwd=False):
+    """The kernel families ortk_attention_plan names for the arguments of a run_case result, under the tuning values of the moment:
+    ["fwd_mfma"], ["attn16b_bwd"], ..."""
+    return [k.split(":")[0].split("<")[0] for k in L.attention_plan(out["args"], bwd)]
 
 
 def recover_keep(L, out, nkv, H, Lq, Lk, dk, in_dt=0):
@@ -337,6 +347,7 @@ def test_wave_kernels(L, nkv, H, Lq, Lk, dk, causal, bias, drop):
     """attn_impl = 1: attn_fwd_wave_kernel and attn_bwd_wave_kernel<32 | 48 | 64>."""
     with forced(L, 1):
         out = run_case(L, nkv, H, Lq, Lk, dk, causal=causal, use_bias=bias, kmask=_tail_mask(nkv, Lk), drop_p=drop, drop_seed=9)
+        assert families(L, out) == (["fwd_wave"] if Lk <= 64 else ["fwd"]) and families(L, out, True) == (["bwd_wave"] if Lk <= 64 else ["bwd"])
         if drop:
             assert_mask_is_the_hash(L, out, nkv, H, Lq, Lk, dk)
 
@@ -350,6 +361,7 @@ def test_fp32_mfma_kernels_on_short_query_blocks(L, nkv, H, Lq, Lk, dk, causal, 
     """attn_impl = 3: the fp32-MFMA block kernels below their automatic threshold of 33 query rows."""
     with forced(L, 3):
         out = run_case(L, nkv, H, Lq, Lk, dk, causal=causal, use_bias=True, kmask=_tail_mask(nkv, Lk), drop_p=drop, drop_seed=11)
+        assert families(L, out) == ["fwd_mfma"] and families(L, out, True) == ["bwd_mfma"]
         if drop:
             assert_mask_is_the_hash(L, out, nkv, H, Lq, Lk, dk)
 
@@ -365,8 +377,10 @@ def test_fp32_mfma_backward_in_two_parts(L, nkv, H, Lq, Lk, dk):
         dq, dk_, dv = (torch.full((n, d), NAN, device="cuda") for n in (nkv * Lq, nkv * Lk, nkv * Lk))
         ds = torch.full((nkv, H, Lq, Lk), NAN, device="cuda")
         a.dq, a.d_k, a.dv, a.dscore = dq.data_ptr(), dk_.data_ptr(), dv.data_ptr(), ds.data_ptr()
+        assert families(L, out, True) == ["bwd_mfma"]
         for part in (1, 2):
             a.bwd_part = part
+            assert families(L, out, True) == ["bwd_mfma"]
             L.check(L.lib().ortk_attention_bwd(C.byref(a), L.stream_ptr()), "attn_bwd")
             if part == 1:       # part 1 guarantees dQ and dscore
                 torch.cuda.synchronize()
@@ -387,6 +401,7 @@ def test_decode_kernel(L, nkv, H, Lq, Lk, dk, mask, drop):
     """attn_impl = 4: attn_decode_kernel<32 | 64> (forward only; up to 8 query rows, 64 keys, no causal mask, no dropout)."""
     with forced(L, 4):
         out = run_case(L, nkv, H, Lq, Lk, dk, use_bias=mask, kmask=_tail_mask(nkv, Lk) if mask else None, drop_p=drop, drop_seed=13, bwd=False)
+        assert families(L, out) == (["fwd"] if drop else ["decode"])
         if drop:
             assert_mask_is_the_hash(L, out, nkv, H, Lq, Lk, dk)
 

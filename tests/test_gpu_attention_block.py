@@ -8,7 +8,7 @@ O, P, dQ, dK, dV and dscore: the new kernels are another mapping of the same per
 import pytest
 import torch
 
-from test_gpu_attention import run_case, _caps, assert_mask_is_the_hash, rnd  # noqa: F401  (rnd: the operands run_case draws)
+from test_gpu_attention import run_case, _caps, assert_mask_is_the_hash, families, rnd  # noqa: F401  (rnd: the operands run_case draws)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,13 +26,16 @@ def bits(t):
     return t.view(torch.int16 if t.element_size() == 2 else torch.int32)
 
 
-def both_mappings(L, *args, **kw):
-    """run_case with attn16_block = 1, then with 0; every output bit-identical.  Returns the first run."""
+def both_mappings(L, *args, mapped=True, **kw):
+    """run_case with attn16_block = 1, then with 0; every output bit-identical.  Returns the first run.  mapped: the shape is one the
+    attn16b kernels serve (the plan must name them under 1, and the wave-per-tile kernels under 0 and for every other shape)."""
     old = L.set_tuning(attn16_block=1)
     try:
         out = run_case(L, *args, **kw)
+        assert (families(L, out), families(L, out, True)) == ((["attn16b_fwd"], ["attn16b_bwd"]) if mapped else (["attn16_fwd"], ["attn16_bwd"]))
         L.set_tuning(attn16_block=0)
         blk = run_case(L, *args, **kw)
+        assert (families(L, blk), families(L, blk, True)) == (["attn16_fwd"], ["attn16_bwd"])
     finally:
         L.set_tuning(attn16_block=old["attn16_block"])
     for name in ("o", "p", "dq", "dk", "dv", "ds"):
@@ -81,6 +84,20 @@ def test_cross_shape_ragged(L, dk):
                   drop_rows=row_pos, poison_p=True, slack=T, **BF16)
 
 
+def test_cross_shape_ragged_with_an_empty_group(L):
+    """q_off[g + 1] == q_off[g]: an image none of whose captions has a valid row (kv_ragged = 0: it still owns 36 keys).  It has no row
+    of O, dQ, P or dscore — its blocks of P and dscore keep their NaN sentinels — and its rows of dK and dV are written as zeros."""
+    H, T, spi, Lk = 2, 17, 5, 36
+    lengths = [17, 17, 17, 17, 17] + [0] * 5 + [4, 4, 4, 3, 1]
+    off, row_pos = _caps(lengths, T)
+    assert [off[(g + 1) * spi] - off[g * spi] for g in range(3)] == [85, 0, 16]
+    kmask = torch.ones(3, Lk); kmask[1, 20:] = 0; kmask[2, 35] = 0
+    out = both_mappings(L, 3, H, spi * T, Lk, 64, kmask=kmask.view(-1), drop_p=0.1, drop_seed=43, q_off=off, stride=spi, kv_ragged=0,
+                        drop_rows=row_pos, poison_p=True, slack=T, **BF16)
+    assert torch.isnan(out["p"][1]).all() and torch.isnan(out["ds"][1]).all()
+    assert not out["dk"][Lk:2 * Lk].float().any() and not out["dv"][Lk:2 * Lk].float().any()
+
+
 @pytest.mark.parametrize("Lk", [33, 37, 48, 64])        # 3 | 3 | 3 | 4 key tiles; 37: P rows not 16-byte aligned
 @pytest.mark.parametrize("Lq,bias", [(33, True), (48, True), (49, False), (96, False)])     # 3 tiles | 3 full | 4: two per wave | 6 full
 def test_tile_count_edges(L, Lq, Lk, bias):
@@ -110,7 +127,7 @@ def test_ragged_self_attention_of_long_captions(L):
 def test_shapes_that_stay_with_the_wave_per_tile_kernels(L, Lq, Lk, in_dt, bias):
     nkv, H = 2, 2
     both_mappings(L, nkv, H, Lq, Lk, 64, use_bias=bias, kmask=two_masked(nkv, Lk), drop_p=0.1, drop_seed=15, precision=1, in_dt=in_dt,
-                  out_dt=in_dt)
+                  out_dt=in_dt, mapped=False)
 
 
 @pytest.mark.parametrize("with_q_off", [False, True])

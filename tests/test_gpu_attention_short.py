@@ -8,7 +8,7 @@ implementation."""
 import pytest
 import torch
 
-from test_gpu_attention import run_case, _caps, assert_mask_is_the_hash, rnd  # noqa: F401  (rnd: the operands run_case draws)
+from test_gpu_attention import run_case, _caps, assert_mask_is_the_hash, families, rnd  # noqa: F401  (rnd: the operands run_case draws)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,8 +31,10 @@ def short_and_block(L, *args, short=1, **kw):
     old = L.set_tuning(attn16_short=short)
     try:
         out = run_case(L, *args, **kw)
+        assert families(L, out) == ["attn16s_fwd"] and ("dq" not in out or families(L, out, True) == ["attn16s_bwd"])
         L.set_tuning(attn16_short=0)
         blk = run_case(L, *args, **kw)
+        assert families(L, blk)[0] in ("attn16_fwd", "attn16b_fwd") and ("dq" not in blk or families(L, blk, True)[0] in ("attn16_bwd", "attn16b_bwd"))
     finally:
         L.set_tuning(attn16_short=old["attn16_short"])
     for name in ("o", "p", "dq", "dk", "dv", "ds"):
