@@ -344,8 +344,9 @@ typedef struct ortk_tuning {
     int32_t attn_impl;       /* 0 automatic | 1 wave kernels | 3 fp32-MFMA kernels | 4 small register-only kernels (ortk_attn.hip dispatch) */
     int32_t attn16_min_lq;   /* fp32-input query blocks shorter than this stay off the bf16-operand attention kernels (33) */
     int32_t side_stream;     /* 1: the executor queues weight gradients and other independent work on a second stream (default) | 0 */
-    int32_t row_chain;       /* rows-stationary chains (ortk_row_chain / ortk_row_bchain) in the executor: 0 none (one launch per operator) | 1 forward passes
-                                (default) | 2 + the encoder's backward | 3 + the decoder's backward */
+    int32_t row_chain;       /* rows-stationary chains (ortk_row_chain) in the executor's forward passes: 1 (default) | 0 none (one launch per operator).
+                                2, 3: refused (they put the encoder's / the decoder's backward on ortk_row_bchain: measured, not kept, removed from
+                                the executor; the operator stays) */
     int32_t chain_wide;      /* 1 (default): forward chains of 12 289 .. 19 456 rows run the 76-row form of the kernel — one round of workgroups
                                 instead of two (profiles/r04_row_chains.txt) | 0: the 48-row form everywhere | 2: the 76-row form wherever it saves
                                 a round (A/B: two instead of three at the decode's 36 864 encoder rows measures the same) */
@@ -371,10 +372,10 @@ typedef struct ortk_tuning {
     int32_t feats_bf16;           /* 1 (default, mixed precision with the side stream): a bf16 copy of the region features per step (att_embed and its weight
                                      gradient on the bf16-operand kernels; the weight gradient in the backward's last grouped launch) and the chain weights
                                      packed on a third queue beside att_embed | 0: fp32 features, everything at the head of the forward on the caller's stream */
-    int32_t ln_fuse;              /* bit 0: the executor's backward runs a d_model-wide data gradient and the LayerNorm backward behind it as ONE launch
-                                     (ortk_gemm ln_mode 2 on short row panels).  OFF by default: alone the fused launch ties the two it replaces
-                                     (59.5 vs 62.0 us at 16 640 x 512 x 512), inside the step it needs a free compute unit per workgroup and waits for
-                                     the units the side stream's weight gradients hold: 11.65 vs 10.40 ms per XE step (scratch/wgrad_group_ab.py)
+    int32_t ln_fuse;              /* bit 0: unused, refused (it made the executor's backward run a d_model-wide data gradient and the LayerNorm backward
+                                     behind it as ONE launch, ortk_gemm ln_mode 2: alone the fused launch ties the two it replaces, 59.5 vs 62.0 us at
+                                     16 640 x 512 x 512; inside the step it needs a free compute unit per workgroup and waits for the units the side
+                                     stream's weight gradients hold, 11.65 vs 10.40 ms per XE step.  Removed from the executor; the operator stays)
                                      | bit 1: unused, refused (it selected the 128-row backward panels of round 3, removed) | bit 2: the LayerNorm backward of width 512 with four
                                      instead of eight consecutive columns per lane (measurement) | bit 3: the executor keeps the LayerNorm output gradients
                                      (data gradient -> ortk_layernorm_bwd_dt) in fp32 in mixed precision too; default: bf16 there, as every other gradient

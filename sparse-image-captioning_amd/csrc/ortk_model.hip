@@ -178,9 +178,6 @@ struct ChainSet {
     bool on = false;
     ChainPackTable t;
     int e0 = -1, eb[MAXLAYERS], d0 = -1, db[MAXLAYERS], dc[MAXLAYERS];
-    // backward chains (bchain_layout): X = [FFN' -> LN' -> . Wout] on a masked gradient, Y = [dq . Wcq -> LN' -> . Wo],
-    // ZX(l) = [dQKV . Wqkv -> LN' of layer l] + X of layer l - 1, Z0 = the bottom of a stack
-    int bx_top = -1, by[MAXLAYERS], bzx[MAXLAYERS], bz0 = -1, ex_top = -1, ezx[MAXLAYERS], ez0 = -1;
     size_t bytes = 0;
     int units(int c) const { return t.first[c + 1] - t.first[c]; }
     const void* stream_of(const void* pk, int c) const { return reinterpret_cast<const char*>(pk) + (size_t)t.base[c] * 16; }
@@ -261,45 +258,6 @@ static void chain_layout(const ortk_config& c, const Offsets& o, bool enc, bool 
     }
     cs.bytes = (size_t)base * 16;
 }
-// units over the TRANSPOSED bf16 weight copy (block (N, K) of the arena stored (K, N) at the same offset)
-static void bchain_layout(const ortk_config& c, const Offsets& o, ChainSet& cs, bool sizing = false) {
-    cs.on = chain_cfg_ok(c);
-    cs.bytes = 0;
-    if (!cs.on && !(sizing && chain_cfg_ok(c, true))) return;
-    const int L = c.n_layers, NC = c.d_ff / 512, ff = c.d_ff;
-    ChainPackTable& t = cs.t;
-    t.n_chains = 0; t.first[0] = 0;
-    int nu = 0;
-    int64_t base = 0;
-    auto unit = [&](int64_t off, int ld) { t.u[nu].offset = (int32_t)off; t.u[nu].ld = ld; t.form[nu] = 0; ++nu; };
-    auto close = [&]() {
-        const int c_ = t.n_chains++;
-        t.base[c_] = base; t.first[c_ + 1] = nu;
-        base += (int64_t)8 * (nu - t.first[c_] + 1) * 16 * 256;
-        return c_;
-    };
-    auto zq = [&](int64_t wqkv) { for (int i = 0; i < 3; ++i) unit(wqkv + (int64_t)i * 512, 1536); };          // dQKV . Wqkv: columns 512 i .. of Wqkv^T
-    auto xf = [&](int64_t w1, int64_t w2, int64_t wout) {
-        for (int k = 0; k < NC; ++k) { unit(w2 + (int64_t)k * 512 * 512, 512); unit(w1 + (int64_t)k * 512, ff); }
-        unit(wout, 512);
-    };
-    // decoder
-    xf(o.dec[L - 1].w1, o.dec[L - 1].w2, o.dec[L - 1].cow); cs.bx_top = close();
-    for (int l = L - 1; l >= 0; --l) {
-        unit(o.dec[l].cqw, 512); unit(o.dec[l].wo, 512); cs.by[l] = close();
-        zq(o.dec[l].wqkv);
-        if (l > 0) { xf(o.dec[l - 1].w1, o.dec[l - 1].w2, o.dec[l - 1].cow); cs.bzx[l] = close(); }
-        else cs.bz0 = close();
-    }
-    // encoder
-    xf(o.enc[L - 1].w1, o.enc[L - 1].w2, o.enc[L - 1].wo); cs.ex_top = close();
-    for (int l = L - 1; l >= 0; --l) {
-        zq(o.enc[l].wqkv);
-        if (l > 0) { xf(o.enc[l - 1].w1, o.enc[l - 1].w2, o.enc[l - 1].wo); cs.ezx[l] = close(); }
-        else cs.ez0 = close();
-    }
-    cs.bytes = (size_t)base * 16;
-}
 
 struct Bump {
     char* base; size_t off;
@@ -334,13 +292,11 @@ struct TrainWS {
     // backward temporaries
     float *ga, *gb, *gy; void* gdo /*Q: dO of an attention backward*/; void *gt /*A*/, *gt2 /*A*/, *gt3 /*A*/, *gqkv /*A*/, *gh /*A*/, *gkv /*A*/; float* scalar;
     void* chain_pk = nullptr;               // weight units of the rows-stationary chains in streaming order (chain_layout; mixed precision)
-    void* chain_pk_b = nullptr;             // ... of the backward chains (bchain_layout, from the transposed copy)
-    void* gh2 = nullptr;                    // second FFN hidden-gradient buffer: the backward chains alternate (a weight gradient still reads the other)
     // grouped weight gradients (ortk_wgrad_group, mixed precision): a layer's dY operands stay alive until the layer's ONE launch on the
     // side stream has read them, while the next layer's are already being written
     static constexpr int NGT = 10;          // (rows, d) gradient temporaries in rotation: 4 per decoder layer, two layers alive + slack
     void* gtp[NGT] = {};
-    void* gqkv2 = nullptr;                  // layers alternate between gqkv / gqkv2 and gh / gh2
+    void *gqkv2 = nullptr, *gh2 = nullptr;  // layers alternate between gqkv / gqkv2 and gh / gh2
     void* wg_ws = nullptr; size_t wg_ws_bytes = 0;      // partial tiles + tickets of one grouped launch (launches are ordered by their stream)
     void* feats16 = nullptr;                // bf16 copy of the region features (mixed precision): operand of att_embed and of its weight gradient
     size_t bytes;
@@ -396,14 +352,12 @@ static void carve_train(const ortk_config& c, int B, int S, int R, int T, void* 
     {   // (sized whatever the tuning switch says: the workspace size is a function of the configuration and the shapes only)
         ChainSet cs; chain_layout(c, o, true, true, cs, 0, 0, true);
         if (cs.bytes) w.chain_pk = b.take_bytes(cs.bytes);
-        ChainSet bs; bchain_layout(c, o, bs, true);
-        if (bs.bytes) { w.chain_pk_b = b.take_bytes(bs.bytes); w.gh2 = act(Mx * ff); }
     }
     if (c.precision) {
         w.gtp[0] = w.gt; w.gtp[1] = w.gt2; w.gtp[2] = w.gt3;
         for (int i = 3; i < TrainWS::NGT; ++i) w.gtp[i] = act(Mx * d);
         w.gqkv2 = act(Mx * 3 * d);
-        if (!w.gh2) w.gh2 = act(Mx * ff);
+        w.gh2 = act(Mx * ff);
         // the largest group: a decoder layer (6 projections), an encoder layer, the generator, the memory's K|V projection
         const int64_t lay_tiles = 2 * ortk_cdiv(d, 256) * ortk_cdiv(ff, 256) + 4 * ortk_cdiv(d, 256) * ortk_cdiv(d, 256) + ortk_cdiv(3 * d, 256) * ortk_cdiv(d, 256);
         const int64_t gen_tiles = ortk_cdiv(w.ldv, 256) * ortk_cdiv(d, 256), kv_tiles = ortk_cdiv(L * 2 * d, 256) * ortk_cdiv(d, 256);
@@ -517,6 +471,16 @@ struct Ctx {
         return 0;
     }
     int wait_ev(hipEvent_t e) const { return (e && hipStreamWaitEvent(s, e, 0) != hipSuccess) ? ORTK_EINVAL : 0; }
+    int side_wait_ev(hipEvent_t e) const { return (e && hipStreamWaitEvent(side->s, e, 0) != hipSuccess) ? ORTK_EINVAL : 0; }
+    // ONE launch on queue `q` (side->s or side->s2) behind everything queued on the caller's stream so far; *done = its completion
+    // event (not recorded when the launch fails).  A weight gradient's caller then marks what the launch reads: reads(buf, *done).
+    template <typename Launch> int side_launch(hipStream_t q, hipEvent_t* done, Launch&& launch) const {
+        hipEvent_t ready = side->take();
+        *done = side->take();
+        if (hipEventRecord(ready, s) != hipSuccess || hipStreamWaitEvent(q, ready, 0) != hipSuccess) return ORTK_EINVAL;
+        if (int e = launch(q)) return e;
+        return hipEventRecord(*done, q) != hipSuccess ? ORTK_EINVAL : 0;
+    }
     Ctx on_side() const { Ctx t = *this; t.s = side->s; t.use_side = false; return t; }
     int join() const {                                   // everything forked so far (the side stream runs in order)
         if (last_done) { if (hipStreamWaitEvent(s, last_done, 0) != hipSuccess) return ORTK_EINVAL; last_done = nullptr; }
@@ -637,10 +601,8 @@ static int flush_wgrads(const Ctx& c, bool urgent = false) {
     }
     int e = 0;
     if (c.use_side) {
-        hipEvent_t ready = c.side->take(), done = c.side->take();
-        if (hipEventRecord(ready, c.s) != hipSuccess || hipStreamWaitEvent(c.side->s, ready, 0) != hipSuccess) return ORTK_EINVAL;
-        e = ortk_wgrad_group(&c.grp, (ortk_stream)c.side->s);
-        if (!e && hipEventRecord(done, c.side->s) != hipSuccess) e = ORTK_EINVAL;
+        hipEvent_t done;
+        e = c.side_launch(c.side->s, &done, [&](hipStream_t q) { return ortk_wgrad_group(&c.grp, (ortk_stream)q); });
         if (!e) { const uint64_t seq = c.next_seq(); for (int i = 0; i < c.grp.n; ++i) c.reads(c.grp.item[i].dY, done, seq); }
     } else {
         e = ortk_wgrad_group(&c.grp, (ortk_stream)c.s);
@@ -673,15 +635,12 @@ static int wgrad_gemm(const Ctx& c, const void* dY, int dydt, int64_t lddy, cons
     a.splitk = (int)std::max<int64_t>(1, std::min(sk, max_sk));
     a.colsum = db;                         // bias gradient fused into the wgrad kernel (both precisions; ortk_gemm falls back to ortk_colsum)
     if (c.use_side) {
-        hipEvent_t ready = c.side->take(), done = c.side->take();
-        if (hipEventRecord(ready, c.s) != hipSuccess || hipStreamWaitEvent(c.side->s, ready, 0) != hipSuccess) return ORTK_EINVAL;
-        TRY(ortk_gemm(&a, (ortk_stream)c.side->s));
-        if (hipEventRecord(done, c.side->s) != hipSuccess) return ORTK_EINVAL;
+        hipEvent_t done;
+        TRY(c.side_launch(c.side->s, &done, [&](hipStream_t q) { return ortk_gemm(&a, (ortk_stream)q); }));
         c.reads(dY, done);
         return 0;
     }
-    TRY(ortk_gemm(&a, (ortk_stream)c.s));
-    return 0;
+    return ortk_gemm(&a, (ortk_stream)c.s);
 }
 static int ln_fwd(const Ctx& c, const float* x, int64_t a, int64_t b, void* y, int ydt, float* st, int64_t rows) {
     return ortk_layernorm_fwd(x, c.P + a, c.P + b, y, ydt, st, rows, c.cfg->d_model, 1e-6f, (ortk_stream)c.s);
@@ -707,33 +666,16 @@ static int drop_bwd(const Ctx& c, const float* dx, void* tmp, int64_t n, uint32_
     return 0;
 }
 
-// dX = dLN/dx(dY W) + dres in ONE launch (ortk_gemm ln_mode 2: short row panels, LayerNorm backward in the epilogue), or — sparse plans,
-// fp32 mode, widths other than 512, a sub-block of a packed projection — the data-gradient GEMM into `gy` followed by ln_bwd.
+// dX = dLN/dx(dY W) + dres: the data-gradient GEMM into `gy`, then ln_bwd.
 // (W stored (N_out, K_in) with K_in = d_model; the LayerNorm is the one whose OUTPUT the projection read.)
 static int dgrad_ln_bwd(const Ctx& c, const void* dY, int dydt, int64_t lddy, int64_t woff, int64_t M, int Nout, int Kin, float* gy,
                         const float* x, float* G, int64_t na, int64_t nb, const float* st, const float* dres, float* dx, void* dz, int next_op,
                         bool whole_block = true) {
-    const bool fusable = tuning().ln_fuse & 1 && c.prec && c.W16T && whole_block && dydt == ORTK_BF16 && Kin == 512 && Kin == c.cfg->d_model &&
-                         (Nout % 64) == 0 && Ctx::ell_block(c.ell_b, woff, Kin, Nout) < 0 && !c.ell_b;
-    if (!fusable) {
-        // Mixed precision on the dense kernels: the LayerNorm's output gradient lives as bf16 between the two launches, like every other
-        // gradient that is a GEMM operand there (half the bytes out of the GEMM's epilogue and into ln_bwd; tuning().ln_fuse & 8 keeps fp32)
-        const int gdt = (c.prec && c.adt == ORTK_BF16 && c.W16T && whole_block && !c.ell_b && Kin == 512 && Kin == c.cfg->d_model && !(tuning().ln_fuse & 8)) ? ORTK_BF16 : ORTK_F32;
-        TRY(dgrad_gemm(c, dY, dydt, lddy, woff, gy, gdt, Kin, M, Nout, Kin, nullptr, 0, 0, 1.f, whole_block));
-        return ln_bwd(c, gy, x, G, na, nb, st, dres, dx, M, dz, next_op, gdt);
-    }
-    const bool mask = dz && next_op >= 0;        // (mixed precision: the masked copy is also the bf16 conversion)
-    ortk_gemm_args a; std::memset(&a, 0, sizeof(a));
-    a.A = dY; a.a_dtype = ORTK_BF16; a.lda = lddy;
-    a.B = reinterpret_cast<const __bf16*>(c.W16T) + woff; a.b_dtype = ORTK_BF16; a.ldb = Nout;
-    a.C = dx; a.c_dtype = ORTK_F32; a.ldc = Kin; a.M = (int)M; a.N = Kin; a.K = Nout; a.precision = 1;
-    a.ln_mode = 2; a.ln_a = c.P + na; a.ln_stats = const_cast<float*>(st); a.ln_eps = 1e-6f; a.ln_x = x; a.ln_dres = dres;
-    a.ln_da = G + na; a.ln_db = G + nb;
-    a.ln_y = mask ? dz : nullptr; a.ln_y_dtype = c.adt;
-    a.drop_p = c.p_drop(); a.drop_seed = mask ? c.sub((uint32_t)next_op) : 0; a.drop_rows = c.drop_rows;
-    TRY(c.before_write(dx));
-    if (mask) TRY(c.before_write(dz));
-    return ortk_gemm(&a, (ortk_stream)c.s);
+    // Mixed precision on the dense kernels: the LayerNorm's output gradient lives as bf16 between the two launches, like every other
+    // gradient that is a GEMM operand there (half the bytes out of the GEMM's epilogue and into ln_bwd; tuning().ln_fuse & 8 keeps fp32)
+    const int gdt = (c.prec && c.adt == ORTK_BF16 && c.W16T && whole_block && !c.ell_b && Kin == 512 && Kin == c.cfg->d_model && !(tuning().ln_fuse & 8)) ? ORTK_BF16 : ORTK_F32;
+    TRY(dgrad_gemm(c, dY, dydt, lddy, woff, gy, gdt, Kin, M, Nout, Kin, nullptr, 0, 0, 1.f, whole_block));
+    return ln_bwd(c, gy, x, G, na, nb, st, dres, dx, M, dz, next_op, gdt);
 }
 
 static const float DIM_MAT_SENTINEL = -1.f;
@@ -761,7 +703,48 @@ extern "C" uint32_t ortk_dropout_site_seed(uint64_t seed, int32_t stack, int32_t
 }
 namespace ortk {
 
-struct EncPtrs { void* y1; void* qkv; float* P; void* o; float* xm; void* y2; void* h; float* xout; float *st1, *st2; };
+// ------------------------------------------------------------------------------------------------ the model's three attention calls
+// One builder per call — encoder self-, decoder self-, cross-attention — for what its forward and its backward share: operands, shapes,
+// the probabilities the forward stores and the backward reads, the dropout site, the valid-position layout.  (These are the fields whose
+// drift between the two passes breaks the dropout replay silently.)  The forward adds o / kmask / bias / causal_period, the backward
+// d_o / dq / d_k / dv / dscore.
+static ortk_attn_args attn_call(const Ctx& c, int qdt, float* p, int nkv, int Lq, int Lk, uint32_t op) {
+    ortk_attn_args a; std::memset(&a, 0, sizeof(a));
+    a.precision = c.prec; a.qkv_dtype = qdt; a.p = p;
+    a.nkv = nkv; a.H = c.cfg->n_heads; a.Lq = Lq; a.Lk = Lk; a.dk = c.cfg->d_model / c.cfg->n_heads;
+    a.drop_p = c.p_drop(); a.drop_seed = c.sub(op);
+    return a;
+}
+// Q | K | V as column blocks of one (rows, 3 d) projection output
+static void attn_packed_qkv(ortk_attn_args& a, const void* qkv, const AttMode& am, int d) {
+    a.q = (const float*)qkv; a.k = (const float*)off_elems(qkv, am.k * d, a.qkv_dtype); a.v = (const float*)off_elems(qkv, am.v * d, a.qkv_dtype);
+    a.ldq = a.ldk = a.ldv = 3 * d;
+}
+static ortk_attn_args enc_self_attn(const Ctx& c, const EncBuf& b, int qdt, int l, int B, int S) {
+    ortk_attn_args a = attn_call(c, qdt, b.P, B, S, S, eop(l, 0));
+    attn_packed_qkv(a, b.qkv, att_mode(c.cfg->share_att_enc), c.cfg->d_model);
+    return a;
+}
+static ortk_attn_args dec_self_attn(const Ctx& c, const TrainWS& w, const ortk_batch* bt, int l) {
+    ortk_attn_args a = attn_call(c, w.qdt_self, w.dec[l].Ps, bt->R, bt->T, bt->T, dop(l, 0));
+    attn_packed_qkv(a, w.dec[l].qkv, att_mode(c.cfg->share_att_dec), c.cfg->d_model);
+    if (bt->row_pos) { a.q_off = bt->cap_off; a.q_off_stride = 1; a.kv_ragged = 1; }      // valid positions: a caption's keys are its own rows
+    return a;
+}
+static ortk_attn_args cross_attn(const Ctx& c, const Offsets& o, const TrainWS& w, const ortk_batch* bt, int l) {
+    const int spi = bt->R / bt->B;
+    ortk_attn_args a = attn_call(c, w.qdt_cross, w.dec[l].Pc, bt->B, spi * bt->T, bt->S, dop(l, 2));
+    a.q = (const float*)w.dec[l].qc; a.ldq = c.cfg->d_model;
+    a.k = (const float*)off_elems(w.ckv, o.ckv_slot[l] * o.cw, w.qdt_cross); a.v = (const float*)off_elems(w.ckv, o.ckv_slot[l] * o.cw + o.cv, w.qdt_cross);
+    a.ldk = a.ldv = o.ckv_slots * o.cw;
+    if (bt->row_pos) { a.q_off = bt->cap_off; a.q_off_stride = spi; a.drop_rows = bt->row_pos; }      // ... an image's rows: those of its spi captions
+    return a;
+}
+// the backward of a self-attention: dO -> dQ | dK | dV as column blocks of the (rows, 3 d) buffer `gq`
+static void attn_packed_grads(ortk_attn_args& a, const void* dO, void* gq, const AttMode& am, int d, int A) {
+    a.d_o = (const float*)dO; a.lddo = d; a.dqkv_dtype = A;
+    a.dq = gq; a.d_k = off_elems(gq, am.gk * d, A); a.dv = off_elems(gq, am.gv * d, A); a.lddq = a.lddk = a.lddv = 3 * d;
+}
 
 // encoder stack; `bufs[l]` may alias between layers when nothing has to be kept for a backward pass.
 // `mem` receives the final LayerNorm in dtype `mem_dt`.
@@ -782,14 +765,14 @@ static int queue_box_bias(const Ctx& c, const Offsets& o, const float* boxes, fl
 
 // `box_queued`: the caller has already queued the geometry bias (queue_box_bias; *box_queued = its completion event or NULL)
 static int encoder_forward(const Ctx& c, const Offsets& o, const float* feats, const float* boxes, const float* masks, int B, int S,
-                           float* x0, float* logbias, const EncPtrs* bufs, void* mem, int mem_dt, float* st_mem, int qdt = ORTK_F32,
+                           float* x0, float* logbias, const EncBuf* bufs, void* mem, int mem_dt, float* st_mem, int qdt = ORTK_F32,
                            const hipEvent_t* box_queued = nullptr, const ChainSet* cs = nullptr, const void* chain_pk = nullptr,
                            bool keep = true,         // keep = false (decode): the chains do not store what only a backward would read
                            const void* feats16 = nullptr, hipEvent_t feats16_done = nullptr,     // bf16 copy of the features, made on another queue
                            hipEvent_t pack_done = nullptr) {                                        // the chains' packed weights, likewise
     const ortk_config& cfg = *c.cfg;
     const float* P = c.P;
-    const int d = cfg.d_model, ff = cfg.d_ff, H = cfg.n_heads, L = cfg.n_layers, dk = d / H, A = c.adt;
+    const int d = cfg.d_model, ff = cfg.d_ff, H = cfg.n_heads, L = cfg.n_layers, A = c.adt;
     const int64_t Me = (int64_t)B * S;
     // att_embed: relu(Linear) on valid regions, zeros elsewhere, dropout (relation_transformer.py:331-333,349-350)
     // (the plain `transformer` embeds every row, padded regions included: transformer.py:627-629)
@@ -803,14 +786,9 @@ static int encoder_forward(const Ctx& c, const Offsets& o, const float* feats, c
     } else {
         TRY(queue_box_bias(c, o, boxes, logbias, B, S, &box_done));
     }
-    if (feats16) {
-        TRY(c.wait_ev(feats16_done));
-        TRY(fwd_gemm(c, feats16, ORTK_BF16, cfg.feat, o.att_w, P + o.att_b, x0, ORTK_F32, d, Me, d, cfg.feat, true, c.p_src(), c.sub(OP_SRC),
-                     nullptr, 0, plain ? nullptr : masks));
-    } else {
-        TRY(fwd_gemm(c, feats, ORTK_F32, cfg.feat, o.att_w, P + o.att_b, x0, ORTK_F32, d, Me, d, cfg.feat, true, c.p_src(), c.sub(OP_SRC),
-                     nullptr, 0, plain ? nullptr : masks));
-    }
+    if (feats16) TRY(c.wait_ev(feats16_done));
+    TRY(fwd_gemm(c, feats16 ? feats16 : feats, feats16 ? ORTK_BF16 : ORTK_F32, cfg.feat, o.att_w, P + o.att_b, x0, ORTK_F32, d, Me, d, cfg.feat, true,
+                 c.p_src(), c.sub(OP_SRC), nullptr, 0, plain ? nullptr : masks));
     TRY(c.wait_ev(pack_done));
     const float* x = x0;
     const AttMode am = att_mode(cfg.share_att_enc);
@@ -825,15 +803,17 @@ static int encoder_forward(const Ctx& c, const Offsets& o, const float* feats, c
         TRY(chain_run(&ca, cs->stream_of(chain_pk, cs->e0), c.s));
     }
     for (int l = 0; l < L; ++l) {
-        const EncOff& e = o.enc[l]; const EncPtrs& b = bufs[l];
+        const EncOff& e = o.enc[l]; const EncBuf& b = bufs[l];
+        if (!chains) {
+            TRY(ln_fwd(c, x, e.n0a, e.n0b, b.y1, A, b.st1, Me));
+            TRY(fwd_gemm(c, b.y1, A, d, e.wqkv, P + e.bqkv, b.qkv, qdt, 3 * d, Me, am.n * d, d));
+        }
+        ortk_attn_args a = enc_self_attn(c, b, qdt, l, B, S);
+        a.o = b.o; a.o_dtype = A; a.ldo = d;
+        a.kmask = masks; a.bias = plain ? nullptr : logbias + (int64_t)l * B * H * S * S;
+        if (l == 0) TRY(c.wait_ev(box_done));
+        TRY(ortk_attention_fwd(&a, (ortk_stream)c.s));
         if (chains) {
-            ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec; a.qkv_dtype = qdt;
-            a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, am.k * d, qdt); a.v = (const float*)off_elems(b.qkv, am.v * d, qdt);
-            a.ldq = a.ldk = a.ldv = 3 * d; a.o = b.o; a.o_dtype = A; a.ldo = d;
-            a.kmask = masks; a.bias = plain ? nullptr : logbias + (int64_t)l * B * H * S * S; a.p = b.P;
-            a.nkv = B; a.H = H; a.Lq = S; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(eop(l, 0));
-            if (l == 0) TRY(c.wait_ev(box_done));
-            TRY(ortk_attention_fwd(&a, (ortk_stream)c.s));
             ortk_chain_args ca; std::memset(&ca, 0, sizeof(ca));
             ca.n_units = cs->units(cs->eb[l]); ca.M = Me; ca.x_in = x;
             ca.a_in = b.o; ca.bias_r = P + e.bo; ca.x_mid = b.xm; ca.seed_r = c.sub(eop(l, 1));
@@ -851,15 +831,6 @@ static int encoder_forward(const Ctx& c, const Offsets& o, const float* feats, c
             x = b.xout;
             continue;
         }
-        TRY(ln_fwd(c, x, e.n0a, e.n0b, b.y1, A, b.st1, Me));
-        TRY(fwd_gemm(c, b.y1, A, d, e.wqkv, P + e.bqkv, b.qkv, qdt, 3 * d, Me, am.n * d, d));
-        ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec; a.qkv_dtype = qdt;
-        a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, am.k * d, qdt); a.v = (const float*)off_elems(b.qkv, am.v * d, qdt);
-        a.ldq = a.ldk = a.ldv = 3 * d; a.o = b.o; a.o_dtype = A; a.ldo = d;
-        a.kmask = masks; a.bias = plain ? nullptr : logbias + (int64_t)l * B * H * S * S; a.p = b.P;
-        a.nkv = B; a.H = H; a.Lq = S; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(eop(l, 0));
-        if (l == 0) TRY(c.wait_ev(box_done));
-        TRY(ortk_attention_fwd(&a, (ortk_stream)c.s));
         TRY(fwd_gemm(c, b.o, A, d, e.wo, P + e.bo, b.xm, ORTK_F32, d, Me, d, d, false, c.p_drop(), c.sub(eop(l, 1)), x, d));
         TRY(ln_fwd(c, b.xm, e.n1a, e.n1b, b.y2, A, b.st2, Me));
         TRY(fwd_gemm(c, b.y2, A, d, e.w1, P + e.b1, b.h, A, ff, Me, ff, d, true, c.p_drop(), c.sub(eop(l, 2))));
@@ -868,13 +839,6 @@ static int encoder_forward(const Ctx& c, const Offsets& o, const float* feats, c
     }
     if (!chains) TRY(ln_fwd(c, x, o.enc_na, o.enc_nb, mem, mem_dt, st_mem, Me));
     return 0;
-}
-
-static void enc_ptrs_from_ws(const TrainWS& w, int L, EncPtrs* out) {
-    for (int l = 0; l < L; ++l) {
-        const EncBuf& e = w.enc[l];
-        out[l] = EncPtrs{e.y1, e.qkv, e.P, e.o, e.xm, e.y2, e.h, e.xout, e.st1, e.st2};
-    }
 }
 
 // bf16 working copy of the trainable arena (weights are the B operand of every forward / dgrad GEMM)
@@ -972,6 +936,78 @@ extern "C" void* ortk_train_workspace_memory(const ortk_config* cfg, int32_t B, 
     return w.mem;
 }
 
+// The head of a forward (phases 0 and 1; phase 2 finds the weight copies and the packed chain weights of phase 1 and only repacks when
+// its row count asks for the other form of the chain kernel): element-type casts, the transposed weight copy, the sparse forward plan,
+// the chains' layout and packed weights — and the events the rest of the forward waits for.
+struct FwdHead {
+    ChainSet cs;
+    bool box_early = false, f16 = false;
+    hipEvent_t box_done = nullptr, feats16_done = nullptr, fplan_done = nullptr, pack_done = nullptr;
+};
+static int forward_head(Ctx& c, const Offsets& o, const TrainWS& w, const ortk_batch* bt, int phase, FwdHead& h) {
+    const ortk_config* cfg = c.cfg;
+    const float* params = c.P;
+    const ortk_stream stream = (ortk_stream)c.s;
+    // The geometry bias reads the fp32 parameters: with the side stream it starts BEFORE the bf16 weight copies are made
+    // (0.14 ms of casts it used to wait behind; the encoder's first attention then waited for it), and the transposed copy,
+    // which only the backward reads, is made on the side stream behind it.
+    h.box_early = c.use_side && !cfg->no_box && phase != 2;
+    // mixed precision with the side stream: the region features get a bf16 copy there, ahead of the geometry bias (25 us for 75 MB): the
+    // att_embed product then runs on the LDS-DMA tiles instead of the fp32-operand kernel (89 -> 35 us at the head of the step), and its
+    // weight gradient joins the last grouped launch of the backward (it was a 120-us launch of its own at the very end)
+    h.f16 = c.use_side && w.feats16 && phase != 2 && (cfg->feat % 64) == 0 && tuning().feats_bf16;
+    if (phase != 2) {
+        if (h.f16) {
+            TRY(ortk_cast_bf16(bt->att_feats, w.feats16, w.Me * cfg->feat, (ortk_stream)c.side->s));
+            TRY(c.side_mark(&h.feats16_done));
+        }
+        if (h.box_early) TRY(queue_box_bias(c, o, bt->boxes, w.logbias, bt->B, bt->S, &h.box_done));
+        TRY(make_w16(cfg, o, params, w.w16, stream));
+        if (c.use_side) {
+            if (!h.box_early) TRY(c.fork());    // (the previous backward on the caller's stream still reads the old copy)
+            TRY(make_w16t(cfg, o, params, w.w16t, (ortk_stream)c.side->s));     // done before the decoder prefix the forward waits for
+            TRY(c.side_mark(nullptr));
+        } else {
+            TRY(make_w16t(cfg, o, params, w.w16t, stream));      // read by the backward that follows this forward
+        }
+    }
+    // sparse plans are rebuilt from THIS call's effective weights (a new mask sample per step): no stale images
+    c.ell_f = cfg->sparse_fwd;        // (built below, once it is known who uses it first)
+    const int64_t Md = batch_compact(bt) ? bt->Mc : w.Md;
+    // rows-stationary chains: their weight units go into streaming order once per forward (phase 2 finds phase 1's image)
+    ChainSet& cs = h.cs;
+    chain_layout(*cfg, o, true, true, cs, w.Me, Md);
+    // (a sparse forward plan that takes a product of a chain switches the chains off; one over the other products — region embedding,
+    //  K|V projection of the memory, generator — or a data-gradient plan alone leaves them on)
+    if (cs.on && (!w.chain_pk || plan_hits_chain(c.ell_f, cs))) cs.on = false;
+    if (cfg->sparse_fwd && phase != 2) {
+        // With the chains on, no product of a layer is in the plan; unless the region embedding is, its first user is the K|V
+        // projection of the memory, after the encoder: the build (0.2 ms) then runs beside the encoder on the side stream.
+        const void* src = cfg->precision ? (const void*)w.w16 : (const void*)params;
+        const int sdt = cfg->precision ? ORTK_BF16 : ORTK_F32;
+        if (cs.on && c.use_side && Ctx::ell_block(c.ell_f, o.att_w, cfg->d_model, cfg->feat) < 0) {
+            TRY(c.fork());                        // (the bf16 weight copy is made on the caller's stream)
+            TRY(ortk_sparse_build(cfg->sparse_fwd, src, sdt, (ortk_stream)c.side->s));
+            TRY(c.side_mark(&h.fplan_done));
+        } else {
+            TRY(ortk_sparse_build(cfg->sparse_fwd, src, sdt, stream));
+        }
+    }
+    // Phase 1 has no captions, so it packs for the kernel forms of (Me, R * T).  A phase 2 on the valid positions whose row count
+    // picks the OTHER form of the chain kernel (76-row blocks stream the FFN units in another order) packs again, from the same bf16
+    // weight copy, for the layout chain_run() will derive from its own row count (the encoder's units, already consumed, ride along).
+    const bool repack2 = phase == 2 && cs.on && chain_wide(w.Md) != chain_wide(Md);
+    // (with the side streams: on the third queue, beside att_embed — 117 us the first chain used to wait for on the caller's stream;
+    //  the caller's stream and the side stream's decoder prefix wait for it right before their first chain)
+    if (cs.on && (phase != 2 || repack2)) {
+        if (c.use_side && phase != 2 && tuning().feats_bf16)
+            TRY(c.side_launch(c.side->s2, &h.pack_done, [&](hipStream_t q) { return chain_pack_all(w.w16, w.chain_pk, cs.t, q); }));
+        else
+            TRY(chain_pack_all(w.w16, w.chain_pk, cs.t, c.s));
+    }
+    return 0;
+}
+
 // phase 0: the whole forward.  phase 1: weight copies + encoder only (the memory stays in `ws`: ortk_train_workspace_memory);
 // phase 2: the decoder and generator on the encoder state phase 1 left in the same workspace (same params / train / seed).
 // An SCST step runs its encoder ONCE this way: phase 1, the rollout decode on that memory (ortk_decode_opts.memory), phase 2 on
@@ -990,80 +1026,18 @@ extern "C" int ortk_forward_phase(const ortk_config* cfg, const float* params, c
     Ctx c{cfg, ortk_s(stream), cfg->precision, seed, train != 0, params, w.w16, w.adt};
     c.side = (c.adt == ORTK_BF16 && !ortk_prof_serial()) ? side_for(c.s) : nullptr;
     c.use_side = c.side != nullptr;
-    // The geometry bias reads the fp32 parameters: with the side stream it starts BEFORE the bf16 weight copies are made
-    // (0.14 ms of casts it used to wait behind; the encoder's first attention then waited for it), and the transposed copy,
-    // which only the backward reads, is made on the side stream behind it.
-    hipEvent_t box_done = nullptr;
-    const bool box_early = c.use_side && !cfg->no_box && phase != 2;
-    // mixed precision with the side stream: the region features get a bf16 copy there, ahead of the geometry bias (25 us for 75 MB): the
-    // att_embed product then runs on the LDS-DMA tiles instead of the fp32-operand kernel (89 -> 35 us at the head of the step), and its
-    // weight gradient joins the last grouped launch of the backward (it was a 120-us launch of its own at the very end)
-    hipEvent_t feats16_done = nullptr;
-    const bool f16 = c.use_side && w.feats16 && phase != 2 && (cfg->feat % 64) == 0 && tuning().feats_bf16;
-    if (phase != 2) {
-        if (f16) {
-            TRY(ortk_cast_bf16(bt->att_feats, w.feats16, w.Me * cfg->feat, (ortk_stream)c.side->s));
-            TRY(c.side_mark(&feats16_done));
-        }
-        if (box_early) TRY(queue_box_bias(c, o, bt->boxes, w.logbias, bt->B, bt->S, &box_done));
-        TRY(make_w16(cfg, o, params, w.w16, stream));
-        if (c.use_side) {
-            if (!box_early) TRY(c.fork());      // (the previous backward on the caller's stream still reads the old copy)
-            TRY(make_w16t(cfg, o, params, w.w16t, (ortk_stream)c.side->s));     // done before the decoder prefix the forward waits for
-            TRY(c.side_mark(nullptr));
-        } else {
-            TRY(make_w16t(cfg, o, params, w.w16t, stream));      // read by the backward that follows this forward
-        }
-    }
-    // sparse plans are rebuilt from THIS call's effective weights (a new mask sample per step): no stale images
-    c.ell_f = cfg->sparse_fwd;        // (built below, once it is known who uses it first)
     const float* P = params;
-    const int d = cfg->d_model, ff = cfg->d_ff, H = cfg->n_heads, L = cfg->n_layers, dk = d / H, V = cfg->vocab, A = w.adt;
-    const int B = bt->B, S = bt->S, R = bt->R, T = bt->T, spi = R / B;
+    const int d = cfg->d_model, ff = cfg->d_ff, L = cfg->n_layers, V = cfg->vocab, A = w.adt;
+    const int B = bt->B, S = bt->S, T = bt->T;
     const bool compact = batch_compact(bt);
     if (compact && (logp_out || !w.qdt_self || !w.qdt_cross)) return ORTK_EINVAL;     // fused criterion + bf16-operand attention only
-    // rows-stationary chains: their weight units go into streaming order once per forward (phase 2 finds phase 1's image)
-    ChainSet cs; chain_layout(*cfg, o, true, true, cs, w.Me, batch_compact(bt) ? bt->Mc : w.Md);
-    // (a sparse forward plan that takes a product of a chain switches the chains off; one over the other products — region embedding,
-    //  K|V projection of the memory, generator — or a data-gradient plan alone leaves them on)
-    if (cs.on && (!w.chain_pk || plan_hits_chain(c.ell_f, cs))) cs.on = false;
-    const bool dchains = cs.on && w.qdt_self == ORTK_BF16 && w.qdt_cross == ORTK_BF16 && A == ORTK_BF16;
-    hipEvent_t fplan_done = nullptr;
-    if (cfg->sparse_fwd && phase != 2) {
-        // With the chains on, no product of a layer is in the plan; unless the region embedding is, its first user is the K|V
-        // projection of the memory, after the encoder: the build (0.2 ms) then runs beside the encoder on the side stream.
-        const void* src = cfg->precision ? (const void*)w.w16 : (const void*)params;
-        const int sdt = cfg->precision ? ORTK_BF16 : ORTK_F32;
-        if (cs.on && c.use_side && Ctx::ell_block(c.ell_f, o.att_w, cfg->d_model, cfg->feat) < 0) {
-            TRY(c.fork());                        // (the bf16 weight copy is made on the caller's stream)
-            TRY(ortk_sparse_build(cfg->sparse_fwd, src, sdt, (ortk_stream)c.side->s));
-            TRY(c.side_mark(&fplan_done));
-        } else {
-            TRY(ortk_sparse_build(cfg->sparse_fwd, src, sdt, stream));
-        }
-    }
     const int64_t Me = w.Me, Md = compact ? bt->Mc : w.Md;
-    // Phase 1 has no captions, so it packs for the kernel forms of (Me, R * T).  A phase 2 on the valid positions whose row count
-    // picks the OTHER form of the chain kernel (76-row blocks stream the FFN units in another order) packs again, from the same bf16
-    // weight copy, for the layout chain_run() will derive from its own row count (the encoder's units, already consumed, ride along).
-    const bool repack2 = phase == 2 && cs.on && chain_wide(w.Md) != chain_wide(Md);
-    // (with the side streams: on the third queue, beside att_embed — 117 us the first chain used to wait for on the caller's stream;
-    //  the caller's stream and the side stream's decoder prefix wait for it right before their first chain)
-    hipEvent_t pack_done = nullptr;
-    if (cs.on && (phase != 2 || repack2)) {
-        if (c.use_side && phase != 2 && tuning().feats_bf16) {
-            hipEvent_t w16_ready = c.side->take();
-            pack_done = c.side->take();
-            if (hipEventRecord(w16_ready, c.s) != hipSuccess || hipStreamWaitEvent(c.side->s2, w16_ready, 0) != hipSuccess) return ORTK_EINVAL;
-            TRY(chain_pack_all(w.w16, w.chain_pk, cs.t, c.side->s2));
-            if (hipEventRecord(pack_done, c.side->s2) != hipSuccess) return ORTK_EINVAL;
-        } else {
-            TRY(chain_pack_all(w.w16, w.chain_pk, cs.t, c.s));
-        }
-    }
-    EncPtrs ep[MAXLAYERS]; enc_ptrs_from_ws(w, L, ep);
+    FwdHead head;
+    TRY(forward_head(c, o, w, bt, phase, head));
+    const ChainSet& cs = head.cs;
+    const bool dchains = cs.on && w.qdt_self == ORTK_BF16 && w.qdt_cross == ORTK_BF16 && A == ORTK_BF16;
+    const hipEvent_t pack_done = head.pack_done;
     const AttMode am = att_mode(cfg->share_att_dec);
-    const int64_t cw = o.cw, cv = o.cv;
     // Self-attention sublayer (and the cross-attention query projection) of decoder layer l, on context `cx`'s stream.
     auto self_part = [&](const Ctx& cx, int l, const float* x) -> int {
         const DecOff& e = o.dec[l]; const DecBuf& b = w.dec[l];
@@ -1079,12 +1053,9 @@ extern "C" int ortk_forward_phase(const ortk_config* cfg, const float* params, c
             TRY(ln_fwd(cx, x, e.n0a, e.n0b, b.y1, A, b.st1, Md));
             TRY(fwd_gemm(cx, b.y1, A, d, e.wqkv, P + e.bqkv, b.qkv, w.qdt_self, 3 * d, Md, am.n * d, d));
         }
-        ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = cx.prec; a.qkv_dtype = w.qdt_self;
-        a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, am.k * d, w.qdt_self); a.v = (const float*)off_elems(b.qkv, am.v * d, w.qdt_self);
-        a.ldq = a.ldk = a.ldv = 3 * d; a.o = b.o1; a.o_dtype = A; a.ldo = d;
-        a.kmask = w.keymask; a.p = b.Ps; a.nkv = R; a.H = H; a.Lq = T; a.Lk = T; a.dk = dk; a.causal_period = T;
-        a.drop_p = cx.p_drop(); a.drop_seed = cx.sub(dop(l, 0));
-        if (compact) { a.q_off = bt->cap_off; a.q_off_stride = 1; a.kv_ragged = 1; }      // a caption's keys are its own (valid) rows
+        ortk_attn_args a = dec_self_attn(cx, w, bt, l);
+        a.o = b.o1; a.o_dtype = A; a.ldo = d;
+        a.kmask = w.keymask; a.causal_period = T;
         TRY(ortk_attention_fwd(&a, (ortk_stream)cx.s));
         if (dchains) {                // [Wo + x -> LayerNorm 1 -> Wcq]
             ortk_chain_args ca; std::memset(&ca, 0, sizeof(ca));
@@ -1106,11 +1077,11 @@ extern "C" int ortk_forward_phase(const ortk_config* cfg, const float* params, c
     const bool prefix_side = c.use_side && phase == 0;       // (split phases: the token side has no encoder to run beside)
     if (prefix_side) {
         TRY(c.fork());                     // the side stream sees the bf16 weight copy
-        if (pack_done && hipStreamWaitEvent(c.side->s, pack_done, 0) != hipSuccess) return ORTK_EINVAL;      // ... and the packed chain weights
+        TRY(c.side_wait_ev(pack_done));    // ... and the packed chain weights
     }
     if (phase != 2)
-        TRY(encoder_forward(c, o, bt->att_feats, bt->boxes, bt->att_masks, B, S, w.x0, w.logbias, ep, w.mem, A, w.st_mem, w.qdt_enc,
-                            box_early ? &box_done : nullptr, &cs, w.chain_pk, true, f16 ? w.feats16 : nullptr, feats16_done, pack_done));
+        TRY(encoder_forward(c, o, bt->att_feats, bt->boxes, bt->att_masks, B, S, w.x0, w.logbias, w.enc, w.mem, A, w.st_mem, w.qdt_enc,
+                            head.box_early ? &head.box_done : nullptr, &cs, w.chain_pk, true, head.f16 ? w.feats16 : nullptr, head.feats16_done, pack_done));
     else TRY(c.wait_ev(pack_done));
     // From here on every operator with a dropout site runs on DECODER rows: on the valid positions it draws what the padded
     // (caption, position) layout draws (a step is the same function of its seed in both layouts; an SCST update on the valid
@@ -1122,7 +1093,7 @@ extern "C" int ortk_forward_phase(const ortk_config* cfg, const float* params, c
         if (cfg->sparse_bwd) bwd_plan_forget(cfg->sparse_bwd);
         return c.join();                   // (the transposed weight copy of the side stream included)
     }
-    TRY(c.wait_ev(fplan_done));
+    TRY(c.wait_ev(head.fplan_done));
     {
         const Ctx cx = prefix_side ? c.on_side() : c;
         // (no_pad_keys: rollout captions — the key mask hides nothing, as in the cached passes that drew them; ortk_batch)
@@ -1143,19 +1114,15 @@ extern "C" int ortk_forward_phase(const ortk_config* cfg, const float* params, c
         bwd_plan_built_by(cfg->sparse_bwd, ws, seed, train != 0);
     }
     // decoder
-    const int U = o.ckv_slots;            // distinct decoder layers: one K|V slice each in the packed projection
-    TRY(fwd_gemm(c, w.mem, A, d, o.ckv_w, P + o.ckv_b, w.ckv, w.qdt_cross, U * cw, Me, (int)(U * cw), d));
+    const int64_t ldkv = o.ckv_slots * o.cw;      // distinct decoder layers: one K|V slice each in the packed projection
+    TRY(fwd_gemm(c, w.mem, A, d, o.ckv_w, P + o.ckv_b, w.ckv, w.qdt_cross, ldkv, Me, (int)ldkv, d));
     const float* x = w.dx0;
     for (int l = 0; l < L; ++l) {
         const DecOff& e = o.dec[l]; const DecBuf& b = w.dec[l];
         if (l == 0 && prefix_side) TRY(c.wait_ev(prefix_done)); else TRY(self_part(c, l, x));
-        ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-        a.qkv_dtype = w.qdt_cross; a.q = (const float*)b.qc; a.ldq = d;
-        a.k = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw, w.qdt_cross); a.v = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw + cv, w.qdt_cross);
-        a.ldk = a.ldv = U * cw;
-        a.o = b.o2; a.o_dtype = A; a.ldo = d; a.kmask = bt->att_masks; a.p = b.Pc; a.nkv = B; a.H = H; a.Lq = spi * T; a.Lk = S; a.dk = dk;
-        a.drop_p = c.p_drop(); a.drop_seed = c.sub(dop(l, 2));
-        if (compact) { a.q_off = bt->cap_off; a.q_off_stride = spi; a.drop_rows = bt->row_pos; }      // an image's rows: those of its spi captions
+        ortk_attn_args a = cross_attn(c, o, w, bt, l);
+        a.o = b.o2; a.o_dtype = A; a.ldo = d;
+        a.kmask = bt->att_masks;
         TRY(ortk_attention_fwd(&a, stream));
         if (dchains) {                // [Wco + x -> LayerNorm 2 -> FFN + x -> LayerNorm 0 of layer l + 1 (or the stack's) -> next Wqkv]
             ortk_chain_args ca; std::memset(&ca, 0, sizeof(ca));
@@ -1242,6 +1209,216 @@ extern "C" int ortk_backward(const ortk_config* cfg, const float* params, float*
     return ortk_backward_phase(cfg, params, grads, bt, ws, ws_bytes, train, seed, 0, stream);
 }
 
+// ------------------------------------------------------------------------------------------------ backward
+// What the two halves of a backward share: the call's context and buffers, the rotation of the (rows, d) gradient temporaries, the
+// buffers and switches of the grouped weight gradients, the fold of a shared projection's two gradients.
+struct Bwd {
+    Ctx c;                       // (its pending-read table and side-stream sequence carry over from the decoder half to the encoder half)
+    const Offsets& o; const TrainWS& w; const ortk_batch* bt; float* G; ortk_stream stream;
+    int d, ff, L, A;
+    float inv_keep;
+    // the (rows, d) bf16 gradient temporary rotates over three buffers: its producers (ln_bwd's masked copy, the cross-
+    // attention dQ, the att_embed gate) never have to wait for the side-stream wgrad that still reads the previous one
+    // (grouped weight gradients: ten, so that the four of a layer stay untouched until the layer's launch has read them)
+    void* gt_pool[TrainWS::NGT]; int n_gt, gt_i = 0; void* gt_cur;
+    void* gt_new() { gt_i = (gt_i + 1) % n_gt; gt_cur = gt_pool[gt_i]; return gt_cur; }
+    // ortk_tuning.wgrad_group: the weight gradients of a layer / of the generator / of the memory's K|V projection as one launch each
+    bool grp_layers, grp_gen, grp_kv;
+    bool tail_group;             // the bf16 feature copy of this step's forward (same conditions there) lets att_embed's weight gradient join layer 0's group
+    void* gq_of(int l) const { return (grp_layers && (l & 1)) ? w.gqkv2 : w.gqkv; }      // (a layer's group still reads the other one)
+    void* gh_of(int l) const { return (grp_layers && (l & 1)) ? w.gh2 : w.gh; }
+    // share_att: column blocks of a (rows, 3 d) gradient that receive dQ (0) / dK / dV, and the add that folds the shared projection's
+    // two gradients together before the (rows, n*d) projection GEMMs
+    int fold(const AttMode& m, int64_t rows, void* gq) const {
+        if (m.gsrc < 0) return 0;
+        return ortk_axpy_cols(off_elems(gq, (int64_t)m.gsrc * d, A), off_elems(gq, (int64_t)m.gdst * d, A), A, 3 * d, rows, d, stream);
+    }
+};
+
+// ---- decoder half: generator, decoder stack, token embedding, cross-attention K/V projections; leaves the gradient
+// of the encoder memory in w.gy.  Every gradient at arena offsets >= ortk_arena_decoder_offset is final afterwards.
+static int backward_decoder_half(Bwd& s) {
+    Ctx& c = s.c;
+    const ortk_config* cfg = c.cfg;
+    const Offsets& o = s.o; const TrainWS& w = s.w; const ortk_batch* bt = s.bt;
+    float* const G = s.G; const ortk_stream stream = s.stream;
+    const int d = s.d, ff = s.ff, L = s.L, A = s.A, T = bt->T;
+    const bool compact = batch_compact(bt);
+    const int64_t Me = w.Me, Md = compact ? bt->Mc : w.Md;
+    // dK|dV slice of every decoder layer in w.gkv: distinct layers first (the order of the packed K|V weight block), the
+    // layers that share one of them behind.  Cross-attention with share_att "kv": all dK slices (width d) first, all dV slices
+    // behind them (column L*d on), folded by one add over L*d columns.
+    const int U = o.ckv_slots;
+    int gslot[MAXLAYERS];
+    { int extra = U; for (int l = 0; l < L; ++l) gslot[l] = cfg->share_dec[l] > 0 ? extra++ : o.ckv_slot[l]; }
+    const AttMode amd = att_mode(cfg->share_att_dec);
+    const int64_t cw = o.cw, ldg = (int64_t)L * 2 * d, gdv = cfg->share_att_dec == 1 ? (int64_t)L * d : d;
+    float* dx = w.ga; float* dx2 = w.gb;
+    c.drop_rows = compact ? bt->row_pos : nullptr;      // (decoder rows: the masked copies draw what the forward drew; reset below)
+    // generator (over the padded vocabulary: pad columns of dlogits are exact zeros)
+    const int Vp = (int)w.ldv;
+    c.grp_on = s.grp_gen;
+    TRY(wgrad_gemm(c, w.dlogits, A, w.ldv, w.dec_out, A, d, G + o.gen_w, G + o.gen_b, Md, Vp, d));
+    TRY(flush_wgrads(c));
+    c.grp_on = false;
+    TRY(dgrad_gemm(c, w.dlogits, A, w.ldv, o.gen_w, w.gy, ORTK_F32, d, Md, Vp, d));
+    TRY(ln_bwd(c, w.gy, w.dec[L - 1].xout, G, o.dec_na, o.dec_nb, w.st_out, nullptr, dx, Md, s.gt_new(), dop(L - 1, 5)));
+    for (int l = L - 1; l >= 0; --l) {
+        const DecOff& e = o.dec[l]; const DecBuf& b = w.dec[l];
+        const float* xin = l == 0 ? w.dx0 : w.dec[l - 1].xout;
+        const void* dt; int dtt;
+        void* const ghl = s.gh_of(l); void* const gql = s.gq_of(l);
+        c.grp_on = s.grp_layers;
+        // feed-forward sublayer
+        TRY(drop_bwd(c, dx, s.gt_cur, Md * d, dop(l, 5), &dt, &dtt, true));
+        TRY(wgrad_gemm(c, dt, dtt, d, b.h, A, ff, G + e.w2, G + e.b2, Md, d, ff));
+        TRY(dgrad_gemm(c, dt, dtt, d, e.w2, ghl, A, ff, Md, d, ff, b.h, A, ff, s.inv_keep));
+        TRY(wgrad_gemm(c, ghl, A, ff, b.y3, A, d, G + e.w1, G + e.b1, Md, ff, d));
+        TRY(dgrad_ln_bwd(c, ghl, A, ff, e.w1, Md, ff, d, w.gy, b.xm2, G, e.n2a, e.n2b, b.st3, dx, dx2, s.gt_new(), dop(l, 3)));
+        // cross-attention sublayer
+        TRY(drop_bwd(c, dx2, s.gt_cur, Md * d, dop(l, 3), &dt, &dtt, true));
+        TRY(wgrad_gemm(c, dt, dtt, d, b.o2, A, d, G + e.cow, G + e.cob, Md, d, d));
+        // the out-projection's input gradient only feeds the attention backward's products: bf16 beside bf16 Q / K / V
+        void* dO = w.qdt_cross ? w.gdo : (void*)w.gy;
+        TRY(dgrad_gemm(c, dt, dtt, d, e.cow, dO, w.qdt_cross, d, Md, d, d));
+        ortk_attn_args a = cross_attn(c, o, w, bt, l);
+        a.d_o = (const float*)dO; a.lddo = d; a.dq = s.gt_new(); a.lddq = d; a.dqkv_dtype = A;
+        a.d_k = off_elems(w.gkv, gslot[l] * cw, A); a.dv = off_elems(w.gkv, gslot[l] * cw + gdv, A);
+        a.lddk = a.lddv = ldg;
+        TRY(c.before_write(s.gt_cur));
+        TRY(ortk_attention_bwd(&a, stream));
+        TRY(wgrad_gemm(c, s.gt_cur, A, d, b.y2, A, d, G + e.cqw, G + e.cqb, Md, d, d));
+        {
+            const void* dq_ = s.gt_cur;
+            TRY(dgrad_ln_bwd(c, dq_, A, d, e.cqw, Md, d, d, w.gy, b.xm1, G, e.n1a, e.n1b, b.st2, dx2, dx, s.gt_new(), dop(l, 1), cfg->share_att_dec != 2));
+        }
+        // self-attention sublayer
+        TRY(drop_bwd(c, dx, s.gt_cur, Md * d, dop(l, 1), &dt, &dtt, true));
+        TRY(wgrad_gemm(c, dt, dtt, d, b.o1, A, d, G + e.wo, G + e.bo, Md, d, d));
+        dO = w.qdt_self ? w.gdo : (void*)w.gy;
+        TRY(dgrad_gemm(c, dt, dtt, d, e.wo, dO, w.qdt_self, d, Md, d, d));
+        a = dec_self_attn(c, w, bt, l);
+        attn_packed_grads(a, dO, gql, amd, d, A);
+        TRY(c.before_write(gql));
+        TRY(ortk_attention_bwd(&a, stream));
+        TRY(s.fold(amd, Md, gql));
+        TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Md, amd.n * d, d));
+        TRY(flush_wgrads(c, l == 0));        // the layer's six weight gradients: one launch
+        c.grp_on = false;
+        TRY(dgrad_ln_bwd(c, gql, A, 3 * d, e.wqkv, Md, amd.n * d, d, w.gy, xin, G, e.n0a, e.n0b, b.st1, dx, dx2, s.gt_new(), l > 0 ? (int)dop(l - 1, 5) : -1));
+        std::swap(dx, dx2);
+    }
+    // the embedding gradient (atomics into the 5 M-element table) only feeds the optimizer: beside the K/V projection GEMMs
+    if (c.use_side) {
+        TRY(c.fork());
+        TRY(embed_bwd_rows(bt->seqs, bt->seq_stride, dx, G + o.lut, Md, compact ? bt->row_pos : nullptr, T, d, c.p_drop(), c.sub(OP_EMB), c.side->s));
+        hipEvent_t e_done = nullptr;
+        TRY(c.side_mark(&e_done));
+        c.reads(dx, e_done);               // dx (w.ga / w.gb) is rewritten by the encoder half
+    } else {
+        TRY(embed_bwd_rows(bt->seqs, bt->seq_stride, dx, G + o.lut, Md, compact ? bt->row_pos : nullptr, T, d, c.p_drop(), c.sub(OP_EMB), c.s));
+    }
+    // cross-attention K/V projections of all layers, and the gradient of the encoder memory
+    // layers that share weights also share the projected K|V: their dK|dV slices add up into the slice of the layer they share
+    if (cfg->share_att_dec == 1)           // K = V: dK += dV, all layers at once
+        TRY(ortk_axpy_cols(off_elems(w.gkv, gdv, A), w.gkv, A, ldg, Me, (int64_t)L * d, stream));
+    for (int l = 0; l < L; ++l)
+        if (cfg->share_dec[l] > 0)
+            TRY(ortk_axpy_cols(off_elems(w.gkv, gslot[l] * cw, A), off_elems(w.gkv, o.ckv_slot[l] * cw, A), A, ldg, Me, cw, stream));
+    c.grp_on = s.grp_kv;
+    TRY(wgrad_gemm(c, w.gkv, A, ldg, w.mem, A, d, G + o.ckv_w, G + o.ckv_b, Me, (int)(U * cw), d));
+    TRY(flush_wgrads(c, true));
+    c.grp_on = false;
+    TRY(dgrad_gemm(c, w.gkv, A, ldg, o.ckv_w, w.gy, ORTK_F32, d, Me, (int)(U * cw), d));
+    TRY(c.join());
+    c.drop_rows = nullptr;
+    return 0;
+}
+
+// ---- encoder half (reads the memory gradient left in w.gy)
+static int backward_encoder_half(Bwd& s) {
+    Ctx& c = s.c;
+    const ortk_config* cfg = c.cfg;
+    const Offsets& o = s.o; const TrainWS& w = s.w; const ortk_batch* bt = s.bt;
+    float* const G = s.G; const ortk_stream stream = s.stream;
+    const int d = s.d, ff = s.ff, L = s.L, A = s.A, H = cfg->n_heads, B = bt->B, S = bt->S;
+    const int64_t Me = w.Me;
+    const AttMode ame = att_mode(cfg->share_att_enc);
+    // Gradient of the geometry-bias weights of layers [l0, l0 + n): only feeds the optimizer.  With the side stream the
+    // layers 1 .. L-1 go as soon as layer 1's attention backward has written their score gradients — one 0.36 ms VALU
+    // kernel for all layers at the very end of the step had the att_embed weight gradient as its only company (the
+    // embedding's sin / cos are then evaluated twice: 2 x 0.08 ms of side-stream time against 0.25 ms of exposed tail).
+    const bool box_split = c.use_side && !cfg->no_box && L > 2;
+    hipEvent_t box_done_ev = nullptr;
+    auto box_grad = [&](int l0, int n) -> int {
+        const float* wg[MAXLAYERS]; const float* bg[MAXLAYERS]; float* dwg[MAXLAYERS]; float* dbg[MAXLAYERS];
+        for (int l = 0; l < n; ++l) {
+            wg[l] = c.P + o.enc[l0 + l].wg; bg[l] = c.P + o.enc[l0 + l].bg; dwg[l] = G + o.enc[l0 + l].wg; dbg[l] = G + o.enc[l0 + l].bg;
+        }
+        const float* ds = w.dscore + (int64_t)l0 * B * H * S * S;
+        auto launch = [&](hipStream_t q) {
+            return ortk_box_logbias_bwd(bt->boxes, wg, bg, cfg->box_trig ? dim_mat() : nullptr, ds, dwg, dbg, n, B, S, H, (ortk_stream)q);
+        };
+        // on the THIRD queue (in order behind the side stream's weight-gradient groups it delayed every later group by its 0.3 ms:
+        // the side stream reached the end of the step 0.25 ms late); joined at the end of the backward
+        return c.use_side ? c.side_launch(c.side->s2, &box_done_ev, launch) : launch(c.s);
+    };
+    float* dx = w.ga; float* dx2 = w.gb;
+    TRY(ln_bwd(c, w.gy, w.enc[L - 1].xout, G, o.enc_na, o.enc_nb, w.st_mem, nullptr, dx, Me, s.gt_new(), eop(L - 1, 3)));
+    for (int l = L - 1; l >= 0; --l) {
+        const EncOff& e = o.enc[l]; const EncBuf& b = w.enc[l];
+        const float* xin = l == 0 ? w.x0 : w.enc[l - 1].xout;
+        const void* dt; int dtt;
+        void* const ghl = s.gh_of(l); void* const gql = s.gq_of(l);
+        c.grp_on = s.grp_layers;
+        TRY(drop_bwd(c, dx, s.gt_cur, Me * d, eop(l, 3), &dt, &dtt, true));
+        TRY(wgrad_gemm(c, dt, dtt, d, b.h, A, ff, G + e.w2, G + e.b2, Me, d, ff));
+        TRY(dgrad_gemm(c, dt, dtt, d, e.w2, ghl, A, ff, Me, d, ff, b.h, A, ff, s.inv_keep));
+        TRY(wgrad_gemm(c, ghl, A, ff, b.y2, A, d, G + e.w1, G + e.b1, Me, ff, d));
+        TRY(dgrad_ln_bwd(c, ghl, A, ff, e.w1, Me, ff, d, w.gy, b.xm, G, e.n1a, e.n1b, b.st2, dx, dx2, s.gt_new(), eop(l, 1)));
+        TRY(drop_bwd(c, dx2, s.gt_cur, Me * d, eop(l, 1), &dt, &dtt, true));
+        TRY(wgrad_gemm(c, dt, dtt, d, b.o, A, d, G + e.wo, G + e.bo, Me, d, d));
+        // (layer 0 with the tail group: the three gradients whose operands exist go now; wqkv's and att_embed's, which the step ends with, form a small last group)
+        if (l == 0 && s.tail_group) TRY(flush_wgrads(c));
+        void* dOe = w.qdt_enc ? w.gdo : (void*)w.gy;
+        TRY(dgrad_gemm(c, dt, dtt, d, e.wo, dOe, w.qdt_enc, d, Me, d, d));
+        ortk_attn_args a = enc_self_attn(c, b, w.qdt_enc, l, B, S);
+        attn_packed_grads(a, dOe, gql, ame, d, A);
+        a.dscore = cfg->no_box ? nullptr : w.dscore + (int64_t)l * B * H * S * S;
+        TRY(c.before_write(gql));
+        TRY(ortk_attention_bwd(&a, stream));
+        if (l == 1 && box_split) TRY(box_grad(1, L - 1));     // layers 1 .. L-1: beside the last two encoder layers
+        if (l == 0 && s.tail_group && !cfg->no_box) TRY(box_grad(0, box_split ? 1 : L));      // (third queue: done before the step's last launch needs the units)
+        TRY(s.fold(ame, Me, gql));
+        TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Me, ame.n * d, d));
+        if (l > 0 || !s.tail_group) TRY(flush_wgrads(c, l == 0));        // the layer's four weight gradients: one launch (layer 0: below)
+        c.grp_on = false;
+        TRY(dgrad_ln_bwd(c, gql, A, 3 * d, e.wqkv, Me, ame.n * d, d, w.gy, xin, G, e.n0a, e.n0b, b.st1, dx2, dx, s.gt_new(), l > 0 ? (int)eop(l - 1, 3) : -1));
+    }
+    // The tail.  With the grouped weight gradients and the bf16 feature copy: layer 0's last weight gradient was held back, att_embed's
+    // joins the one that is still held back (wqkv's), and the two go as ONE launch on the side stream; the geometry-bias gradient of layer 0 went
+    // to the third queue right behind layer 0's attention backward (its workgroups hold the LDS of every unit: beside the last launch they delayed it by their 63 us).  (Before: an urgent 4-gradient launch beside the last LayerNorm backward, which
+    // took 116 instead of 24 us for it, then a 120-us att_embed launch of its own on the caller's stream.)
+    if (!cfg->no_box && !s.tail_group) TRY(box_grad(0, box_split ? 1 : L));
+    // att_embed: x0 = dropout(relu(.) * mask)  ->  d(pre-activation) = dx * [x0 > 0] / (1 - p_src)
+    TRY(c.before_write(s.gt_new()));
+    TRY(ortk_gate_apply(dx, w.x0, s.gt_cur, A, Me * d, c.p_src() > 0.f ? 1.f / (1.f - c.p_src()) : 1.f, stream));
+    if (s.tail_group) {
+        c.grp_on = true;
+        TRY(wgrad_gemm(c, s.gt_cur, A, d, w.feats16, ORTK_BF16, cfg->feat, G + o.att_w, G + o.att_b, Me, d, cfg->feat));
+        TRY(flush_wgrads(c, true));
+        c.grp_on = false;
+    } else {   // the last weight gradient stays on the caller's stream: the side stream is busy with the geometry-bias gradient
+        const bool us = c.use_side;
+        c.use_side = false;
+        TRY(wgrad_gemm(c, s.gt_cur, A, d, bt->att_feats, ORTK_F32, cfg->feat, G + o.att_w, G + o.att_b, Me, d, cfg->feat));
+        c.use_side = us;
+    }
+    TRY(c.wait_ev(box_done_ev));
+    return c.join();       // every gradient is final in the caller's stream order
+}
+
+// phase 0: the whole backward.  phase 1: the decoder half only; phase 2: the encoder half on the memory gradient phase 1 left in w.gy.
 extern "C" int ortk_backward_phase(const ortk_config* cfg, const float* params, float* grads, const ortk_batch* bt, void* ws,
                                    size_t ws_bytes, int32_t train, uint64_t seed, int32_t phase, ortk_stream stream) {
     if (phase < 0 || phase > 2) return ORTK_EINVAL;
@@ -1266,378 +1443,20 @@ extern "C" int ortk_backward_phase(const ortk_config* cfg, const float* params, 
     }
     c.side = (c.adt == ORTK_BF16 && !ortk_prof_serial()) ? side_for(c.s) : nullptr;
     c.use_side = c.side != nullptr;
-    float* G = grads;
-    const int d = cfg->d_model, ff = cfg->d_ff, H = cfg->n_heads, L = cfg->n_layers, dk = d / H, A = w.adt;
-    const int B = bt->B, S = bt->S, R = bt->R, T = bt->T, spi = R / B;
-    const bool compact = batch_compact(bt);
-    if (compact && (!w.qdt_self || !w.qdt_cross)) return ORTK_EINVAL;
-    const int64_t Me = w.Me, Md = compact ? bt->Mc : w.Md;
-    const float inv_keep = c.p_drop() > 0.f ? 1.f / (1.f - c.p_drop()) : 1.f;
-    // dK|dV slice of every decoder layer in w.gkv: distinct layers first (the order of the packed K|V weight block), the
-    // layers that share one of them behind
-    const int U = o.ckv_slots;
-    int gslot[MAXLAYERS];
-    { int extra = U; for (int l = 0; l < L; ++l) gslot[l] = cfg->share_dec[l] > 0 ? extra++ : o.ckv_slot[l]; }
-    // share_att: column blocks of w.gqkv that receive dQ (0) / dK / dV, and the add that folds the shared projection's two
-    // gradients together before the (rows, n*d) projection GEMMs.  Cross-attention with "kv": all dK slices (width d)
-    // first, all dV slices behind them (column L*d on), folded by one add over L*d columns.
-    const AttMode ame = att_mode(cfg->share_att_enc), amd = att_mode(cfg->share_att_dec);
-    const int64_t cw = o.cw, cv = o.cv, ldg = (int64_t)L * 2 * d, gdv = cfg->share_att_dec == 1 ? (int64_t)L * d : d;
-    auto fold = [&](const AttMode& m, int64_t rows, void* gq) -> int {
-        if (m.gsrc < 0) return 0;
-        return ortk_axpy_cols(off_elems(gq, (int64_t)m.gsrc * d, A), off_elems(gq, (int64_t)m.gdst * d, A), A, 3 * d, rows, d, stream);
-    };
-
-    float* dx = w.ga; float* dx2 = w.gb;
-    // the (rows, d) bf16 gradient temporary rotates over three buffers: its producers (ln_bwd's masked copy, the cross-
-    // attention dQ, the att_embed gate) never have to wait for the side-stream wgrad that still reads the previous one
-    // (grouped weight gradients: ten, so that the four of a layer stay untouched until the layer's launch has read them)
-    const int wgm = tuning().wgrad_group;
-    const bool grouped = A == ORTK_BF16 && (wgm & 7) != 0 && w.gtp[TrainWS::NGT - 1] != nullptr;
-    const int n_gt = grouped ? TrainWS::NGT : 3;
-    void* gt_pool[TrainWS::NGT] = {w.gt, w.gt2, w.gt3};
-    for (int i = 3; i < n_gt; ++i) gt_pool[i] = w.gtp[i];
-    int gt_i = 0;
-    void* gt_cur = w.gt;
-    auto gt_new = [&]() { gt_i = (gt_i + 1) % n_gt; gt_cur = gt_pool[gt_i]; return gt_cur; };
     c.wg_ws = w.wg_ws; c.wg_ws_bytes = w.wg_ws_bytes;
-    // Backward chains (ortk_chain.hip): everything between two attention-backward calls except the weight gradients in one
-    // rows-stationary launch each.  Mixed precision, bf16 Q / K / V / dO in all three attention stacks, dense products.
-    ChainSet bs; bchain_layout(*cfg, o, bs);
-    const bool bch_any = bs.on && w.chain_pk_b && A == ORTK_BF16 && w.qdt_self == ORTK_BF16 && w.qdt_cross == ORTK_BF16 && w.qdt_enc == ORTK_BF16 &&
-                         !c.ell_b && !cfg->sparse_fwd;
-    // ortk_tuning.row_chain: 1 = forward chains only, 2 = + the encoder's backward (one round of workgroups at 9 216 rows), 3 = + the decoder's
-    const bool bch_enc = bch_any && tuning().row_chain >= 2, bch = bch_any && tuning().row_chain >= 3;
-    if (bch_enc && phase != 2) TRY(chain_pack_all(w.w16t, w.chain_pk_b, bs.t, c.s));
-    const bool grp_layers = grouped && (wgm & 1), grp_gen = grouped && (wgm & 2), grp_kv = grouped && (wgm & 4);
-    // the bf16 feature copy of this step's forward (same conditions there) lets att_embed's weight gradient join layer 0's group
-    const bool tail_group = grp_layers && c.use_side && w.feats16 && (cfg->feat % 64) == 0 && tuning().feats_bf16 && !bch_enc;
-    auto gq_of = [&](int l) { return (grp_layers && (l & 1)) ? w.gqkv2 : w.gqkv; };
-    auto gh_of = [&](int l) { return (grp_layers && (l & 1)) ? w.gh2 : w.gh; };
-    const int NCc = ff / 512;
-    int gh_i = 0;
-    auto gh_new = [&]() { gh_i ^= 1; return gh_i ? w.gh2 : w.gh; };
-    // X = [FFN' -> LayerNorm' -> . Wout] of one layer, standalone (the top of a stack) or as the tail of a ZX chain: the fields of `ca`
-    auto x_part = [&](ortk_bchain_args& ca, const void* hrow, void* ghbuf, const float* xrows, const float* strows, int64_t na, int64_t nb,
-                      const float* dres, float* dxo, void* dzo, uint32_t seed, void* dO) {
-        ca.NC = NCc; ca.hgate = hrow; ca.gh = ghbuf; ca.gate_scale = inv_keep;
-        ca.xb = xrows; ca.stb = strows; ca.gb = params + na; ca.dresb = dres; ca.dxb = dxo; ca.dab = G + na; ca.dbb = G + nb;
-        ca.dzb = dzo; ca.seed_b = seed; ca.mask_b = 1;
-        ca.n2 = 1; ca.out2 = dO;
-    };
-    if (phase != 2) {
-    c.drop_rows = compact ? bt->row_pos : nullptr;      // (decoder rows: the masked copies draw what the forward drew; reset below)
-    // ---- decoder half: generator, decoder stack, token embedding, cross-attention K/V projections; leaves the gradient
-    // of the encoder memory in w.gy.  Every gradient at arena offsets >= ortk_arena_decoder_offset is final afterwards.
-    // generator (over the padded vocabulary: pad columns of dlogits are exact zeros)
-    const int Vp = (int)w.ldv;
-    c.grp_on = grp_gen;
-    TRY(wgrad_gemm(c, w.dlogits, A, w.ldv, w.dec_out, A, d, G + o.gen_w, G + o.gen_b, Md, Vp, d));
-    TRY(flush_wgrads(c));
-    c.grp_on = false;
-    TRY(dgrad_gemm(c, w.dlogits, A, w.ldv, o.gen_w, w.gy, ORTK_F32, d, Md, Vp, d));
-    TRY(ln_bwd(c, w.gy, w.dec[L - 1].xout, G, o.dec_na, o.dec_nb, w.st_out, nullptr, dx, Md, gt_new(), dop(L - 1, 5)));
-    if (bch) {
-        // cur = gradient of the FFN sublayer's INPUT rows (xm2) of the layer in hand, oth = the other fp32 buffer; dtA / dtB = the masked
-        // bf16 gradients the weight gradients of W2 / Wco read; ghb = the FFN hidden gradient (W1's weight gradient)
-        float* cur = dx2; float* oth = dx;
-        void* dtA = gt_cur; void* dtB = gt_new(); void* ghb = gh_new();
-        {   // X of the top layer, on the masked gradient the final LayerNorm's backward left
-            const DecOff& e = o.dec[L - 1]; const DecBuf& b = w.dec[L - 1];
-            ortk_bchain_args ca; std::memset(&ca, 0, sizeof(ca)); ca.drop_rows = c.drop_rows;
-            ca.n_units = bs.units(bs.bx_top); ca.M = Md; ca.nin = 0; ca.dz0 = dtA;
-            x_part(ca, b.h, ghb, b.xm2, b.st3, e.n2a, e.n2b, dx, cur, dtB, c.sub(dop(L - 1, 3)), w.gdo);
-            ca.drop_p = c.p_drop(); ca.eps = 1e-6f;
-            TRY(c.before_write(dtB)); TRY(c.before_write(ghb));
-            TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.bx_top), c.s));
-        }
-        for (int l = L - 1; l >= 0; --l) {
-            const DecOff& e = o.dec[l]; const DecBuf& b = w.dec[l];
-            const float* xin = l == 0 ? w.dx0 : w.dec[l - 1].xout;
-            void* const gql = gq_of(l);
-            c.grp_on = grp_layers;
-            TRY(wgrad_gemm(c, dtA, A, d, b.h, A, ff, G + e.w2, G + e.b2, Md, d, ff));
-            TRY(wgrad_gemm(c, ghb, A, ff, b.y3, A, d, G + e.w1, G + e.b1, Md, ff, d));
-            TRY(wgrad_gemm(c, dtB, A, d, b.o2, A, d, G + e.cow, G + e.cob, Md, d, d));
-            // cross-attention backward: dO = w.gdo (the chain's last product) -> dq, dK | dV
-            void* dq = gt_new();
-            ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-            a.qkv_dtype = w.qdt_cross; a.q = (const float*)b.qc; a.ldq = d;
-            a.k = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw, w.qdt_cross); a.v = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw + cv, w.qdt_cross);
-            a.ldk = a.ldv = U * cw;
-            a.p = b.Pc; a.nkv = B; a.H = H; a.Lq = spi * T; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(dop(l, 2));
-            a.d_o = (const float*)w.gdo; a.lddo = d; a.dq = dq; a.lddq = d; a.dqkv_dtype = A;
-            a.d_k = off_elems(w.gkv, gslot[l] * cw, A); a.dv = off_elems(w.gkv, gslot[l] * cw + gdv, A);
-            a.lddk = a.lddv = ldg;
-            if (compact) { a.q_off = bt->cap_off; a.q_off_stride = spi; a.drop_rows = bt->row_pos; }
-            TRY(c.before_write(dq));
-            TRY(ortk_attention_bwd(&a, stream));
-            TRY(wgrad_gemm(c, dq, A, d, b.y2, A, d, G + e.cqw, G + e.cqb, Md, d, d));
-            // Y: [dq . Wcq -> LayerNorm 1' (+ cur) -> masked copy -> . Wo]
-            void* dtD = gt_new();
-            {
-                ortk_bchain_args ca; std::memset(&ca, 0, sizeof(ca)); ca.drop_rows = c.drop_rows;
-                ca.n_units = bs.units(bs.by[l]); ca.M = Md; ca.nin = 1; ca.ain = dq; ca.ld_ain = d;
-                ca.xa = b.xm1; ca.sta = b.st2; ca.ga = params + e.n1a; ca.dresa = cur; ca.dxa = oth; ca.daa = G + e.n1a; ca.dba = G + e.n1b;
-                ca.dza = dtD; ca.seed_a = c.sub(dop(l, 1)); ca.mask_a = 1;
-                ca.n2 = 1; ca.out2 = w.gdo;
-                ca.drop_p = c.p_drop(); ca.eps = 1e-6f;
-                TRY(c.before_write(dtD));
-                TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.by[l]), c.s));
-            }
-            TRY(wgrad_gemm(c, dtD, A, d, b.o1, A, d, G + e.wo, G + e.bo, Md, d, d));
-            // self-attention backward: dO = w.gdo -> packed dQ | dK | dV
-            std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-            a.qkv_dtype = w.qdt_self; a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, amd.k * d, w.qdt_self);
-            a.v = (const float*)off_elems(b.qkv, amd.v * d, w.qdt_self); a.ldq = a.ldk = a.ldv = 3 * d;
-            a.p = b.Ps; a.nkv = R; a.H = H; a.Lq = T; a.Lk = T; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(dop(l, 0));
-            a.d_o = (const float*)w.gdo; a.lddo = d; a.dqkv_dtype = A;
-            a.dq = gql; a.d_k = off_elems(gql, amd.gk * d, A); a.dv = off_elems(gql, amd.gv * d, A); a.lddq = a.lddk = a.lddv = 3 * d;
-            if (compact) { a.q_off = bt->cap_off; a.q_off_stride = 1; a.kv_ragged = 1; }
-            TRY(c.before_write(gql));
-            TRY(ortk_attention_bwd(&a, stream));
-            TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Md, 3 * d, d));
-            TRY(flush_wgrads(c, l == 0));
-            c.grp_on = false;
-            // Z (+ X of the layer below): [dQKV . Wqkv -> LayerNorm 0' (+ oth) -> masked copy] [-> FFN' -> LayerNorm 2' -> masked copy -> . Wco]
-            ortk_bchain_args ca; std::memset(&ca, 0, sizeof(ca)); ca.drop_rows = c.drop_rows;
-            ca.M = Md; ca.nin = 3; ca.ain = gql; ca.ld_ain = 3 * d;
-            ca.xa = xin; ca.sta = b.st1; ca.ga = params + e.n0a; ca.dresa = oth; ca.dxa = cur; ca.daa = G + e.n0a; ca.dba = G + e.n0b;
-            ca.drop_p = c.p_drop(); ca.eps = 1e-6f;
-            if (l > 0) {
-                const DecOff& en = o.dec[l - 1]; const DecBuf& bn = w.dec[l - 1];
-                dtA = gt_new(); void* dtBn = gt_new(); ghb = gh_new();
-                ca.n_units = bs.units(bs.bzx[l]);
-                ca.dza = dtA; ca.seed_a = c.sub(dop(l - 1, 5)); ca.mask_a = 1;
-                x_part(ca, bn.h, ghb, bn.xm2, bn.st3, en.n2a, en.n2b, cur, oth, dtBn, c.sub(dop(l - 1, 3)), w.gdo);
-                TRY(c.before_write(dtA)); TRY(c.before_write(dtBn)); TRY(c.before_write(ghb));
-                TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.bzx[l]), c.s));
-                dtB = dtBn;
-                std::swap(cur, oth);          // cur = gradient of xm2 of layer l - 1 (what the chain wrote last)
-            } else {
-                ca.n_units = bs.units(bs.bz0);
-                TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.bz0), c.s));
-                dx = cur; dx2 = oth;           // the gradient of the embedded tokens
-            }
-        }
-    } else
-    for (int l = L - 1; l >= 0; --l) {
-        const DecOff& e = o.dec[l]; const DecBuf& b = w.dec[l];
-        const float* xin = l == 0 ? w.dx0 : w.dec[l - 1].xout;
-        const void* dt; int dtt;
-        void* const ghl = gh_of(l); void* const gql = gq_of(l);
-        c.grp_on = grp_layers;
-        // feed-forward sublayer
-        TRY(drop_bwd(c, dx, gt_cur, Md * d, dop(l, 5), &dt, &dtt, true));
-        TRY(wgrad_gemm(c, dt, dtt, d, b.h, A, ff, G + e.w2, G + e.b2, Md, d, ff));
-        TRY(dgrad_gemm(c, dt, dtt, d, e.w2, ghl, A, ff, Md, d, ff, b.h, A, ff, inv_keep));
-        TRY(wgrad_gemm(c, ghl, A, ff, b.y3, A, d, G + e.w1, G + e.b1, Md, ff, d));
-        TRY(dgrad_ln_bwd(c, ghl, A, ff, e.w1, Md, ff, d, w.gy, b.xm2, G, e.n2a, e.n2b, b.st3, dx, dx2, gt_new(), dop(l, 3)));
-        // cross-attention sublayer
-        TRY(drop_bwd(c, dx2, gt_cur, Md * d, dop(l, 3), &dt, &dtt, true));
-        TRY(wgrad_gemm(c, dt, dtt, d, b.o2, A, d, G + e.cow, G + e.cob, Md, d, d));
-        // the out-projection's input gradient only feeds the attention backward's products: bf16 beside bf16 Q / K / V
-        void* dO = w.qdt_cross ? w.gdo : (void*)w.gy;
-        TRY(dgrad_gemm(c, dt, dtt, d, e.cow, dO, w.qdt_cross, d, Md, d, d));
-        ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-        a.qkv_dtype = w.qdt_cross; a.q = (const float*)b.qc; a.ldq = d;
-        a.k = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw, w.qdt_cross); a.v = (const float*)off_elems(w.ckv, o.ckv_slot[l] * cw + cv, w.qdt_cross);
-        a.ldk = a.ldv = U * cw;
-        a.p = b.Pc; a.nkv = B; a.H = H; a.Lq = spi * T; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(dop(l, 2));
-        a.d_o = (const float*)dO; a.lddo = d; a.dq = gt_new(); a.lddq = d; a.dqkv_dtype = A;
-        a.d_k = off_elems(w.gkv, gslot[l] * cw, A); a.dv = off_elems(w.gkv, gslot[l] * cw + gdv, A);
-        a.lddk = a.lddv = ldg;
-        if (compact) { a.q_off = bt->cap_off; a.q_off_stride = spi; a.drop_rows = bt->row_pos; }
-        TRY(c.before_write(gt_cur));
-        TRY(ortk_attention_bwd(&a, stream));
-        TRY(wgrad_gemm(c, gt_cur, A, d, b.y2, A, d, G + e.cqw, G + e.cqb, Md, d, d));
-        {
-            const void* dq_ = gt_cur;
-            TRY(dgrad_ln_bwd(c, dq_, A, d, e.cqw, Md, d, d, w.gy, b.xm1, G, e.n1a, e.n1b, b.st2, dx2, dx, gt_new(), dop(l, 1), cfg->share_att_dec != 2));
-        }
-        // self-attention sublayer
-        TRY(drop_bwd(c, dx, gt_cur, Md * d, dop(l, 1), &dt, &dtt, true));
-        TRY(wgrad_gemm(c, dt, dtt, d, b.o1, A, d, G + e.wo, G + e.bo, Md, d, d));
-        dO = w.qdt_self ? w.gdo : (void*)w.gy;
-        TRY(dgrad_gemm(c, dt, dtt, d, e.wo, dO, w.qdt_self, d, Md, d, d));
-        std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-        a.qkv_dtype = w.qdt_self; a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, amd.k * d, w.qdt_self);
-        a.v = (const float*)off_elems(b.qkv, amd.v * d, w.qdt_self); a.ldq = a.ldk = a.ldv = 3 * d;
-        a.p = b.Ps; a.nkv = R; a.H = H; a.Lq = T; a.Lk = T; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(dop(l, 0));
-        a.d_o = (const float*)dO; a.lddo = d; a.dqkv_dtype = A;
-        a.dq = gql; a.d_k = off_elems(gql, amd.gk * d, A); a.dv = off_elems(gql, amd.gv * d, A); a.lddq = a.lddk = a.lddv = 3 * d;
-        if (compact) { a.q_off = bt->cap_off; a.q_off_stride = 1; a.kv_ragged = 1; }
-        TRY(c.before_write(gql));
-        TRY(ortk_attention_bwd(&a, stream));
-        TRY(fold(amd, Md, gql));
-        TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Md, amd.n * d, d));
-        TRY(flush_wgrads(c, l == 0));        // the layer's six weight gradients: one launch
-        c.grp_on = false;
-        TRY(dgrad_ln_bwd(c, gql, A, 3 * d, e.wqkv, Md, amd.n * d, d, w.gy, xin, G, e.n0a, e.n0b, b.st1, dx, dx2, gt_new(), l > 0 ? (int)dop(l - 1, 5) : -1));
-        std::swap(dx, dx2);
-    }
-    // the embedding gradient (atomics into the 5 M-element table) only feeds the optimizer: beside the K/V projection GEMMs
-    if (c.use_side) {
-        TRY(c.fork());
-        TRY(embed_bwd_rows(bt->seqs, bt->seq_stride, dx, G + o.lut, Md, compact ? bt->row_pos : nullptr, T, d, c.p_drop(), c.sub(OP_EMB), c.side->s));
-        hipEvent_t e_done = nullptr;
-        TRY(c.side_mark(&e_done));
-        c.reads(dx, e_done);               // dx (w.ga / w.gb) is rewritten by the encoder half
-    } else {
-        TRY(embed_bwd_rows(bt->seqs, bt->seq_stride, dx, G + o.lut, Md, compact ? bt->row_pos : nullptr, T, d, c.p_drop(), c.sub(OP_EMB), ortk_s(stream)));
-    }
-    // cross-attention K/V projections of all layers, and the gradient of the encoder memory
-    // layers that share weights also share the projected K|V: their dK|dV slices add up into the slice of the layer they share
-    if (cfg->share_att_dec == 1)           // K = V: dK += dV, all layers at once
-        TRY(ortk_axpy_cols(off_elems(w.gkv, gdv, A), w.gkv, A, ldg, Me, (int64_t)L * d, stream));
-    for (int l = 0; l < L; ++l)
-        if (cfg->share_dec[l] > 0)
-            TRY(ortk_axpy_cols(off_elems(w.gkv, gslot[l] * cw, A), off_elems(w.gkv, o.ckv_slot[l] * cw, A), A, ldg, Me, cw, stream));
-    c.grp_on = grp_kv;
-    TRY(wgrad_gemm(c, w.gkv, A, ldg, w.mem, A, d, G + o.ckv_w, G + o.ckv_b, Me, (int)(U * cw), d));
-    TRY(flush_wgrads(c, true));
-    c.grp_on = false;
-    TRY(dgrad_gemm(c, w.gkv, A, ldg, o.ckv_w, w.gy, ORTK_F32, d, Me, (int)(U * cw), d));
-    TRY(c.join());
-    c.drop_rows = nullptr;
-    }
+    if (batch_compact(bt) && (!w.qdt_self || !w.qdt_cross)) return ORTK_EINVAL;
+    const int A = w.adt, wgm = tuning().wgrad_group;
+    const bool grouped = A == ORTK_BF16 && (wgm & 7) != 0 && w.gtp[TrainWS::NGT - 1] != nullptr;
+    Bwd s{c, o, w, bt, grads, stream, cfg->d_model, cfg->d_ff, cfg->n_layers, A, c.p_drop() > 0.f ? 1.f / (1.f - c.p_drop()) : 1.f};
+    s.n_gt = grouped ? TrainWS::NGT : 3;
+    s.gt_pool[0] = w.gt; s.gt_pool[1] = w.gt2; s.gt_pool[2] = w.gt3;
+    for (int i = 3; i < s.n_gt; ++i) s.gt_pool[i] = w.gtp[i];
+    s.gt_cur = w.gt;
+    s.grp_layers = grouped && (wgm & 1); s.grp_gen = grouped && (wgm & 2); s.grp_kv = grouped && (wgm & 4);
+    s.tail_group = s.grp_layers && c.use_side && w.feats16 && (cfg->feat % 64) == 0 && tuning().feats_bf16;
+    if (phase != 2) TRY(backward_decoder_half(s));
     if (phase == 1) return 0;
-    // ---- encoder half (reads the memory gradient left in w.gy)
-    // Gradient of the geometry-bias weights of layers [l0, l0 + n): only feeds the optimizer.  With the side stream the
-    // layers 1 .. L-1 go as soon as layer 1's attention backward has written their score gradients — one 0.36 ms VALU
-    // kernel for all layers at the very end of the step had the att_embed weight gradient as its only company (the
-    // embedding's sin / cos are then evaluated twice: 2 x 0.08 ms of side-stream time against 0.25 ms of exposed tail).
-    const bool box_split = c.use_side && !cfg->no_box && L > 2;
-    hipEvent_t box_done_ev = nullptr;
-    auto box_grad = [&](int l0, int n) -> int {
-        const float* wg[MAXLAYERS]; const float* bg[MAXLAYERS]; float* dwg[MAXLAYERS]; float* dbg[MAXLAYERS];
-        for (int l = 0; l < n; ++l) {
-            wg[l] = params + o.enc[l0 + l].wg; bg[l] = params + o.enc[l0 + l].bg; dwg[l] = G + o.enc[l0 + l].wg; dbg[l] = G + o.enc[l0 + l].bg;
-        }
-        const float* ds = w.dscore + (int64_t)l0 * B * H * S * S;
-        if (c.use_side) {
-            // on the THIRD queue (in order behind the side stream's weight-gradient groups it delayed every later group by its 0.3 ms:
-            // the side stream reached the end of the step 0.25 ms late); joined at the end of the backward
-            hipEvent_t ready = c.side->take();
-            box_done_ev = c.side->take();
-            if (hipEventRecord(ready, c.s) != hipSuccess || hipStreamWaitEvent(c.side->s2, ready, 0) != hipSuccess) return ORTK_EINVAL;
-            TRY(ortk_box_logbias_bwd(bt->boxes, wg, bg, cfg->box_trig ? dim_mat() : nullptr, ds, dwg, dbg, n, B, S, H, (ortk_stream)c.side->s2));
-            if (hipEventRecord(box_done_ev, c.side->s2) != hipSuccess) return ORTK_EINVAL;
-            return 0;
-        }
-        return ortk_box_logbias_bwd(bt->boxes, wg, bg, cfg->box_trig ? dim_mat() : nullptr, ds, dwg, dbg, n, B, S, H, stream);
-    };
-    dx = w.ga; dx2 = w.gb;
-    TRY(ln_bwd(c, w.gy, w.enc[L - 1].xout, G, o.enc_na, o.enc_nb, w.st_mem, nullptr, dx, Me, gt_new(), eop(L - 1, 3)));
-    if (bch_enc) {
-        // cur = gradient of the FFN sublayer's input rows (xm) of the layer in hand; oth = the other fp32 buffer
-        float* cur = dx2; float* oth = dx;
-        void* dtA = gt_cur; void* dtB = gt_new(); void* ghb = gh_new();
-        {
-            const EncOff& e = o.enc[L - 1]; const EncBuf& b = w.enc[L - 1];
-            ortk_bchain_args ca; std::memset(&ca, 0, sizeof(ca)); ca.drop_rows = c.drop_rows;
-            ca.n_units = bs.units(bs.ex_top); ca.M = Me; ca.nin = 0; ca.dz0 = dtA;
-            x_part(ca, b.h, ghb, b.xm, b.st2, e.n1a, e.n1b, dx, cur, dtB, c.sub(eop(L - 1, 1)), w.gdo);
-            ca.drop_p = c.p_drop(); ca.eps = 1e-6f;
-            TRY(c.before_write(dtB)); TRY(c.before_write(ghb));
-            TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.ex_top), c.s));
-        }
-        for (int l = L - 1; l >= 0; --l) {
-            const EncOff& e = o.enc[l]; const EncBuf& b = w.enc[l];
-            const float* xin = l == 0 ? w.x0 : w.enc[l - 1].xout;
-            void* const gql = gq_of(l);
-            c.grp_on = grp_layers;
-            TRY(wgrad_gemm(c, dtA, A, d, b.h, A, ff, G + e.w2, G + e.b2, Me, d, ff));
-            TRY(wgrad_gemm(c, ghb, A, ff, b.y2, A, d, G + e.w1, G + e.b1, Me, ff, d));
-            TRY(wgrad_gemm(c, dtB, A, d, b.o, A, d, G + e.wo, G + e.bo, Me, d, d));
-            ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-            a.qkv_dtype = w.qdt_enc; a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, ame.k * d, w.qdt_enc);
-            a.v = (const float*)off_elems(b.qkv, ame.v * d, w.qdt_enc); a.ldq = a.ldk = a.ldv = 3 * d;
-            a.p = b.P; a.nkv = B; a.H = H; a.Lq = S; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(eop(l, 0));
-            a.d_o = (const float*)w.gdo; a.lddo = d; a.dqkv_dtype = A;
-            a.dq = gql; a.d_k = off_elems(gql, ame.gk * d, A); a.dv = off_elems(gql, ame.gv * d, A); a.lddq = a.lddk = a.lddv = 3 * d;
-            a.dscore = cfg->no_box ? nullptr : w.dscore + (int64_t)l * B * H * S * S;
-            TRY(c.before_write(gql));
-            TRY(ortk_attention_bwd(&a, stream));
-            if (l == 1 && box_split) TRY(box_grad(1, L - 1));
-            TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Me, 3 * d, d));
-            TRY(flush_wgrads(c, l == 0));
-            c.grp_on = false;
-            ortk_bchain_args ca; std::memset(&ca, 0, sizeof(ca)); ca.drop_rows = c.drop_rows;
-            ca.M = Me; ca.nin = 3; ca.ain = gql; ca.ld_ain = 3 * d;
-            ca.xa = xin; ca.sta = b.st1; ca.ga = params + e.n0a; ca.dresa = cur; ca.dxa = oth; ca.daa = G + e.n0a; ca.dba = G + e.n0b;
-            ca.drop_p = c.p_drop(); ca.eps = 1e-6f;
-            if (l > 0) {
-                const EncOff& en = o.enc[l - 1]; const EncBuf& bn = w.enc[l - 1];
-                dtA = gt_new(); void* dtBn = gt_new(); ghb = gh_new();
-                ca.n_units = bs.units(bs.ezx[l]);
-                ca.dza = dtA; ca.seed_a = c.sub(eop(l - 1, 3)); ca.mask_a = 1;
-                x_part(ca, bn.h, ghb, bn.xm, bn.st2, en.n1a, en.n1b, oth, cur, dtBn, c.sub(eop(l - 1, 1)), w.gdo);
-                TRY(c.before_write(dtA)); TRY(c.before_write(dtBn)); TRY(c.before_write(ghb));
-                TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.ezx[l]), c.s));
-                dtB = dtBn;
-            } else {
-                ca.n_units = bs.units(bs.ez0);
-                TRY(bchain_run(&ca, bs.stream_of(w.chain_pk_b, bs.ez0), c.s));
-                dx = oth; dx2 = cur;           // the gradient of the embedded regions (att_embed's output)
-            }
-        }
-    } else
-    for (int l = L - 1; l >= 0; --l) {
-        const EncOff& e = o.enc[l]; const EncBuf& b = w.enc[l];
-        const float* xin = l == 0 ? w.x0 : w.enc[l - 1].xout;
-        const void* dt; int dtt;
-        void* const ghl = gh_of(l); void* const gql = gq_of(l);
-        c.grp_on = grp_layers;
-        TRY(drop_bwd(c, dx, gt_cur, Me * d, eop(l, 3), &dt, &dtt, true));
-        TRY(wgrad_gemm(c, dt, dtt, d, b.h, A, ff, G + e.w2, G + e.b2, Me, d, ff));
-        TRY(dgrad_gemm(c, dt, dtt, d, e.w2, ghl, A, ff, Me, d, ff, b.h, A, ff, inv_keep));
-        TRY(wgrad_gemm(c, ghl, A, ff, b.y2, A, d, G + e.w1, G + e.b1, Me, ff, d));
-        TRY(dgrad_ln_bwd(c, ghl, A, ff, e.w1, Me, ff, d, w.gy, b.xm, G, e.n1a, e.n1b, b.st2, dx, dx2, gt_new(), eop(l, 1)));
-        TRY(drop_bwd(c, dx2, gt_cur, Me * d, eop(l, 1), &dt, &dtt, true));
-        TRY(wgrad_gemm(c, dt, dtt, d, b.o, A, d, G + e.wo, G + e.bo, Me, d, d));
-        // (layer 0 with the tail group: the three gradients whose operands exist go now; wqkv's and att_embed's, which the step ends with, form a small last group)
-        if (l == 0 && tail_group) TRY(flush_wgrads(c));
-        void* dOe = w.qdt_enc ? w.gdo : (void*)w.gy;
-        TRY(dgrad_gemm(c, dt, dtt, d, e.wo, dOe, w.qdt_enc, d, Me, d, d));
-        ortk_attn_args a; std::memset(&a, 0, sizeof(a)); a.precision = c.prec;
-        a.qkv_dtype = w.qdt_enc; a.q = (const float*)b.qkv; a.k = (const float*)off_elems(b.qkv, ame.k * d, w.qdt_enc);
-        a.v = (const float*)off_elems(b.qkv, ame.v * d, w.qdt_enc); a.ldq = a.ldk = a.ldv = 3 * d;
-        a.p = b.P; a.nkv = B; a.H = H; a.Lq = S; a.Lk = S; a.dk = dk; a.drop_p = c.p_drop(); a.drop_seed = c.sub(eop(l, 0));
-        a.d_o = (const float*)dOe; a.lddo = d; a.dqkv_dtype = A;
-        a.dq = gql; a.d_k = off_elems(gql, ame.gk * d, A); a.dv = off_elems(gql, ame.gv * d, A); a.lddq = a.lddk = a.lddv = 3 * d;
-        a.dscore = cfg->no_box ? nullptr : w.dscore + (int64_t)l * B * H * S * S;
-        TRY(c.before_write(gql));
-        TRY(ortk_attention_bwd(&a, stream));
-        if (l == 1 && box_split) TRY(box_grad(1, L - 1));     // layers 1 .. L-1: beside the last two encoder layers
-        if (l == 0 && tail_group && !cfg->no_box) TRY(box_grad(0, box_split ? 1 : L));      // (third queue: done before the step's last launch needs the units)
-        TRY(fold(ame, Me, gql));
-        TRY(wgrad_gemm(c, gql, A, 3 * d, b.y1, A, d, G + e.wqkv, G + e.bqkv, Me, ame.n * d, d));
-        if (l > 0 || !tail_group) TRY(flush_wgrads(c, l == 0));        // the layer's four weight gradients: one launch (layer 0: below)
-        c.grp_on = false;
-        TRY(dgrad_ln_bwd(c, gql, A, 3 * d, e.wqkv, Me, ame.n * d, d, w.gy, xin, G, e.n0a, e.n0b, b.st1, dx2, dx, gt_new(), l > 0 ? (int)eop(l - 1, 3) : -1));
-    }
-    // The tail.  With the grouped weight gradients and the bf16 feature copy: layer 0's last weight gradient was held back, att_embed's
-    // joins the one that is still held back (wqkv's), and the two go as ONE launch on the side stream; the geometry-bias gradient of layer 0 went
-    // to the third queue right behind layer 0's attention backward (its workgroups hold the LDS of every unit: beside the last launch they delayed it by their 63 us).  (Before: an urgent 4-gradient launch beside the last LayerNorm backward, which
-    // took 116 instead of 24 us for it, then a 120-us att_embed launch of its own on the caller's stream.)
-    if (!cfg->no_box && !tail_group) TRY(box_grad(0, box_split ? 1 : L));
-    // att_embed: x0 = dropout(relu(.) * mask)  ->  d(pre-activation) = dx * [x0 > 0] / (1 - p_src)
-    TRY(c.before_write(gt_new()));
-    TRY(ortk_gate_apply(dx, w.x0, gt_cur, A, Me * d, c.p_src() > 0.f ? 1.f / (1.f - c.p_src()) : 1.f, stream));
-    if (tail_group) {
-        c.grp_on = true;
-        TRY(wgrad_gemm(c, gt_cur, A, d, w.feats16, ORTK_BF16, cfg->feat, G + o.att_w, G + o.att_b, Me, d, cfg->feat));
-        TRY(flush_wgrads(c, true));
-        c.grp_on = false;
-    } else {   // the last weight gradient stays on the caller's stream: the side stream is busy with the geometry-bias gradient
-        const bool us = c.use_side;
-        c.use_side = false;
-        TRY(wgrad_gemm(c, gt_cur, A, d, bt->att_feats, ORTK_F32, cfg->feat, G + o.att_w, G + o.att_b, Me, d, cfg->feat));
-        c.use_side = us;
-    }
-    TRY(c.wait_ev(box_done_ev));
-    return c.join();       // every gradient is final in the caller's stream order
+    return backward_encoder_half(s);
 }
 
 static int encode_impl(const ortk_config*, const float*, const float*, const float*, const float*, int32_t, int32_t, void*,
@@ -1708,7 +1527,7 @@ struct DecodeWS {
     int64_t ldv; int adt;
     void* w16;
     float *x0, *logbias; void* mem /*A*/; float* st; void* ckv /*ckvdt*/;
-    EncPtrs enc;                       // one set of encoder buffers, reused by every layer
+    EncBuf enc;                        // one set of encoder buffers, reused by every layer
     float *xa, *xb; void* y /*A*/; float* qkv; void* o /*A*/; void* q /*ckvdt when xq16*/; void* h /*A*/; float* logits;
     float* gstats = nullptr;           // soft-max partials of the logit rows (rows, ldv / 64, 2): mixed precision
     float* gsamp = nullptr;            // Gumbel-max candidates of the logit rows (rows, ldv / 64, 4): sampling decodes, mixed precision
@@ -1831,7 +1650,7 @@ static int encode_impl(const ortk_config* cfg, const float* params, const float*
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
     TRY(make_w16(cfg, o, params, w.w16, stream));
     Ctx c{cfg, ortk_s(stream), cfg->precision, 0, false, params, w.w16, w.adt};
-    EncPtrs ep[MAXLAYERS];
+    EncBuf ep[MAXLAYERS];
     for (int l = 0; l < cfg->n_layers; ++l) ep[l] = w.enc;
     return encoder_forward(c, o, att_feats, boxes, att_masks, B, S, w.x0, w.logbias, ep, memory_out, ORTK_F32, w.st);      // (fp32 memory out: no chains)
 }
@@ -2168,7 +1987,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const int64_t Me = (int64_t)B * S;
     // No activations are kept: every encoder layer reuses one buffer set, and the residual stream is updated in
     // place (x is dead once xm = x + attn(...) exists, so the FFN sublayer writes its output back over x).
-    EncPtrs ep[MAXLAYERS];
+    EncBuf ep[MAXLAYERS];
     for (int l = 0; l < L; ++l) ep[l] = w.enc;
     // the side stream carries the geometry bias of the encoder (0.4 ms at 1 024 images, VALU-bound) beside att_embed and the
     // first projection; nothing else of a decode runs there

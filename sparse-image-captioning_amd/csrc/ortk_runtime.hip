@@ -39,10 +39,10 @@ extern "C" void ortk_get_tuning(ortk_tuning* out) { if (out) *out = ortk::g_tuni
 extern "C" int ortk_set_tuning(const ortk_tuning* t) {
     if (!t) return ORTK_EINVAL;
     auto in = [](int32_t v, int32_t lo, int32_t hi) { return v >= lo && v <= hi; };
-    // (gemm_t64, side_stream, row_chain, chain_wide and spmm_alias are read as thresholds / flags: any value is served)
-    if (!in(t->attn_impl, 0, 4) || t->attn16_min_lq < 1 || !in(t->f32_split, 0, 7) || t->wgrad_wgs < 1 ||
+    // (gemm_t64, side_stream, chain_wide and spmm_alias are read as thresholds / flags: any value is served)
+    if (!in(t->row_chain, 0, 1) /* 2, 3: the executor's backward chains, removed */ || !in(t->attn_impl, 0, 4) || t->attn16_min_lq < 1 || !in(t->f32_split, 0, 7) || t->wgrad_wgs < 1 ||
         !in(t->wgrad_group, 0, 15) || !in(t->wgrad_group_splitk, 0, 8) || t->wgrad_group_wgs < 1 || !in(t->wgrad_group_tail, 0, 1) ||
-        !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 15) || (t->ln_fuse & 2) /* bit 1: the 128-row backward panels, removed */ ||
+        !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 15) || (t->ln_fuse & 3) /* bit 0: the executor's fused data gradient + LayerNorm backward, bit 1: the 128-row backward panels, removed */ ||
         !in(t->samp_epilogue, 0, 1) || !in(t->gemm_epilogue, 0, 3) ||
         !(in(t->attn16_short, 0, 1) || t->attn16_short == 4 || t->attn16_short == 8) || !in(t->attn16_block, 0, 1)) return ORTK_EINVAL;
     ortk::g_tuning = *t;

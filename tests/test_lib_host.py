@@ -204,6 +204,30 @@ def test_product_never_imports_the_oracle():
                     "oracle/ort_oracle.py", ""), os.path.join(dirpath, f)
 
 
+def test_set_tuning_refuses_the_removed_backward_forms():
+    """ortk_tuning.row_chain is 0 or 1 and ortk_tuning.ln_fuse carries bits 2 and 3 only: the executor's backward chains
+    (row_chain 2, 3) and its LayerNorm backward in the data gradient's epilogue (ln_fuse bit 0) are gone, like the 128-row
+    panels of ln_fuse bit 1 before them.  A refused call changes nothing."""
+    import sparse_image_captioning_amd as P
+    L = P._lib
+    prev = L.set_tuning()
+    try:
+        for rc in (0, 1):
+            L.set_tuning(row_chain=rc)
+            assert L.set_tuning()["row_chain"] == rc
+        for lf in (0, 4, 8, 12):
+            L.set_tuning(ln_fuse=lf)
+            assert L.set_tuning()["ln_fuse"] == lf
+        L.set_tuning(row_chain=1, ln_fuse=4)
+        for bad in (dict(row_chain=2), dict(row_chain=3), dict(row_chain=-1), dict(ln_fuse=1), dict(ln_fuse=2), dict(ln_fuse=9)):
+            with pytest.raises(L.OrtkError):
+                L.set_tuning(**bad)
+            now = L.set_tuning()
+            assert (now["row_chain"], now["ln_fuse"]) == (1, 4), (bad, now)
+    finally:
+        L.set_tuning(**prev)
+
+
 def test_dim_mat_constants_match_torch():
     """The 8 wavelengths 1/1000^(k/8) used by the box kernel (computed with powf on the host) equal torch's fp32
     evaluation (relation_transformer.py:241-243) bit for bit."""
