@@ -162,6 +162,7 @@ class RelationTransformerModel(CaptionModelBase):
         self._ws_cache = {}
         self._vr_stage = {}                # pinned staging rings of the valid-position tables, per (caption rows, positions)
         self._seed_counter = 0
+        self._seed_base = None             # None: torch.initial_seed(); a loaded trainer sets the base its run started with
         self.done_beams = None
 
     # ------------------------------------------------------------------ arena plumbing
@@ -365,7 +366,8 @@ class RelationTransformerModel(CaptionModelBase):
 
     def _next_seed(self):
         self._seed_counter += 1
-        return (torch.initial_seed() * 1000003 + self._seed_counter) & 0xFFFFFFFFFFFFFFFF or 1
+        base = torch.initial_seed() if self._seed_base is None else self._seed_base
+        return (base * 1000003 + self._seed_counter) & 0xFFFFFFFFFFFFFFFF or 1
 
     def _workspace(self, key, nbytes, cache):
         # ONE cached buffer per kind of call ("train", "decode" + chunk of a multi-stream decode, "step"), grown to the largest

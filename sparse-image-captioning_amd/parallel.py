@@ -26,6 +26,12 @@ def rank():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
+def barrier():
+    """Every rank waits here (a checkpoint: rank 0 writes, the others must not run ahead and read half a file)."""
+    if _active():
+        dist.barrier()
+
+
 def sample_row_offset(images_per_rank, rows_per_image, r=None):
     """First GLOBAL decode row of rank r's shard (``ortk_decode_opts.sample_row_offset``): the multinomial draws of an SCST rollout
     are keyed by (seed, position, global row), so N ranks on their image shards sample exactly what one process samples on the

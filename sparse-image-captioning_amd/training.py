@@ -14,12 +14,14 @@ The update rule is Adam at the Noam rate by default; ``lr_scheduler`` / ``optim`
 """
 import ctypes as C
 import math
+import os
 import warnings
 
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from . import optim_state as S
 from . import parallel
 from .pruning import prune
 
@@ -134,7 +136,8 @@ class NativeTrainer:
         ns = self.spec.n_states
         self.m = torch.zeros(n, device=self.dev) if ns >= 1 else None
         self.v = torch.zeros(n, device=self.dev) if ns >= 2 else None
-        self.step_count = 0
+        self.step_count = 0                # feeds the rate, the sparsity-loss ramp and the sparse-plan overflow check
+        self.optim_step = 0                # feeds the update rule: Adam's bias corrections, first_step (equal unless a load sets them apart)
         self.loss_dev = torch.zeros(1, device=self.dev)
         self.norm_dev = torch.zeros(1, device=self.dev)
         self._sum_scratch = None
@@ -281,7 +284,7 @@ class NativeTrainer:
         parallel.allreduce_arena(self.grads, self.dm if (self.masked and self.train_masks) else None, dtype=self.allreduce_dtype)
 
     def _adam(self, p, g, m, v, lr, eps, zero=False):
-        t = self.step_count
+        t = self.optim_step
         b1, b2 = self.betas
         fn = L.lib().ortk_adam_clip_zero if zero else L.lib().ortk_adam_clip
         L.check(fn(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), lr, b1, b2, eps, self.clip,
@@ -293,7 +296,7 @@ class NativeTrainer:
         spec = self.spec
         if spec.kind == "adam" and weight_decay == 0.0:
             return self._adam(p, g, s1, s2, lr, eps, zero)
-        t = self.step_count
+        t = self.optim_step
         k = L.OptimArgs()
         k.p, k.g, k.n = p.data_ptr(), g.data_ptr(), p.numel()
         k.s1 = s1.data_ptr() if spec.n_states >= 1 else None
@@ -312,6 +315,163 @@ class NativeTrainer:
         _decay_start, _decay_every, _decay_rate), optim_alpha / _beta / _epsilon, weight_decay, max_train_step, noamopt_factor /
         _warmup; names the config does not carry keep their defaults.  `kw` overrides and adds the trainer's own arguments."""
         return cls(model, **dict(OptimSpec.options_from_config(config), **kw))
+
+    # ------------------------------------------------------------------ save and resume (formats and refusals: optim_state.py)
+    def _quiesce(self):
+        """Nothing of a step is in flight on another stream: the decoder-half update, a pending all-reduce."""
+        if self._pending is not None:
+            self._pending.wait()
+            self._pending = None
+        if self._opt_stream is not None:
+            torch.cuda.current_stream().wait_stream(self._opt_stream)
+
+    def _trains_masks(self):
+        return bool(self.masked and self.train_masks)
+
+    def _state_names(self):
+        """(entries by name, names with weight-optimiser state, names with mask-optimiser state | None), arena order."""
+        entries = {e["name"]: e for e in self.model.named_weight_entries()}
+        masks = [n + S.MASK_SUFFIX for n, e in entries.items() if e["kind"] == 1] if self._trains_masks() else None
+        return entries, list(entries), masks
+
+    def _shapes(self, entries):
+        shapes = {n: e["shape"] for n, e in entries.items()}
+        shapes.update({n + S.MASK_SUFFIX: e["shape"] for n, e in entries.items() if e["kind"] == 1})
+        return shapes
+
+    def optimizer_group_names(self):
+        """Parameter names per param group of the reference's optimiser for this model, in its parameter order."""
+        return S.group_names(self.model.named_weight_entries(), self._trains_masks(), self.model.mask_freeze_scope if self.masked else None)
+
+    def _gather(self, arenas, names, entries):
+        """{torch's array name: {parameter name: CPU fp32 tensor shaped like the parameter}} from the flat state arenas."""
+        out = {}
+        for array, arena in zip(S.STATE_ARRAYS[self.spec.kind], arenas):
+            host = arena.detach().cpu()
+            out[array] = {}
+            for n in names:
+                e = entries[n[:-len(S.MASK_SUFFIX)] if n.endswith(S.MASK_SUFFIX) else n]
+                out[array][n] = host[e["offset"]:e["offset"] + e["numel"]].view(e["shape"]).clone()
+        return out
+
+    def _scatter(self, arenas, maps, entries):
+        """Inverse of `_gather`: one host image per arena (zero where the map has no parameter), one copy to the device."""
+        for array, arena in zip(S.STATE_ARRAYS[self.spec.kind], arenas):
+            host = torch.zeros(arena.numel())
+            for n, t in maps[array].items():
+                e = entries[n[:-len(S.MASK_SUFFIX)] if n.endswith(S.MASK_SUFFIX) else n]
+                host[e["offset"]:e["offset"] + e["numel"]] = t.reshape(-1)
+            arena.copy_(host)
+
+    def _options(self):
+        o = dict(grad_clip=self.clip, label_smoothing=self.label_smoothing, max_train_step=self.max_train_step)
+        if self.masked:
+            o.update(sparsity_target=self.sparsity_target, sparsity_weight=self.sparsity_weight, prune_supermask_lr=self.mask_lr,
+                     mask_eps=self.mask_eps)
+        return o
+
+    def _after_load(self):
+        self.grads.zero_()
+        self._grads_clean = True
+        if self._trains_masks():
+            self.dm.zero_()
+
+    def state_dict(self):
+        """Everything a continued run needs beside the model's weights (``model.state_dict()``): the optimiser arrays by parameter
+        name, both step counts, the epoch and the seed base and counter that key every dropout site, mask sample and rollout.  A plain
+        dict of ints, floats, strings and CPU fp32 tensors; loads with ``torch.load(..., weights_only=True)``."""
+        self._quiesce()
+        entries, names, masks = self._state_names()
+        m = self.model
+        sd = dict(format=S.FORMAT, spec=S.spec_fields(self.spec), rate_step=self.step_count, optim_step=self.optim_step, epoch=self.epoch,
+                  seed=dict(base=torch.initial_seed() if m._seed_base is None else m._seed_base, counter=m._seed_counter),
+                  options=self._options(), state=self._gather((self.m, self.v), names, entries))
+        if masks is not None:
+            sd["mask_state"] = self._gather((self.mm, self.mv), masks, entries)
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue exactly where ``state_dict()`` was taken.  ValueError (naming the field and both values, before anything is written)
+        on another format, kind or scheduler, a differing optimiser constant, a missing or unexpected parameter name, a shape
+        mismatch, a masked / dense mismatch; ONE warning lists the other options that differ (schedule constants, clip, ...)."""
+        entries, names, masks = self._state_names()
+        diff = S.check_native_state(sd, self.spec, names, self._shapes(entries), masks, self._options())
+        S.warn_differences(diff)
+        self._quiesce()
+        self._scatter((self.m, self.v), sd["state"], entries)
+        if masks is not None:
+            self._scatter((self.mm, self.mv), sd["mask_state"], entries)
+        self.step_count, self.optim_step, self.epoch = int(sd["rate_step"]), int(sd["optim_step"]), sd["epoch"]
+        self.model._seed_base, self.model._seed_counter = int(sd["seed"]["base"]), int(sd["seed"]["counter"])
+        self._after_load()
+
+    def optimizer_state_dict(self):
+        """What ``state_dict()`` of the reference's optimiser holds for this model (``optimizer_last.pth``): the inner ``torch.optim``
+        state — per-parameter entries in the reference's parameter order, one param group, or two for a supermask model — as the
+        installed torch writes it.  The wrapper's own step count is not part of it (``RateOpt.__getattr__``)."""
+        self._quiesce()
+        entries, names, masks = self._state_names()
+        groups = self.optimizer_group_names()
+        state = self._gather((self.m, self.v), groups[0], entries)
+        mask_state = self._gather((self.mm, self.mv), groups[1], entries) if masks is not None else None
+        return S.pack_optimizer_state(self.spec, groups, self._shapes(entries), state, mask_state, self.optim_step,
+                                      lr=self.rate() if self.step_count > 0 else None,
+                                      mask_lr=self.mask_lr if self.masked else 0.0, mask_eps=self.mask_eps if self.masked else 0.0)
+
+    def load_optimizer_state_dict(self, d, rate_step=None):
+        """Load a reference-format optimiser state, e.g. the contents of a reference run's ``optimizer_last.pth``.  ``optim_step`` is
+        the entries' ``step``; sgdm / sgdmom store none, there a loaded ``momentum_buffer`` means "not the first step".
+
+        ``rate_step=None`` continues the rate schedule (and the sparsity-loss ramp) at the loaded ``step``: the uninterrupted run.  It
+        is a ValueError where the kind stores no step (sgd, sgdm, sgdmom): pass a value.
+        ``rate_step=0`` is what the reference's ``--resume_training`` does: it restores only the inner optimiser, its new wrapper
+        counts from 0 and ``prepare()`` sets ``global_step = 0``, so the schedule and the sparsity-loss ramp restart.
+
+        ValueError on param groups with ``amsgrad``, ``centered``, ``maximize``, ``lr_decay`` or ``initial_accumulator_value`` other
+        than the defaults the reference uses, on constants that differ from this trainer's and on a group layout, a parameter count
+        or a shape that does not fit the model."""
+        entries, names, masks = self._state_names()
+        groups = self.optimizer_group_names()
+        state, mask_state, step = S.unpack_optimizer_state(self.spec, d, groups, self._shapes(entries),
+                                                           mask_lr=self.mask_lr if self.masked else 0.0,
+                                                           mask_eps=self.mask_eps if self.masked else 0.0)
+        optim_step, rate_step = S.resolve_steps(self.spec, step, rate_step)
+        self._quiesce()
+        self._scatter((self.m, self.v), state, entries)
+        if masks is not None:
+            self._scatter((self.mm, self.mv), mask_state, entries)       # (frozen masks are in no group: their arrays stay zero)
+        self.optim_step, self.step_count = optim_step, rate_step
+        self._after_load()
+
+    def save_checkpoint(self, log_dir, tag="last"):
+        """``model_{tag}.pth`` and ``optimizer_{tag}.pth`` — the reference's names and formats (utils/training.py:82-83,
+        scripts/train_n_prune_transformer.py:211-214), so the reference can load them — and ``trainer_{tag}.pth``, the native state.
+        Every file is complete under a temporary name before any is renamed.  Under torch.distributed rank 0 writes."""
+        model_path, optim_path, trainer_path = S.checkpoint_paths(log_dir, tag)
+
+        def files():
+            os.makedirs(log_dir, exist_ok=True)
+            return {model_path: {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
+                    optim_path: self.optimizer_state_dict(), trainer_path: self.state_dict()}
+        S.write_files(files)
+
+    def load_checkpoint(self, log_dir, tag="last", rate_step=None):
+        """With ``trainer_{tag}.pth`` present: the model and the native state, an exact continuation (`rate_step` does not apply).
+        Without it the directory is a reference checkpoint: the model, then ``load_optimizer_state_dict(..., rate_step)``.  Every
+        rank reads the files itself."""
+        model_path, optim_path, trainer_path = S.checkpoint_paths(log_dir, tag)
+        native = os.path.isfile(trainer_path)
+        other, weights = S.read_file(trainer_path if native else optim_path), S.read_file(model_path)
+        own = set(self.model.state_dict())
+        missing = sorted(k for k in own - set(weights) if not k.endswith(".pe"))          # (a buffer the constructor rebuilds)
+        unexpected = sorted(set(weights) - own)
+        if missing or unexpected:
+            raise ValueError(f"{model_path}: missing keys {missing[:4]}, unexpected keys {unexpected[:4]}")
+        if native:                       # (either refuses before it writes: a refused checkpoint leaves model and trainer as they were)
+            self.load_state_dict(other)
+        else:
+            self.load_optimizer_state_dict(other, rate_step=rate_step)
+        self.model.load_state_dict(weights, strict=False)
 
     # ------------------------------------------------------------------ steps
     def xe_step(self, data, train=True):
@@ -462,7 +622,7 @@ class NativeTrainer:
         if coef is not None:
             k.extra_coef = coef.data_ptr()
         k.n, k.index0, k.mode, k.seed = b - a, a, (1 if draws is not None else m._mode(train)), m._mask_seed(seed)
-        t, (b1, b2) = self.step_count, self.betas
+        t, (b1, b2) = self.optim_step, self.betas
         k.lr_w, k.eps_w = lr, self.eps
         k.lr_m, k.eps_m = (self.mask_lr, self.mask_eps) if self.train_masks else (0.0, 1.0)
         k.beta1, k.beta2, k.clip, k.bc1, k.bc2 = b1, b2, self.clip, 1.0 - b1 ** t, 1.0 - b2 ** t
@@ -507,6 +667,7 @@ class NativeTrainer:
     def _step(self, data, tok_weight, norm_mask, train, seed=None, encoded=False, rollouts=False, smoothing=0.0):
         m = self.model
         self.step_count += 1
+        self.optim_step += 1
         if not self._grads_clean:
             self.grads.zero_()
         self._grads_clean = False
