@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 16   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 17   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -366,8 +366,10 @@ typedef struct ortk_tuning {
                                 1 the encoder / decoder layers | 2 the generator | 4 the memory's K|V projection | 8 the row ranges of a tile meet in
                                 memory (workspace) instead of adding with atomics.  0 = one launch per projection (ortk_gemm).  Mixed precision only */
     int32_t wgrad_group_splitk;   /* row ranges of every grouped launch of the executor: 0 automatic (the two fields below) | 1..8 */
-    int32_t wgrad_group_wgs;      /* workgroups a grouped launch of the executor is given (row ranges = this / its 256 x 256 tiles, rounded; 80: the
-                                     launch shares the chip with the caller's stream instead of filling it, scratch/wgrad_group_ab.py) */
+    int32_t wgrad_group_wgs;      /* workgroups a grouped launch of the executor is given (row ranges = this / its 256 x 256 tiles, rounded; 96: the
+                                     launch shares the chip with the caller's stream instead of filling it, scratch/wgrad_group_ab.py — a decoder layer's
+                                     56 tiles as two row ranges, which pays since the LayerNorm backwards issue no atomics: 80, one range, left the
+                                     decoder half of the backward waiting for the side stream, profiles/ln_bwd_partials.txt) */
     int32_t wgrad_group_tail;     /* 1 (default): the last group before the caller's stream waits for the side stream gets a full round of workgroups | 0 */
     int32_t feats_bf16;           /* 1 (default, mixed precision with the side stream): a bf16 copy of the region features per step (att_embed and its weight
                                      gradient on the bf16-operand kernels; the weight gradient in the backward's last grouped launch) and the chain weights
@@ -379,7 +381,9 @@ typedef struct ortk_tuning {
                                      | bit 1: unused, refused (it selected the 128-row backward panels of round 3, removed) | bit 2: the LayerNorm backward of width 512 with four
                                      instead of eight consecutive columns per lane (measurement) | bit 3: the executor keeps the LayerNorm output gradients
                                      (data gradient -> ortk_layernorm_bwd_dt) in fp32 in mixed precision too; default: bf16 there, as every other gradient
-                                     that is a GEMM operand in that mode */
+                                     that is a GEMM operand in that mode | bit 4: the executor's LayerNorm backwards add da / db with atomics from
+                                     every workgroup (ortk_layernorm_bwd_dt) instead of leaving block partials that one launch per half of
+                                     the backward sums (ortk_layernorm_bwd_part + ortk_ln_partials_reduce; measurement) */
     int32_t samp_epilogue;        /* 1 (default): sampling decodes in mixed precision take their tokens from the generator GEMM's epilogue (Gumbel-max candidates
                                      + soft-max partials per 64 logits, ortk_gemm_args.tile_samp) and never store the logit rows | 0: logits + sample step */
     int32_t gemm_epilogue;        /* 0 (default): the forward-layout LDS-DMA GEMM kernels run the lean epilogue (options the launcher has verified compiled
@@ -689,6 +693,24 @@ int ortk_layernorm_bwd_drop_rows(const float* dy, const float* x, const float* a
 int ortk_layernorm_bwd_dt(const void* dy, int32_t dy_dtype, const float* x, const float* a, const float* stats, const float* dres,
                           float* dx, float* da, float* db, int64_t rows, int32_t d, float eps, void* dz, int32_t dz_dtype,
                           float drop_p, uint32_t drop_seed, const int32_t* drop_rows, ortk_stream stream);
+/* The partials form of the same backward at d = 512: dx and dz as ortk_layernorm_bwd_dt writes them, bit for bit, but da / db are not
+ * touched and no atomic is issued.  Workgroup k of the launch stores its column sums to part[k][2][512] (da's first, db's behind);
+ * *nblocks_out = ortk_ln_part_blocks(rows) blocks are written, `part` must hold part_blocks >= that many (4 KB each, 16-byte aligned)
+ * and nothing behind them is touched.  ortk_ln_partials_reduce adds them into da / db.  ORTK_EINVAL: d != 512, an operand that is
+ * not 16-byte aligned, part or nblocks_out NULL, part_blocks too small. */
+int ortk_layernorm_bwd_part(const void* dy, int32_t dy_dtype, const float* x, const float* a, const float* stats, const float* dres,
+                            float* dx, float* part, int64_t part_blocks, int32_t* nblocks_out, int64_t rows, int32_t d, float eps,
+                            void* dz, int32_t dz_dtype, float drop_p, uint32_t drop_seed, const int32_t* drop_rows, ortk_stream stream);
+/* blocks of partials a launch over `rows` rows writes (at most 1 024: a workgroup walks ortk_ln_part_rows() consecutive rows, more
+ * where the cap asks for it) */
+int32_t ortk_ln_part_blocks(int64_t rows);
+int32_t ortk_ln_part_rows(void);
+/* da[c] += sum_k part[k][0][c], db[c] += sum_k part[k][1][c] over k < nblocks, for every slot, in ONE launch (64 slots per launch).
+ * The blocks are added in an order fixed by nblocks alone, then ONE atomic add per column and slot: slots may share a destination
+ * (shared layers), and with distinct destinations the result is the same bits from run to run.  Entries of `part` behind nblocks
+ * are not read. */
+typedef struct { const float* part; int32_t nblocks; float* da; float* db; } ortk_ln_slot;
+int ortk_ln_partials_reduce(const ortk_ln_slot* slots, int32_t n, ortk_stream stream);
 
 /* Geometry bias of BoxMultiHeadedAttention (relation_transformer.py:196-256,177-183,286):
  * out[l,b,h,i,j] = log(max(relu(WG[l,h].e_ij + bG[l,h]), 1e-6)).  wg[l]/bg[l] are per-layer device pointers

@@ -116,6 +116,10 @@ class Tuning(C.Structure):
                 ("wgrad_group", C.c_int32), ("wgrad_group_splitk", C.c_int32), ("wgrad_group_wgs", C.c_int32), ("wgrad_group_tail", C.c_int32), ("feats_bf16", C.c_int32), ("ln_fuse", C.c_int32), ("samp_epilogue", C.c_int32), ("gemm_epilogue", C.c_int32), ("attn16_short", C.c_int32), ("attn16_block", C.c_int32)]
 
 
+class LnSlot(C.Structure):       # include/ortk.h: ortk_ln_slot
+    _fields_ = [("part", C.c_void_p), ("nblocks", C.c_int32), ("da", C.c_void_p), ("db", C.c_void_p)]
+
+
 MAX_BEAM = 32      # include/ortk.h: ORTK_MAX_BEAM
 DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_SPLIT_SMALL, DEC_SPARSE_GATHER, DEC_STACK_FP8 = 1, 2, 4, 8, 16, 32, 64, 128      # ortk_decode_opts.exec_flags
 
@@ -221,6 +225,10 @@ SIGNATURES = {
     "ortk_layernorm_bwd_drop": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F, _P, _I32, _F, C.c_uint32, _P]),
     "ortk_layernorm_bwd_drop_rows": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F, _P, _I32, _F, C.c_uint32, _P, _P]),
     "ortk_layernorm_bwd_dt": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _F, _P, _I32, _F, C.c_uint32, _P, _P]),
+    "ortk_layernorm_bwd_part": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _P, _I64, C.POINTER(_I32), _I64, _I32, _F, _P, _I32, _F, C.c_uint32, _P, _P]),
+    "ortk_ln_part_blocks": (_I32, [_I64]),
+    "ortk_ln_part_rows": (_I32, []),
+    "ortk_ln_partials_reduce": (_I32, [C.POINTER(LnSlot), _I32, _P]),
     "ortk_box_logbias_fwd": (_I32, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_F), _P, _I32, _I32, _I32, _I32, _P]),
     "ortk_box_logbias_bwd": (_I32, [_P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_F), _P, C.POINTER(_P), C.POINTER(_P),
                                    _I32, _I32, _I32, _I32, _P]),
@@ -272,7 +280,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 16   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 17   # include/ortk.h: ORTK_VERSION
 
 
 def lib():

@@ -27,6 +27,24 @@ void prof_end(const ProfMark& m, hipStream_t s);
 // nullptr (and *index = -1) when profiling is off or the slots are used up.
 unsigned long long* prof_slot(int* index);
 
+// The partials form of the width-512 LayerNorm backward (ortk_layernorm_bwd_part): a workgroup walks LN_PART_ROWS consecutive rows, or
+// as many as keep a launch at LN_PART_MAX_BLOCKS workgroups (its partials then never exceed 4 MB), and leaves one [2][512] block of
+// column sums.  ONE pair of functions for the launcher, the workspace's sizing and the executor.
+#ifndef ORTK_LN_PART_ROWS
+#define ORTK_LN_PART_ROWS 16
+#endif
+#ifndef ORTK_LN_PART_MAX_BLOCKS
+#define ORTK_LN_PART_MAX_BLOCKS 512
+#endif
+constexpr int LN_PART_ROWS = ORTK_LN_PART_ROWS, LN_PART_MAX_BLOCKS = ORTK_LN_PART_MAX_BLOCKS;
+static inline int ln_part_rows_per_block(int64_t rows) {
+    const int64_t need = (rows + LN_PART_MAX_BLOCKS - 1) / LN_PART_MAX_BLOCKS;
+    return (int)(need > LN_PART_ROWS ? need : LN_PART_ROWS);
+}
+static inline int ln_part_blocks(int64_t rows) { const int64_t r = ln_part_rows_per_block(rows); return (int)((rows + r - 1) / r); }
+// the most blocks any launch over at most `rows` rows writes (ln_part_blocks is not monotonic where the cap sets in): sizes a slot
+static inline int ln_part_blocks_max(int64_t rows) { const int64_t b = (rows + LN_PART_ROWS - 1) / LN_PART_ROWS; return (int)(b < LN_PART_MAX_BLOCKS ? b : LN_PART_MAX_BLOCKS); }
+
 // copy the new token's K and V (columns d..3d of the packed QKV row) into the self-attention cache
 int kv_append(const float* qkv, void* cache_k, void* cache_v, int32_t kv_dtype, int64_t rows, int32_t d, int32_t row_mult, int32_t tmax,
               int32_t t, hipStream_t s);

@@ -299,6 +299,9 @@ struct TrainWS {
     void *gqkv2 = nullptr, *gh2 = nullptr;  // layers alternate between gqkv / gqkv2 and gh / gh2
     void* wg_ws = nullptr; size_t wg_ws_bytes = 0;      // partial tiles + tickets of one grouped launch (launches are ordered by their stream)
     void* feats16 = nullptr;                // bf16 copy of the region features (mixed precision): operand of att_embed and of its weight gradient
+    // block partials of the LayerNorm backwards (d_model = 512; ortk_layernorm_bwd_part): one slot of ln_cap_* blocks ([2][512] floats) per
+    // LayerNorm, 3 L + 1 for the decoder half and 2 L + 1 for the encoder half, summed into the gradient arena by one launch per half
+    float *ln_part_dec = nullptr, *ln_part_enc = nullptr; int64_t ln_cap_dec = 0, ln_cap_enc = 0;
     size_t bytes;
 };
 
@@ -367,6 +370,11 @@ static void carve_train(const ortk_config& c, int B, int S, int R, int T, void* 
         w.wg_ws = b.take_bytes(w.wg_ws_bytes);
         w.feats16 = b.take_bytes((size_t)Me * c.feat * 2);
     }
+    if (d == 512) {     // (4 KB per block: 32 slots x 512 blocks = 64 MB at the bench geometry, both row counts above 8 192)
+        w.ln_cap_dec = ln_part_blocks_max(Md); w.ln_cap_enc = ln_part_blocks_max(Me);
+        w.ln_part_dec = b.take<float>((3 * L + 1) * w.ln_cap_dec * 1024);
+        w.ln_part_enc = b.take<float>((2 * L + 1) * w.ln_cap_enc * 1024);
+    }
     w.bytes = (b.off + 255) & ~(size_t)255;
 }
 
@@ -414,6 +422,14 @@ static SideStream* side_for(hipStream_t caller) {
     return ss->ok ? ss : nullptr;
 }
 
+// The LayerNorm backwards of one half of a backward leave their da / db as block partials (ln_bwd takes the next slot), and the half
+// ends by ONE launch that adds every slot into the gradient arena (ln_parts_reduce) — no atomics from the LayerNorm kernels themselves,
+// which sit on the step's dependency chain (ortk_tuning.ln_fuse & 16: the atomics form).
+struct LnParts {
+    float* base = nullptr; int64_t cap = 0 /* blocks per slot */, rows_max = 0; int max = 0 /* slots */, n = 0;
+    ortk_ln_slot slot[3 * MAXLAYERS + 1];
+};
+
 struct Ctx {
     const ortk_config* cfg; hipStream_t s; int prec; uint64_t seed; bool train;
     const float* P;          // fp32 parameter arena (biases, LayerNorm, embeddings, and weights in fp32 mode)
@@ -439,6 +455,7 @@ struct Ctx {
     bool grp_on = false;
     void* wg_ws = nullptr; size_t wg_ws_bytes = 0;
     mutable hipEvent_t last_done = nullptr;
+    LnParts* lnp = nullptr;                      // the slots of the backward half under way (nullptr: LayerNorm backwards with atomics)
     uint64_t next_seq() const { return ++side_seq; }     // one per launch (or group of launches behind one event) queued on the side stream
     void reads(const void* buf, hipEvent_t done, uint64_t seq = 0) const {
         if (!seq) seq = next_seq();
@@ -584,6 +601,8 @@ static int dgrad_gemm(const Ctx& c, const void* dY, int dydt, int64_t lddy, int6
 // step against 11.3 ungrouped), so a group gets about ortk_tuning.wgrad_group_wgs workgroups — with the ~130-workgroup data-gradient
 // launches of the caller's stream the two queues then share the 256 units side by side (10.7 ms).  `urgent`: the caller's stream is about
 // to wait for this launch (the last group before a join): one full round of workgroups.
+// (96 since the LayerNorm backwards leave block partials: a decoder layer's 56 tiles as TWO row ranges.  As one range, 480 us a launch, the
+// groups ran back to back and the shorter chain only waited for them longer: profiles/ln_bwd_partials.txt.)
 static int flush_wgrads(const Ctx& c, bool urgent = false) {
     if (c.grp.n == 0) return 0;
     int64_t tiles = 0;
@@ -651,8 +670,28 @@ static int ln_bwd(const Ctx& c, const void* dy, const float* x, float* G, int64_
                   const float* dres, float* dx, int64_t rows, void* dz = nullptr, int next_op = -1, int dy_dt = ORTK_F32) {
     const bool fuse = dz && next_op >= 0 && (c.p_drop() > 0.f || c.adt == ORTK_BF16);
     if (fuse) TRY(c.before_write(dz));
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    LnParts* const lp = c.lnp;
+    if (lp && lp->n < lp->max && rows <= lp->rows_max && c.cfg->d_model == 512 && al16(dy) && al16(x) && al16(c.P + a) && al16(dres) && al16(dx) && al16(dz)) {
+        float* const part = lp->base + (int64_t)lp->n * lp->cap * 1024;
+        int32_t nb = 0;
+        TRY(ortk_layernorm_bwd_part(dy, dy_dt, x, c.P + a, st, dres, dx, part, lp->cap, &nb, rows, 512, 1e-6f, fuse ? dz : nullptr,
+                                    c.adt, c.p_drop(), fuse ? c.sub((uint32_t)next_op) : 0, c.drop_rows, (ortk_stream)c.s));
+        lp->slot[lp->n++] = ortk_ln_slot{part, nb, G + a, G + b};
+        return 0;
+    }
     return ortk_layernorm_bwd_dt(dy, dy_dt, x, c.P + a, st, dres, dx, G + a, G + b, rows, c.cfg->d_model, 1e-6f, fuse ? dz : nullptr,
                                  c.adt, c.p_drop(), fuse ? c.sub((uint32_t)next_op) : 0, c.drop_rows, (ortk_stream)c.s);
+}
+// The one launch that adds the slots taken so far into da / db: on the third queue behind what the caller's stream holds (*done: wait for
+// it before the gradients are read), on the caller's stream without a side stream.
+static int ln_parts_reduce(const Ctx& c, hipEvent_t* done) {
+    LnParts* const lp = c.lnp;
+    if (!lp || !lp->n) return 0;
+    auto launch = [&](hipStream_t q) { return ortk_ln_partials_reduce(lp->slot, lp->n, (ortk_stream)q); };
+    const int e = c.use_side ? c.side_launch(c.side->s2, done, launch) : launch(c.s);
+    lp->n = 0;
+    return e;
 }
 // gradient through a residual-branch dropout: the buffer (and its dtype) holding dx * keep/(1-p).
 // Mixed precision always goes through `tmp` (it also performs the fp32 -> bf16 conversion of the GEMM operand).
@@ -1225,6 +1264,8 @@ struct Bwd {
     // ortk_tuning.wgrad_group: the weight gradients of a layer / of the generator / of the memory's K|V projection as one launch each
     bool grp_layers, grp_gen, grp_kv;
     bool tail_group;             // the bf16 feature copy of this step's forward (same conditions there) lets att_embed's weight gradient join layer 0's group
+    LnParts lnp;                 // (c.lnp points here when the partials form is on)
+    void ln_slots(float* base, int64_t cap, int64_t rows_max, int max) { lnp.base = base; lnp.cap = cap; lnp.rows_max = rows_max; lnp.max = max; lnp.n = 0; }
     void* gq_of(int l) const { return (grp_layers && (l & 1)) ? w.gqkv2 : w.gqkv; }      // (a layer's group still reads the other one)
     void* gh_of(int l) const { return (grp_layers && (l & 1)) ? w.gh2 : w.gh; }
     // share_att: column blocks of a (rows, 3 d) gradient that receive dQ (0) / dK / dV, and the add that folds the shared projection's
@@ -1255,6 +1296,8 @@ static int backward_decoder_half(Bwd& s) {
     const int64_t cw = o.cw, ldg = (int64_t)L * 2 * d, gdv = cfg->share_att_dec == 1 ? (int64_t)L * d : d;
     float* dx = w.ga; float* dx2 = w.gb;
     c.drop_rows = compact ? bt->row_pos : nullptr;      // (decoder rows: the masked copies draw what the forward drew; reset below)
+    s.ln_slots(w.ln_part_dec, w.ln_cap_dec, w.Md, 3 * L + 1);
+    hipEvent_t ln_done_ev = nullptr;
     // generator (over the padded vocabulary: pad columns of dlogits are exact zeros)
     const int Vp = (int)w.ldv;
     c.grp_on = s.grp_gen;
@@ -1308,6 +1351,7 @@ static int backward_decoder_half(Bwd& s) {
         TRY(dgrad_ln_bwd(c, gql, A, 3 * d, e.wqkv, Md, amd.n * d, d, w.gy, xin, G, e.n0a, e.n0b, b.st1, dx, dx2, s.gt_new(), l > 0 ? (int)dop(l - 1, 5) : -1));
         std::swap(dx, dx2);
     }
+    TRY(ln_parts_reduce(c, &ln_done_ev));      // da / db of the half's 3 L + 1 LayerNorms: one launch beside what follows
     // the embedding gradient (atomics into the 5 M-element table) only feeds the optimizer: beside the K/V projection GEMMs
     if (c.use_side) {
         TRY(c.fork());
@@ -1330,6 +1374,7 @@ static int backward_decoder_half(Bwd& s) {
     TRY(flush_wgrads(c, true));
     c.grp_on = false;
     TRY(dgrad_gemm(c, w.gkv, A, ldg, o.ckv_w, w.gy, ORTK_F32, d, Me, (int)(U * cw), d));
+    TRY(c.wait_ev(ln_done_ev));
     TRY(c.join());
     c.drop_rows = nullptr;
     return 0;
@@ -1364,6 +1409,8 @@ static int backward_encoder_half(Bwd& s) {
         return c.use_side ? c.side_launch(c.side->s2, &box_done_ev, launch) : launch(c.s);
     };
     float* dx = w.ga; float* dx2 = w.gb;
+    s.ln_slots(w.ln_part_enc, w.ln_cap_enc, Me, 2 * L + 1);
+    hipEvent_t ln_done_ev = nullptr;
     TRY(ln_bwd(c, w.gy, w.enc[L - 1].xout, G, o.enc_na, o.enc_nb, w.st_mem, nullptr, dx, Me, s.gt_new(), eop(L - 1, 3)));
     for (int l = L - 1; l >= 0; --l) {
         const EncOff& e = o.enc[l]; const EncBuf& b = w.enc[l];
@@ -1400,6 +1447,7 @@ static int backward_encoder_half(Bwd& s) {
     // to the third queue right behind layer 0's attention backward (its workgroups hold the LDS of every unit: beside the last launch they delayed it by their 63 us).  (Before: an urgent 4-gradient launch beside the last LayerNorm backward, which
     // took 116 instead of 24 us for it, then a 120-us att_embed launch of its own on the caller's stream.)
     if (!cfg->no_box && !s.tail_group) TRY(box_grad(0, box_split ? 1 : L));
+    TRY(ln_parts_reduce(c, &ln_done_ev));      // da / db of the half's 2 L + 1 LayerNorms (third queue, before the last weight-gradient group)
     // att_embed: x0 = dropout(relu(.) * mask)  ->  d(pre-activation) = dx * [x0 > 0] / (1 - p_src)
     TRY(c.before_write(s.gt_new()));
     TRY(ortk_gate_apply(dx, w.x0, s.gt_cur, A, Me * d, c.p_src() > 0.f ? 1.f / (1.f - c.p_src()) : 1.f, stream));
@@ -1415,6 +1463,7 @@ static int backward_encoder_half(Bwd& s) {
         c.use_side = us;
     }
     TRY(c.wait_ev(box_done_ev));
+    TRY(c.wait_ev(ln_done_ev));
     return c.join();       // every gradient is final in the caller's stream order
 }
 
@@ -1454,6 +1503,7 @@ extern "C" int ortk_backward_phase(const ortk_config* cfg, const float* params, 
     s.gt_cur = w.gt;
     s.grp_layers = grouped && (wgm & 1); s.grp_gen = grouped && (wgm & 2); s.grp_kv = grouped && (wgm & 4);
     s.tail_group = s.grp_layers && c.use_side && w.feats16 && (cfg->feat % 64) == 0 && tuning().feats_bf16;
+    if (w.ln_cap_dec && !(tuning().ln_fuse & 16)) s.c.lnp = &s.lnp;
     if (phase != 2) TRY(backward_decoder_half(s));
     if (phase == 1) return 0;
     return backward_encoder_half(s);

@@ -192,8 +192,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
 // d = 512 (the model width), vector-aligned rows: lane l owns the EIGHT consecutive columns 8 l .. 8 l + 7, so that the masked bf16 copy
 // dz leaves as one 16-byte store per lane (the form above stores bf16x4 = 8 bytes: half the rate per byte, MI355X_MICROARCH.md) and a
 // bf16 dy (DYT = __bf16: the data-gradient GEMM's output stored as bf16) arrives as one 16-byte load.  Same arithmetic, same pipeline.
+//
+// Two forms of the da / db tail.  PART = false: one atomicAdd per column and block into da / db (every block of a launch adds into
+// the same 4 KB at the same time: ~9 us of a 35-us launch at 16 640 rows, profiles/ln_bwd_partials.txt).  PART = true: the block
+// stores its 2 x 512 column sums to part[block][2][512] (`da` is `part`, `db` unused) with one 16-byte store per thread and
+// issues no atomic; ln_part_reduce_kernel adds the blocks of any number of launches into their destinations later, off the
+// dependency chain.  The per-row code is the same instructions in both forms: dx and dz do not depend on the form or the grid.
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_n;
-template <typename DYT>
+template <typename DYT, bool PART>
 __global__ __launch_bounds__(256) void ln_bwd512_kernel(const DYT* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ a,
                                                         const float* __restrict__ stats, const float* __restrict__ dres, float* __restrict__ dx,
                                                         float* __restrict__ da, float* __restrict__ db, int64_t rows, float eps, int rows_per_block,
@@ -279,9 +285,61 @@ __global__ __launch_bounds__(256) void ln_bwd512_kernel(const DYT* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 8; ++i) { red[wave * 2 * d + c0 + i] = pa[i]; red[wave * 2 * d + d + c0 + i] = pb[i]; }
     __syncthreads();
+    if (PART) {     // thread t: columns 4 t .. 4 t + 3 of the block's [2][512] sums (the same four-term sum per column as below)
+        const int c = 4 * threadIdx.x;
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(red + c), w1 = *reinterpret_cast<const f32x4*>(red + 2 * d + c);
+        const f32x4 w2 = *reinterpret_cast<const f32x4*>(red + 4 * d + c), w3 = *reinterpret_cast<const f32x4*>(red + 6 * d + c);
+        f32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (w0[i] + w1[i]) + (w2[i] + w3[i]);
+        *reinterpret_cast<f32x4*>(da + (int64_t)blockIdx.x * (2 * d) + c) = v;
+        return;
+    }
     for (int c = threadIdx.x; c < 2 * d; c += 256) {
         const float v = (red[c] + red[2 * d + c]) + (red[4 * d + c] + red[6 * d + c]);
         atomicAdd(c < d ? &da[c] : &db[c - d], v);
+    }
+}
+
+// Adds the block partials of ln_bwd512_kernel<., true> launches into their destinations: slot s is part[nblocks][2][512] -> da[512], db[512].
+// A workgroup owns LN_RED_COLS consecutive columns of one slot's 1 024; its 256 threads are (LN_RED_COLS / 4 column quads) x (LN_RED_LANES
+// block lanes).  Block lane j sums the blocks j, j + LANES, ... in that order into four accumulators (block index / LANES mod 4: four loads
+// in flight per thread, not one latency chain), the lanes are then added in a fixed tree through LDS, and one atomicAdd per column
+// and slot does dst += sum (slots of one launch may share a destination: shared layers).  Every order is fixed by nblocks alone.
+constexpr int LN_RED_COLS = 32, LN_RED_LANES = 256 / (LN_RED_COLS / 4), LN_RED_SLOTS = 64;
+struct LnSlots { ortk_ln_slot s[LN_RED_SLOTS]; };
+__global__ __launch_bounds__(256) void ln_part_reduce_kernel(LnSlots sl) {
+    constexpr int Q = LN_RED_COLS / 4, WGS = 1024 / LN_RED_COLS;
+    __shared__ f32x4 red4[256];
+    const ortk_ln_slot& s = sl.s[blockIdx.x / WGS];
+    const int q = threadIdx.x % Q, j = threadIdx.x / Q, col = (blockIdx.x % WGS) * LN_RED_COLS + 4 * q;
+    const int nb = s.nblocks;
+    const float* p = s.part + col;
+    f32x4 acc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    int blk = j;
+    for (; blk + 3 * LN_RED_LANES < nb; blk += 4 * LN_RED_LANES) {
+        f32x4 t[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = *reinterpret_cast<const f32x4*>(p + (int64_t)(blk + k * LN_RED_LANES) * 1024);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] += t[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (blk + k * LN_RED_LANES < nb) acc[k] += *reinterpret_cast<const f32x4*>(p + (int64_t)(blk + k * LN_RED_LANES) * 1024);
+    red4[threadIdx.x] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    __syncthreads();
+#pragma unroll
+    for (int h = LN_RED_LANES / 2; h >= 1; h >>= 1) {
+        if (j < h) red4[threadIdx.x] += red4[threadIdx.x + h * Q];
+        __syncthreads();
+    }
+    if (threadIdx.x < LN_RED_COLS) {
+        const int c = (blockIdx.x % WGS) * LN_RED_COLS + threadIdx.x;
+        const float v = reinterpret_cast<const float*>(red4)[threadIdx.x];
+        atomicAdd(c < 512 ? &s.da[c] : &s.db[c - 512], v);
     }
 }
 
@@ -330,8 +388,8 @@ extern "C" int ortk_layernorm_bwd_dt(const void* dy_, int32_t dy_dtype, const fl
     const size_t shm = 8 * (size_t)d * sizeof(float);
     const bool vec = d % 4 == 0 && al16(dy) && al16(x) && al16(a) && al16(dres) && al16(dx) && (dz == nullptr || (reinterpret_cast<uintptr_t>(dz) & 15) == 0);
     if (d == 512 && vec && (dy_dtype == ORTK_BF16 || !(ortk::tuning().ln_fuse & 4))) {       // the model width: eight consecutive columns per lane (16-byte bf16 accesses; ln_fuse & 4: the four-column form, measurement)
-        if (dy_dtype == ORTK_BF16) hipLaunchKernelGGL(ln_bwd512_kernel<__bf16>, grid, block, shm, ortk_s(stream), reinterpret_cast<const __bf16*>(dy_), x, a, stats, dres, dx, da, db, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
-        else hipLaunchKernelGGL(ln_bwd512_kernel<float>, grid, block, shm, ortk_s(stream), dy, x, a, stats, dres, dx, da, db, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
+        if (dy_dtype == ORTK_BF16) hipLaunchKernelGGL((ln_bwd512_kernel<__bf16, false>), grid, block, shm, ortk_s(stream), reinterpret_cast<const __bf16*>(dy_), x, a, stats, dres, dx, da, db, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
+        else hipLaunchKernelGGL((ln_bwd512_kernel<float, false>), grid, block, shm, ortk_s(stream), dy, x, a, stats, dres, dx, da, db, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
         ORTK_CHECK_LAUNCH();
         return 0;
     }
@@ -341,6 +399,45 @@ extern "C" int ortk_layernorm_bwd_dt(const void* dy_, int32_t dy_dtype, const fl
     else          { if (vec) LN_B(true, 32); else LN_B(false, 32); }
 #undef LN_B
     ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
+// The partials form of the d = 512 kernel: no atomics, one [2][512] block of sums per workgroup (ln_part_blocks(rows) of them).
+extern "C" int32_t ortk_ln_part_blocks(int64_t rows) { return rows < 0 ? -1 : ortk::ln_part_blocks(rows); }
+extern "C" int32_t ortk_ln_part_rows(void) { return ortk::LN_PART_ROWS; }
+
+extern "C" int ortk_layernorm_bwd_part(const void* dy, int32_t dy_dtype, const float* x, const float* a, const float* stats, const float* dres,
+                                       float* dx, float* part, int64_t part_blocks, int32_t* nblocks_out, int64_t rows, int32_t d, float eps,
+                                       void* dz, int32_t dz_dtype, float drop_p, uint32_t drop_seed, const int32_t* drop_rows, ortk_stream stream) {
+    if (dy_dtype != ORTK_F32 && dy_dtype != ORTK_BF16) return ORTK_EINVAL;
+    if (!dy || !x || !a || !stats || !dx || !part || !nblocks_out || d != 512 || rows < 0) return ORTK_EINVAL;
+    if (dz && ((dz_dtype != ORTK_F32 && dz_dtype != ORTK_BF16) || drop_p < 0.f || drop_p >= 1.f)) return ORTK_EINVAL;
+    if (!(al16(dy) && al16(x) && al16(a) && al16(dres) && al16(dx) && al16(dz) && al16(part))) return ORTK_EINVAL;
+    const int nb = ortk::ln_part_blocks(rows);
+    if (part_blocks < nb) return ORTK_EINVAL;
+    *nblocks_out = nb;
+    if (rows == 0) return 0;
+    const int rpb = ortk::ln_part_rows_per_block(rows);
+    dim3 grid((unsigned)nb), block(256);
+    const size_t shm = 8 * 512 * sizeof(float);
+    if (dy_dtype == ORTK_BF16) hipLaunchKernelGGL((ln_bwd512_kernel<__bf16, true>), grid, block, shm, ortk_s(stream), reinterpret_cast<const __bf16*>(dy), x, a, stats, dres, dx, part, (float*)nullptr, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
+    else hipLaunchKernelGGL((ln_bwd512_kernel<float, true>), grid, block, shm, ortk_s(stream), reinterpret_cast<const float*>(dy), x, a, stats, dres, dx, part, (float*)nullptr, rows, eps, rpb, dz, (int)dz_dtype, drop_p, drop_seed, drop_rows);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ortk_ln_partials_reduce(const ortk_ln_slot* slots, int32_t n, ortk_stream stream) {
+    if (n < 0 || (n > 0 && !slots)) return ORTK_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (slots[i].nblocks < 0 || !slots[i].da || !slots[i].db || (slots[i].nblocks > 0 && (!slots[i].part || !al16(slots[i].part)))) return ORTK_EINVAL;
+    // (the slots travel as kernel arguments: LN_RED_SLOTS per launch, ONE launch for a training step's 19 + 13)
+    for (int i0 = 0; i0 < n; i0 += LN_RED_SLOTS) {
+        LnSlots sl; int m = 0;
+        for (int i = i0; i < n && m < LN_RED_SLOTS; ++i) if (slots[i].nblocks > 0) sl.s[m++] = slots[i];
+        if (!m) continue;
+        hipLaunchKernelGGL(ln_part_reduce_kernel, dim3((unsigned)(m * (1024 / LN_RED_COLS))), dim3(256), 0, ortk_s(stream), sl);
+        ORTK_CHECK_LAUNCH();
+    }
     return 0;
 }
 

@@ -21,7 +21,7 @@ static ortk_tuning tuning_defaults() {
     t.wgrad_wgs = 384;
     t.wgrad_group = 3;
     t.wgrad_group_splitk = 0;
-    t.wgrad_group_wgs = 80;
+    t.wgrad_group_wgs = 96;
     t.wgrad_group_tail = 1;
     t.feats_bf16 = 1;
     t.ln_fuse = 0;
@@ -42,7 +42,7 @@ extern "C" int ortk_set_tuning(const ortk_tuning* t) {
     // (gemm_t64, side_stream, chain_wide and spmm_alias are read as thresholds / flags: any value is served)
     if (!in(t->row_chain, 0, 1) /* 2, 3: the executor's backward chains, removed */ || !in(t->attn_impl, 0, 4) || t->attn16_min_lq < 1 || !in(t->f32_split, 0, 7) || t->wgrad_wgs < 1 ||
         !in(t->wgrad_group, 0, 15) || !in(t->wgrad_group_splitk, 0, 8) || t->wgrad_group_wgs < 1 || !in(t->wgrad_group_tail, 0, 1) ||
-        !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 15) || (t->ln_fuse & 3) /* bit 0: the executor's fused data gradient + LayerNorm backward, bit 1: the 128-row backward panels, removed */ ||
+        !in(t->feats_bf16, 0, 1) || !in(t->ln_fuse, 0, 31) || (t->ln_fuse & 3) /* bit 0: the executor's fused data gradient + LayerNorm backward, bit 1: the 128-row backward panels, removed */ ||
         !in(t->samp_epilogue, 0, 1) || !in(t->gemm_epilogue, 0, 3) ||
         !(in(t->attn16_short, 0, 1) || t->attn16_short == 4 || t->attn16_short == 8) || !in(t->attn16_block, 0, 1)) return ORTK_EINVAL;
     ortk::g_tuning = *t;
