@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 17   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 18   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -413,6 +413,7 @@ int ortk_set_tuning(const ortk_tuning* t);
 #define ORTK_DEC_SPLIT_SMALL 32
 #define ORTK_DEC_SPARSE_GATHER 64
 #define ORTK_DEC_STACK_FP8 128
+#define ORTK_DEC_GROUPS_JOINT 65536   /* bit 16 (bits 8-15 are the measurement switches) */
 #define ORTK_MAX_BEAM 32      /* widest beam search ortk_decode serves: 2 .. 8 beams run the narrow selection step, 9 .. 32 the wide one */
 typedef struct ortk_decode_opts {
     int32_t beam_size;            /* 1 = greedy; >1 = beam search, at most ORTK_MAX_BEAM beams (and at most cfg->vocab): wider is ORTK_EINVAL
@@ -473,6 +474,18 @@ typedef struct ortk_decode_opts {
      *                           ORTK_DEC_SPARSE_STREAM, ORTK_DEC_SPARSE_GATHER, ORTK_DEC_STACK_SPLIT, ORTK_DEC_SPLIT_SMALL or
      *                           ORTK_DEC_STACK_RB20, with a sparse plan, with `train`, and for a configuration the stack kernel does
      *                           not serve;
+     *   ORTK_DEC_GROUPS_JOINT   (bit 16) with group_size = G > 1: the JOINT diverse executor — the decoder passes of all groups of a
+     *                           global step as ONE launch sequence of the unfused operators over the G * B * bd rows (group-major
+     *                           blocks, each at its own position: per-row positions in the embedding, ortk_attn_args.lk_row /
+     *                           kv_index_off in the cached self-attention; cross-attention stays one call per active block and
+     *                           layer), then ONE selection launch that walks the active groups in ascending order.  All G blocks
+     *                           run in every global step, so the operators see the same row count throughout; blocks that have not
+     *                           started or have finished are idle rows (a valid token at position 0, no keys, nothing of their
+     *                           caches or tables touched).  The position-0 pass of a group stays the separate B-row sequence.  The
+     *                           schedule, the results' definition and the served options are those of group_size; opt-in, never an
+     *                           automatic choice.  ORTK_EINVAL (ortk_decode_workspace_bytes: 0): with group_size <= 1, with any bit
+     *                           of the stack family (ORTK_DEC_STACK, _SPARSE_STREAM, _STACK_RB20, _STACK_SPLIT, _SPARSE_GATHER,
+     *                           _STACK_FP8), with `train`, with num_random_sample > 0;
      *   bits 8-15               measurement / tests only: skip self-attention (1) / cross-attention (2) / the FFN (4), no L2
      *                           prefetchers (8); column-split form: deal the members of a group over different XCDs (16), one member
      *                           of group 0 never arrives (32); beam decodes of every width run the wide selection step (64: ignored
@@ -534,7 +547,7 @@ typedef struct ortk_decode_opts {
      * unaugmented one (with the -inf of decoding_constraint), finished beams score length_penalty(t + 1, cum).  Output rows
      * g * bd .. (g + 1) * bd - 1 of an image: group g's best bd finished hypotheses.  Group 0 is the plain beam search of width bd.
      * bd = 1 (G = b) is served.  Executors: the unfused one (exec_flags 0, ORTK_DEC_SPLIT_SMALL alone or ORTK_DEC_UNFUSED), in both
-     * precisions and with a sparse plan; G launch sequences per position.
+     * precisions and with a sparse plan; G launch sequences per position — or, with ORTK_DEC_GROUPS_JOINT, one per global step.
      * ORTK_EINVAL (ortk_decode_workspace_bytes: 0): G < 0; with G > 1: b % G != 0, G > b, b > ORTK_MAX_BEAM, diversity_lambda negative
      * or not finite, num_random_sample > 0, train, an exec_flags bit of the stack family. */
     int32_t group_size;
@@ -781,6 +794,22 @@ typedef struct ortk_attn_args {
      * index ((g*H + h) * Lq + i') * Lk + j.  Cross-attention on the valid positions (an image's rows are the valid positions of
      * its captions) then draws what the padded layout draws; forward and backward alike. */
     const int32_t* drop_rows;
+    /* forward only, Lq = 1 (cached self-attention of rows at DIFFERENT positions in one launch): lk_row[g] (nkv entries on the
+     * device, 0 <= lk_row[g] <= Lk; values outside are clamped) is the key count of group g — it attends to keys 0 .. lk_row[g]-1.
+     * Lk stays the upper bound: it picks the kernel instance and remains the row stride of kmask and p.  With k_new / v_new the new
+     * position becomes key lk_row[g]-1 of group g (written to that cache row and attended to, as key Lk-1 without lk_row).
+     * lk_row[g] = 0: the group is idle — its o row is written as zeros, nothing is appended, and no cache row, kmask, p or kv_index
+     * entry of the group is read or written.  With lk_row[g] = Lk for every g and no kv_index the results are the bytes of the
+     * call without lk_row (default ortk_tuning).  Served by the fp32-product kernels of the one-row shapes: rowdec, small_fwd and
+     * the generic kernel (which here also reads bf16 caches, kv_dtype = 1, at any Lk <= 128), each in an instance of its own,
+     * behind kv_append's where the kernel does not append itself; ortk_attention_plan reports the routing.  ORTK_EINVAL: Lq != 1,
+     * the backward, drop_p > 0, qkv_dtype / q_off, kv_index without kv_index_off, and a call that only the bf16-operand kernels
+     * would take (precision = 1, more than 48 fp32 keys, no kv_index / kv_group_stride). */
+    const int32_t* lk_row;
+    /* with lk_row and kv_index (then required; not read otherwise): key j of group g is physical row
+     * kv_index[kv_index_off[g] + j] (nkv entries on the device) instead of kv_index[g*Lk + j] — ancestry tables whose row stride
+     * differs from block to block (blocks of rows at different positions), possibly in different buffers of one allocation. */
+    const int64_t* kv_index_off;
 } ortk_attn_args;
 int ortk_attention_fwd(const ortk_attn_args* a, ortk_stream stream);
 int ortk_attention_bwd(const ortk_attn_args* a, ortk_stream stream);

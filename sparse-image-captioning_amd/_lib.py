@@ -122,6 +122,7 @@ class LnSlot(C.Structure):       # include/ortk.h: ortk_ln_slot
 
 MAX_BEAM = 32      # include/ortk.h: ORTK_MAX_BEAM
 DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_SPLIT_SMALL, DEC_SPARSE_GATHER, DEC_STACK_FP8 = 1, 2, 4, 8, 16, 32, 64, 128      # ortk_decode_opts.exec_flags
+DEC_GROUPS_JOINT = 1 << 16      # (bits 8-15: the measurement switches)
 
 
 class DecodeOpts(C.Structure):
@@ -177,7 +178,8 @@ class AttnArgs(C.Structure):
                 ("k_new", C.c_void_p), ("v_new", C.c_void_p), ("ld_new", C.c_int64), ("bwd_part", C.c_int32),
                 ("precision", C.c_int32), ("qkv_dtype", C.c_int32),
                 ("q_off", C.c_void_p), ("q_off_stride", C.c_int32), ("kv_ragged", C.c_int32),
-                ("drop_tf_T", C.c_int32), ("drop_tf_t", C.c_int32), ("drop_tf_lk", C.c_int32), ("drop_rows", C.c_void_p)]
+                ("drop_tf_T", C.c_int32), ("drop_tf_t", C.c_int32), ("drop_tf_lk", C.c_int32), ("drop_rows", C.c_void_p),
+                ("lk_row", C.c_void_p), ("kv_index_off", C.c_void_p)]
 
 
 _P, _I32, _I64, _F, _U32, _U64, _SZ = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32, C.c_uint64, C.c_size_t
@@ -280,7 +282,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 17   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 18   # include/ortk.h: ORTK_VERSION
 
 
 def lib():

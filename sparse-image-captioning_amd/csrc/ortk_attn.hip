@@ -48,24 +48,45 @@ __device__ __forceinline__ Tiles carve_fwd(float* base, int Lk) {
     return t;
 }
 
-__device__ __forceinline__ void load_kv(Tiles& t, const ortk_attn_args& a, int g, int h) {
+// ROWLK (ortk_attn_args.lk_row, one query row per group): group g has Lk = lk_row[g] keys of its own, a.Lk stays the stride of kmask / p
+// and of the default kv_index layout; the caches may be bf16 (kv_dtype)
+__device__ __forceinline__ int lk_of_row(const ortk_attn_args& a, int g) { return min(max(a.lk_row[g], 0), a.Lk); }
+// the group's key count: a.Lk itself, spelled at every use as before, unless ROWLK (lkr = lk_of_row)
+template <bool ROWLK> __device__ __forceinline__ int lk_sel(const ortk_attn_args& a, int lkr) { if constexpr (ROWLK) return lkr; else return a.Lk; }
+// first entry of group g's keys in kv_index
+template <bool ROWLK> __device__ __forceinline__ int64_t kvi_base(const ortk_attn_args& a, int64_t g) {
+    if constexpr (ROWLK) return a.kv_index_off ? a.kv_index_off[g] : g * a.Lk; else return g * a.Lk;
+}
+template <bool ROWLK>
+__device__ __forceinline__ void load_kv(Tiles& t, const ortk_attn_args& a, int g, int h, int lkr) {
     const int tid = threadIdx.x;
-    for (int idx = tid; idx < a.Lk * a.dk; idx += 256) {
+    for (int idx = tid; idx < lk_sel<ROWLK>(a, lkr) * a.dk; idx += 256) {
         const int j = idx / a.dk, dd = idx - j * a.dk;
-        const int64_t row = a.kv_index ? (int64_t)a.kv_index[(int64_t)g * a.Lk + j]
+        const int64_t row = a.kv_index ? (int64_t)a.kv_index[kvi_base<ROWLK>(a, g) + j]
                                        : (int64_t)g * (a.kv_group_stride > 0 ? a.kv_group_stride : a.Lk) + j;
-        t.k[j][dd] = a.k[row * a.ldk + h * a.dk + dd];
-        t.v[j][dd] = a.v[row * a.ldv + h * a.dk + dd];
+        if constexpr (ROWLK) {
+            t.k[j][dd] = ld_elem(a.k, row * a.ldk + h * a.dk + dd, a.kv_dtype);
+            t.v[j][dd] = ld_elem(a.v, row * a.ldv + h * a.dk + dd, a.kv_dtype);
+        } else {
+            t.k[j][dd] = a.k[row * a.ldk + h * a.dk + dd];
+            t.v[j][dd] = a.v[row * a.ldv + h * a.dk + dd];
+        }
     }
-    for (int j = tid; j < a.Lk; j += 256) t.mask[j] = a.kmask ? a.kmask[(int64_t)g * a.Lk + j] : 1.f;
+    for (int j = tid; j < lk_sel<ROWLK>(a, lkr); j += 256) t.mask[j] = a.kmask ? a.kmask[(int64_t)g * a.Lk + j] : 1.f;
 }
 
-__global__ __launch_bounds__(256) void attn_fwd_kernel(ortk_attn_args a) {
-    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+template <bool ROWLK>
+__device__ __forceinline__ void attn_fwd_body(const ortk_attn_args& a, float* smem_f) {
     Tiles t = carve_fwd(smem_f, a.Lk);
     const int g = blockIdx.x / a.H, h = blockIdx.x - g * a.H;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    load_kv(t, a, g, h);
+    int lkr = 0;
+    if constexpr (ROWLK) lkr = lk_of_row(a, g);
+    if (ROWLK && lkr == 0) {      // idle group (the whole workgroup): a zero row, nothing of the group read
+        if (threadIdx.x < a.dk) st_elem(a.o, (int64_t)g * a.ldo + h * a.dk + threadIdx.x, a.o_dtype, 0.f);
+        return;
+    }
+    load_kv<ROWLK>(t, a, g, h, lkr);
     __syncthreads();
     const float scale = sqrtf((float)a.dk);
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
@@ -83,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(ortk_attn_args a) {
         for (int u = 0; u < 2; ++u) {
             const int j = lane + 64 * u;
             s[u] = -INFINITY;
-            if (j < a.Lk) {
+            if (j < lk_sel<ROWLK>(a, lkr)) {
                 float acc = 0.f;
                 for (int dd = 0; dd < a.dk; ++dd) acc += t.q[wave][dd] * t.k[j][dd];
                 acc = acc / scale;
@@ -97,12 +118,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(ortk_attn_args a) {
         mx = wave_max(mx);
         float e[2], sum = 0.f;
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { e[u] = (lane + 64 * u < a.Lk) ? expf(s[u] - mx) : 0.f; sum += e[u]; }
+        for (int u = 0; u < 2; ++u) { e[u] = (lane + 64 * u < lk_sel<ROWLK>(a, lkr)) ? expf(s[u] - mx) : 0.f; sum += e[u]; }
         sum = wave_sum(sum);
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int j = lane + 64 * u;
-            if (j < a.Lk) {
+            if (j < lk_sel<ROWLK>(a, lkr)) {
                 float p = e[u] / sum;
                 if (a.p) a.p[pbase + j] = p;
                 if (a.drop_p > 0.f) p = ortk_keep(a.drop_seed, (uint64_t)(dbase + j), a.drop_p) ? p * inv_keep : 0.f;
@@ -112,11 +133,19 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(ortk_attn_args a) {
         wave_sync();
         if (lane < a.dk) {
             float o = 0.f;
-            for (int j = 0; j < a.Lk; ++j) o += t.p[wave][j] * t.v[j][lane];
+            for (int j = 0; j < lk_sel<ROWLK>(a, lkr); ++j) o += t.p[wave][j] * t.v[j][lane];
             st_elem(a.o, qrow * a.ldo + h * a.dk + lane, a.o_dtype, o);
         }
         wave_sync();
     }
+}
+__global__ __launch_bounds__(256) void attn_fwd_kernel(ortk_attn_args a) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    attn_fwd_body<false>(a, smem_f);
+}
+__global__ __launch_bounds__(256) void attn_fwd_lk_kernel(ortk_attn_args a) {
+    extern __shared__ __attribute__((aligned(16))) float smem_f[];
+    attn_fwd_body<true>(a, smem_f);
 }
 
 // Forward, fast form (Lk <= 64): one wave per (K/V group, head) pair, no workgroup barrier (see the backward below).
@@ -508,15 +537,22 @@ template <> __device__ __forceinline__ void ld_row8<__bf16>(const __bf16* p, flo
 //     the probabilities never leave their registers; the matching V rows are read as 64-byte row segments.
 // The backward runs the same scheme twice: transposed layout for dQ, natural layout (operands of the dP product
 // swapped, no extra loads) for dK and dV.
-template <int NIT, int NJT, typename KVT>
+// ROWLK (ortk_attn_args.lk_row; Lq = 1): the group has Lk = lk_row[g] keys of its own (0: idle, a zero row out and nothing else touched);
+// LkS = a.Lk stays the stride of kmask / p.
+template <int NIT, int NJT, typename KVT, bool ROWLK = false>
 __global__ __launch_bounds__(256) void attn_small_fwd_kernel(ortk_attn_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pair = blockIdx.x * 4 + wave;
     if (pair >= a.nkv * a.H) return;
     const int g = pair / a.H, h = pair - g * a.H;
-    const int Lq = a.Lq, Lk = a.Lk;
+    const int Lq = a.Lq, LkS = a.Lk;
+    const int Lk = ROWLK ? lk_of_row(a, g) : LkS;
+    if (ROWLK && Lk == 0) {
+        st_elem(a.o, (int64_t)g * a.ldo + h * 64 + lane, a.o_dtype, 0.f);
+        return;
+    }
     const int lr = lane & 15, lq = lane >> 4;
-    const int64_t kv0 = (int64_t)g * (a.kv_group_stride > 0 ? a.kv_group_stride : Lk);
+    const int64_t kv0 = (int64_t)g * (a.kv_group_stride > 0 ? a.kv_group_stride : LkS);
     const float* qb = a.q + (int64_t)g * Lq * a.ldq + h * 64;
     const KVT* kb = reinterpret_cast<const KVT*>(a.k) + kv0 * a.ldk + h * 64;
     const KVT* vb = reinterpret_cast<const KVT*>(a.v) + kv0 * a.ldv + h * 64;
@@ -536,7 +572,7 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(ortk_attn_args a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = 16 * jt + 4 * lq + r;
-            mk[jt][r] = j < Lk ? (a.kmask ? a.kmask[(int64_t)g * Lk + j] : 1.f) : -1.f;
+            mk[jt][r] = j < Lk ? (a.kmask ? a.kmask[(int64_t)g * LkS + j] : 1.f) : -1.f;
         }
     const float scale = sqrtf(64.f);
     const float inv_keep = a.drop_p > 0.f ? 1.f / (1.f - a.drop_p) : 1.f;
@@ -558,7 +594,7 @@ __global__ __launch_bounds__(256) void attn_small_fwd_kernel(ortk_attn_args a) {
         }
         const int i = 16 * it + lr;
         const int qpos = a.causal_period > 0 ? i % a.causal_period : 0;
-        const int64_t prow = (((int64_t)g * a.H + h) * Lq + min(i, Lq - 1)) * Lk;
+        const int64_t prow = (((int64_t)g * a.H + h) * Lq + min(i, Lq - 1)) * LkS;
         float mx = -INFINITY;
 #pragma unroll
         for (int jt = 0; jt < NJT; ++jt)
@@ -786,22 +822,32 @@ __global__ __launch_bounds__(256) void attn_small_bwd_kernel(ortk_attn_args a) {
 // 2-KB read shared by the 8 heads; a score is 8 FMAs + a 3-step reduction over the 8 lanes of the head; the soft-max
 // runs redundantly in those lanes; P.V is 8 FMAs per key.  Keys come through the beam ancestry table (kv_index) or
 // a fixed stride.  Replaces 8 x rows workgroups of the generic block kernel (75 us -> see DESIGN.md section 7).
-template <int LKMAX, typename KVT>
+// ROWLK (ortk_attn_args.lk_row): the wave's row has Lk = lk_row[g] keys of its own (0: an idle row, zeros out and nothing else touched);
+// LkS = a.Lk stays the stride of kmask / p, and of kv_index where kv_index_off does not place the row's entries.
+template <int LKMAX, typename KVT, bool ROWLK = false>
 __global__ __launch_bounds__(256) void attn_rowdec_kernel(ortk_attn_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = blockIdx.x * 4 + wave;
     if (g >= a.nkv) return;
-    const int Lk = a.Lk;
+    const int LkS = a.Lk;
+    const int Lk = ROWLK ? lk_of_row(a, g) : LkS;
+    if (ROWLK && Lk == 0) {
+        const int64_t oz = (int64_t)g * a.ldo + 8 * lane;
+        st_elem4(a.o, oz, a.o_dtype, make_float4(0.f, 0.f, 0.f, 0.f));
+        st_elem4(a.o, oz + 4, a.o_dtype, make_float4(0.f, 0.f, 0.f, 0.f));
+        return;
+    }
     const float* qp = a.q + (int64_t)g * a.ldq + 8 * lane;
     const float4 q0 = *reinterpret_cast<const float4*>(qp), q1 = *reinterpret_cast<const float4*>(qp + 4);
-    const int64_t base = (int64_t)g * (a.kv_group_stride > 0 ? a.kv_group_stride : Lk);
+    const int64_t base = (int64_t)g * (a.kv_group_stride > 0 ? a.kv_group_stride : LkS);
+    const int64_t ib = (ROWLK && a.kv_index_off) ? a.kv_index_off[g] : (int64_t)g * LkS;
     float sc[LKMAX];
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < LKMAX; ++j) {
         sc[j] = -INFINITY;
         if (j < Lk) {
-            const int64_t row = a.kv_index ? (int64_t)a.kv_index[(int64_t)g * Lk + j] : base + j;
+            const int64_t row = a.kv_index ? (int64_t)a.kv_index[ib + j] : base + j;
             float4 k0, k1;
             if (a.k_new && j == Lk - 1) {      // the new position: take K from the projection output and append it to the cache
                 ld_row8<float>(a.k_new + (int64_t)g * a.ld_new + 8 * lane, k0, k1);
@@ -813,7 +859,7 @@ __global__ __launch_bounds__(256) void attn_rowdec_kernel(ortk_attn_args a) {
             float d = q0.x * k0.x + q0.y * k0.y + q0.z * k0.z + q0.w * k0.w + q1.x * k1.x + q1.y * k1.y + q1.z * k1.z + q1.w * k1.w;
             d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64);
             d *= 0.125f;                                              // 1 / sqrt(64)
-            if (a.kmask && a.kmask[(int64_t)g * Lk + j] == 0.f) d = -1e9f;
+            if (a.kmask && a.kmask[(int64_t)g * LkS + j] == 0.f) d = -1e9f;
             sc[j] = d;
             mx = fmaxf(mx, d);
         }
@@ -826,7 +872,7 @@ __global__ __launch_bounds__(256) void attn_rowdec_kernel(ortk_attn_args a) {
 #pragma unroll
     for (int j = 0; j < LKMAX; ++j) {
         if (j < Lk) {
-            const int64_t row = a.kv_index ? (int64_t)a.kv_index[(int64_t)g * Lk + j] : base + j;
+            const int64_t row = a.kv_index ? (int64_t)a.kv_index[ib + j] : base + j;
             float4 v0, v1;
             if (a.v_new && j == Lk - 1) {
                 ld_row8<float>(a.v_new + (int64_t)g * a.ld_new + 8 * lane, v0, v1);
@@ -836,7 +882,7 @@ __global__ __launch_bounds__(256) void attn_rowdec_kernel(ortk_attn_args a) {
                 ld_row8<KVT>(reinterpret_cast<const KVT*>(a.v) + row * a.ldv + 8 * lane, v0, v1);
             }
             const float pj = sc[j] * inv;
-            if (a.p) { if ((lane & 7) == 0) a.p[((int64_t)g * a.H + (lane >> 3)) * Lk + j] = pj; }
+            if (a.p) { if ((lane & 7) == 0) a.p[((int64_t)g * a.H + (lane >> 3)) * LkS + j] = pj; }
             o[0] += pj * v0.x; o[1] += pj * v0.y; o[2] += pj * v0.z; o[3] += pj * v0.w;
             o[4] += pj * v1.x; o[5] += pj * v1.y; o[6] += pj * v1.z; o[7] += pj * v1.w;
         }
@@ -1109,6 +1155,20 @@ __global__ void attn_kv_append_kernel(ortk_attn_args a) {
         st_elem(const_cast<float*>(a.v), row * a.ldv + c, a.kv_dtype, a.v_new[g * a.ld_new + c]);
     }
 }
+// the same with per-row key counts (ortk_attn_args.lk_row): the new position is key lk_row[g] - 1 of group g, an idle group (0 keys)
+// appends nothing.  (A kernel of its own: the shared body moved the instruction schedule of the one above.)
+__global__ void attn_kv_append_lk_kernel(ortk_attn_args a) {
+    const int d = a.H * a.dk;
+    const int64_t n = (int64_t)a.nkv * d;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t g = i / d; const int c = (int)(i - g * d);
+        const int j = lk_of_row(a, (int)g) - 1;
+        if (j < 0) continue;
+        const int64_t row = a.kv_index ? (int64_t)a.kv_index[kvi_base<true>(a, g) + j] : g * (a.kv_group_stride > 0 ? a.kv_group_stride : a.Lk) + j;
+        st_elem(const_cast<float*>(a.k), row * a.ldk + c, a.kv_dtype, a.k_new[g * a.ld_new + c]);
+        st_elem(const_cast<float*>(a.v), row * a.ldv + c, a.kv_dtype, a.v_new[g * a.ld_new + c]);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ host side: validate -> plan -> launch
 namespace {
@@ -1126,6 +1186,11 @@ const AttnInst ROWDEC[4][2] = {{INST(rowdec, 8,f32), INST(rowdec, 8,bf16)}, {INS
 const AttnInst SMALL_FWD[3][3] = {{INST(small_fwd, 1,1,f32), INST(small_fwd, 1,2,f32), INST(small_fwd, 1,3,f32)},                // [query tiles - 1, or 2: bf16 K / V][key tiles - 1]
                                   {INST(small_fwd, 2,1,f32), INST(small_fwd, 2,2,f32), INST(small_fwd, 2,3,f32)},
                                   {INST(small_fwd, 1,1,bf16), INST(small_fwd, 1,2,bf16), INST(small_fwd, 1,3,bf16)}};
+// the instances of the same kernels that read ortk_attn_args.lk_row (one query row per group: one query tile)
+const AttnInst ROWDEC_LK[4][2] = {{INST(rowdec, 8,f32,true), INST(rowdec, 8,bf16,true)}, {INST(rowdec, 16,f32,true), INST(rowdec, 16,bf16,true)},
+                                  {INST(rowdec, 24,f32,true), INST(rowdec, 24,bf16,true)}, {INST(rowdec, 32,f32,true), INST(rowdec, 32,bf16,true)}};
+const AttnInst SMALL_FWD_LK[2][3] = {{INST(small_fwd, 1,1,f32,true), INST(small_fwd, 1,2,f32,true), INST(small_fwd, 1,3,f32,true)},             // [kv_dtype][key tiles - 1]
+                                     {INST(small_fwd, 1,1,bf16,true), INST(small_fwd, 1,2,bf16,true), INST(small_fwd, 1,3,bf16,true)}};
 const AttnInst SMALL_BWD[2][2] = {{INST(small_bwd, 1,1), INST(small_bwd, 1,2)}, {INST(small_bwd, 2,1), INST(small_bwd, 2,2)}};    // [query tiles - 1][key tiles - 1]
 const struct { AttnInst k; size_t lds_limit; } BWD_WAVE[3] = {{INST(bwd_wave, 32), 0}, {INST(bwd_wave, 48), wave_lds(48, 192)}, {INST(bwd_wave, 64), wave_lds(64, 192)}};
 AttnInst fwd_mfma_inst(int Lkp, int DKP) {
@@ -1175,9 +1240,21 @@ int plan_fwd(const ortk_attn_args& a_in, AttnPlan& pl) {
     if (a_in.k_new && (a_in.Lq != 1 || a_in.ld_new < (int64_t)a_in.H * a_in.dk)) return ORTK_EINVAL;
     ortk_attn_args a = a_in;
     const int64_t pairs = (int64_t)a.nkv * a.H;
+    const bool rowlk = a.lk_row != nullptr;      // per-row key counts (checked by plan_attention): the *_lk instances below
     if (a.k_new && !rowdec_ok(a)) {       // every other kernel: append first, then attend to the cache as usual
-        pl.add(INST0(kv_append), std::max<int64_t>(1, std::min<int64_t>(ortk_cdiv(pairs * a.dk, 256), 2048)), 256, 0);
+        pl.add(rowlk ? INST0(kv_append_lk) : INST0(kv_append), std::max<int64_t>(1, std::min<int64_t>(ortk_cdiv(pairs * a.dk, 256), 2048)), 256, 0);
         a.k_new = a.v_new = nullptr;
+    }
+    if (rowlk) {
+        // The kernel the call takes without lk_row under the default tuning, in its lk_row instance: the row kernel, the register-only
+        // kernel, the generic kernel (here it also reads bf16 caches).  The bf16-operand kernels have no such instance: a call that
+        // only they take is refused, not computed with other numerics.
+        AttnPlan other;
+        if (attn_impl() == 0 && ortk::attn16_plan(a, false, other)) return ORTK_EINVAL;
+        if (rowdec_ok(a)) pl.add(ROWDEC_LK[(a.Lk - 1) / 8][a.kv_dtype], ortk_cdiv(a.nkv, 4), 256, 0);
+        else if (small_fwd_ok(a)) pl.add(SMALL_FWD_LK[a.kv_dtype][(a.Lk - 1) / 16], ortk_cdiv(pairs, 4), 256, 0);
+        else pl.add(INST0(fwd_lk), pairs, 256, fwd_lds_bytes(a.Lk), fwd_lds_bytes(MAXK));
+        return 0;
     }
     if ((attn_impl() == 0 || a.qkv_dtype) && ortk::attn16_plan(a, false, pl)) return 0;      // mixed precision
     if (a.qkv_dtype || a.q_off) return ORTK_EINVAL;   // bf16 Q / K / V and ragged groups are only understood by the bf16-operand kernels
@@ -1252,6 +1329,8 @@ int plan_attention(const ortk_attn_args& a, bool bwd, AttnPlan& pl) {
     if (!a.q || !a.k || !a.v) return ORTK_EINVAL;
     if (a.Lk < 1 || a.Lk > MAXK || a.dk < 1 || a.dk > MAXD || a.Lq < 1 || a.H < 1 || a.nkv < 0) return ORTK_EINVAL;
     if (a.drop_p < 0.f || a.drop_p >= 1.f) return ORTK_EINVAL;
+    // per-row key counts: the forward of one query row per group, no dropout, fp32 query rows in the regular layout
+    if (a.lk_row && (bwd || a.Lq != 1 || a.drop_p > 0.f || a.qkv_dtype || a.q_off || (a.kv_index && !a.kv_index_off))) return ORTK_EINVAL;
     return bwd ? plan_bwd(a, pl) : plan_fwd(a, pl);
 }
 

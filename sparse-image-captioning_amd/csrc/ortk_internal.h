@@ -113,6 +113,23 @@ int beam_step(const BeamState& st, const float* logp, int32_t t, hipStream_t s, 
 // first loses lambda x (beams of groups 0 .. g-1 of the image that hold its token at column t now); g = 0: the wide step.
 int beam_step_diverse(const BeamState& st, const float* logp, int32_t t, hipStream_t s, float scale, bool fast_exp, const int32_t* const seq0[2],
                       int64_t gstride, int32_t g, float lambda);
+// The joint diverse executor (ORTK_DEC_GROUPS_JOINT): G BeamStates do not fit a kernel's arguments, so the selection launch takes
+// group 0's state and the strides of the group-major carving — group g's arrays lie g x (rows; x L for seq / tok_lp / done_p /
+// done_len; x (L + 1) for kvidx; x L x L for done_seq / done_lp; B for done_cnt) elements behind group 0's.
+struct JointGroups {
+    int32_t G;
+    int64_t rows;                        // rows of one group: B x b
+    const float *logp, *logp0;           // logit rows of the joint pass (G x rows, ldv) and of the position-0 pass (B, ldv)
+    const float *gstats, *gstats0;       // their soft-max partials (BeamState.gstats of either pass), or NULL
+};
+// every group's local step t = Tg - g (0 <= t < L) of global step Tg, in ascending g, in ONE launch (beam_step_diverse's contract per
+// group; scale_later: the scale of positions > 0, position 0 takes 1).  The slot a new beam gets in the ancestry table is numbered over
+// ALL groups' cache rows (group g's first cache row is g x rows x tmax).
+int beam_step_diverse_joint(const BeamState& st0, const JointGroups& jg, int32_t Tg, hipStream_t s, float scale_later, bool fast_exp, float lambda);
+// per-row arrays of the joint decoder pass of global step Tg (block g at position Tg - g when that is 1 .. L - 1, else idle)
+int joint_rows(const int64_t* it, int64_t* tok_tab, int32_t* row_pos, int32_t* lk_row, int64_t* kv_off, int64_t rows, int32_t G, int32_t L, int32_t Tg,
+               int64_t kv_pp, hipStream_t s);
+int joint_kvidx_init(int32_t* kvidx, int64_t rows, int32_t B, int32_t b, int32_t G, int32_t L, hipStream_t s);
 int beam_finalize(const BeamState& st, int64_t* seq_out, float* lp_out, float* score_out, hipStream_t s);
 
 struct SampleState {

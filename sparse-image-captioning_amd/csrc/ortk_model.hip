@@ -1595,6 +1595,9 @@ struct DecodeWS {
     int32_t* status = nullptr;         // [64] decode status word (ortk_decode_status): ALWAYS the first bytes of the workspace
     void* ckv_g = nullptr;             // train-mode decode with greedy rows: projection of the EVAL-mode encoder memory
     int64_t* fin_seq = nullptr; float *fin_lp = nullptr, *fin_score = nullptr;      // diverse beam groups: one group's finalised rows (B * K each)
+    // the joint diverse executor: logits (and their partials) of a group's position-0 pass (B rows), which live beside the joint pass's;
+    // the per-row arrays of a joint pass (joint_rows): token table (rows, T), row_pos / lk_row (rows), kv_off (rows)
+    float *logits0 = nullptr, *gstats0 = nullptr; int64_t* jtok = nullptr; int32_t *jpos = nullptr, *jlk = nullptr; int64_t* jkvoff = nullptr;
     size_t bytes;
 };
 
@@ -1624,9 +1627,10 @@ static int split_degree(bool dense_stack, int32_t flags, int64_t rows) {
     return ((flags & ORTK_DEC_SPLIT_SMALL) && !(flags & ORTK_DEC_STACK) && G >= 4) ? G : 0;     // the small decodes only (8 or 4 per group)
 }
 // groups > 1 (diverse beam search): K is the width of ONE group; every per-row buffer holds `groups` blocks of B * K rows (beam
-// state, self-attention caches and tokens per group; the activation buffers are shared, a group's pass uses their first B * K rows)
+// state, self-attention caches and tokens per group; the activation and logit buffers hold all groups' rows: a group's pass of the
+// staggered executor uses their first B * K rows, the joint executor's pass all of them — `joint` adds what only it needs)
 static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, void* base, DecodeWS& w, bool stack = false, bool sstream = false,
-                         bool train = false, int tp = 0, bool greedy_rows = false, bool fp8 = false, int groups = 1) {
+                         bool train = false, int tp = 0, bool greedy_rows = false, bool fp8 = false, int groups = 1, bool joint = false) {
     const int64_t d = c.d_model, ff = c.d_ff, H = c.n_heads, L = c.n_layers, T = c.seq_len;
     // bf16 K / V storage: only when both decode attention kernels that understand it will be the ones dispatched
     w.kvdt = (c.precision && H == 8 && d == 512 && S > 8 && S <= 48 && T <= 32 && K <= 16) ? ORTK_BF16 : ORTK_F32;
@@ -1685,6 +1689,11 @@ static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, v
         w.done_seq = b.take<int32_t>(rows * T * T); w.done_lp = b.take<float>(rows * T * T);
         w.done_p = b.take<double>(rows * T); w.done_len = b.take<int32_t>(rows * T); w.done_cnt = b.take<int32_t>((int64_t)B * groups);
         if (groups > 1) { w.fin_seq = b.take<int64_t>((int64_t)B * K * T); w.fin_lp = b.take<float>((int64_t)B * K * T); w.fin_score = b.take<float>((int64_t)B * K); }
+        if (joint) {
+            w.logits0 = b.take<float>((int64_t)B * w.ldv);
+            if (c.precision) w.gstats0 = b.take<float>((int64_t)B * (w.ldv / 64) * 2);
+            w.jtok = b.take<int64_t>(rows * T); w.jkvoff = b.take<int64_t>(rows); w.jpos = b.take<int32_t>(rows); w.jlk = b.take<int32_t>(rows);
+        }
     } else {
         w.unfinished = b.take<int32_t>(rows); w.last_step = b.take<int32_t>(4);
     }
@@ -1720,7 +1729,7 @@ static int decode_K(const ortk_decode_opts* o) {
 // Which executor serves a decode call.  Train-mode rows (ortk_decode_opts.train) run on the column-split stack kernel with at least 4
 // workgroups per group (its dropout sites, ortk_decstack.hip) or on the unfused executor; eval-mode (greedy) rows beside them
 // (`with_greedy`) only on the former.  ok = false: the option combination is not served (ORTK_EINVAL).
-struct DecodePlan { bool ok, stack, sstream; int split; bool gather = false; bool fp8 = false; };
+struct DecodePlan { bool ok, stack, sstream; int split; bool gather = false; bool fp8 = false; bool joint = false; };
 // diverse beam groups (ortk_decode_opts.group_size): the number of groups G (1: the plain decode), or -1 for a refused combination
 static int decode_groups(const ortk_decode_opts* o) {
     if (o->group_size < 0) return -1;
@@ -1733,6 +1742,9 @@ static int decode_groups(const ortk_decode_opts* o) {
 static DecodePlan plan_decode(const ortk_config& cfg, int B, int K, const ortk_decode_opts* o) {
     DecodePlan p{true, false, false, 0};
     const int64_t rows = (int64_t)B * K;
+    // the joint diverse executor is the unfused executor's: grouped beam decodes only, in eval mode
+    p.joint = (o->exec_flags & ORTK_DEC_GROUPS_JOINT) != 0;
+    if (p.joint && (o->group_size <= 1 || o->train || o->num_random_sample > 0)) { p.ok = false; return p; }
     if (o->group_size > 1) {
         // every group's decoder pass is a launch sequence of the unfused executor at its own position; an executor of the stack
         // family that the caller named is refused, not replaced (ORTK_DEC_SPLIT_SMALL alone is still the automatic choice)
@@ -1769,7 +1781,7 @@ extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B,
     const DecodePlan pl = plan_decode(*cfg, B, K, o);
     if (!pl.ok) return 0;
     DecodeWS w; carve_decode(*cfg, B, S, K / G, o->num_random_sample <= 0 && o->beam_size > 1, nullptr, w, pl.stack, pl.sstream, o->train != 0,
-                             pl.split, o->with_greedy != 0, pl.fp8, G);
+                             pl.split, o->with_greedy != 0, pl.fp8, G, pl.joint);
     return w.bytes;
 }
 
@@ -1813,8 +1825,13 @@ static int gen_gemm(const Ctx& c, const Offsets& o, const StepBufs& w, int ydt, 
     }
     return ortk_gemm(&a, (ortk_stream)c.s);
 }
+// jp (the joint diverse executor, eval mode): `rows` holds jp->G blocks of groups x per_group rows, each block at a position of its
+// own — the per-row arrays of joint_rows give every row its token and position, its key count and its ancestry entries (kvidx: the
+// first of the two ancestry tables; idle blocks: position 0, no keys); t is not read.  Cross-attention stays one call per block and
+// layer, for the active blocks g_lo .. g_hi alone (an idle block keeps the zero rows its self-attention wrote).
+struct JointPass { const int64_t* tok_tab; const int32_t* row_pos; const int32_t* lk_row; const int64_t* kv_off; int G, g_lo, g_hi; };
 static int decoder_step(const Ctx& c, const Offsets& o, const StepBufs& w, int64_t rows, int groups, int per_group, int /*row_mult*/,
-                        int S, int T, int t, const int32_t* kvidx) {
+                        int S, int T, int t, const int32_t* kvidx, const JointPass* jp = nullptr) {
     const ortk_config* cfg = c.cfg;
     const float* P = c.P;
     ortk_stream stream = (ortk_stream)c.s;
@@ -1827,7 +1844,12 @@ static int decoder_step(const Ctx& c, const Offsets& o, const StepBufs& w, int64
         // (rows x T, N) teacher-forced tensors (cd.drop_rs / drop_r0; ortk_attn_args.drop_tf_*).  pd = 0 in eval mode.
         Ctx cd = c; cd.drop_rs = T; cd.drop_r0 = t;
         const float pd = c.p_drop();
-        TRY(embed_fwd_rows(w.it, 1, P + o.lut, P + o.pe, w.xa, nullptr, rows, nullptr, 1, t, d, cfg->pad_id, pd, c.sub(OP_EMB), c.s, T, t));
+        if (jp) {
+            if (pd > 0.f || !kvidx) return ORTK_EINVAL;
+            TRY(embed_fwd_rows(jp->tok_tab, T, P + o.lut, P + o.pe, w.xa, nullptr, rows, jp->row_pos, T, 0, d, cfg->pad_id, 0.f, c.sub(OP_EMB), c.s));
+        } else {
+            TRY(embed_fwd_rows(w.it, 1, P + o.lut, P + o.pe, w.xa, nullptr, rows, nullptr, 1, t, d, cfg->pad_id, pd, c.sub(OP_EMB), c.s, T, t));
+        }
         float* x = w.xa; float* xn = w.xb;
         for (int l = 0; l < L; ++l) {
             const DecOff& e = o.dec[l];
@@ -1837,7 +1859,8 @@ static int decoder_step(const Ctx& c, const Offsets& o, const StepBufs& w, int64
             a.k_new = w.qkv + am.k * d; a.v_new = w.qkv + am.v * d; a.ld_new = 3 * d;    // this position's K / V join the cache inside the kernel
             a.q = w.qkv; a.ldq = 3 * d; a.k = reinterpret_cast<const float*>(w.cache_k[l]); a.v = reinterpret_cast<const float*>(w.cache_v[l]);
             a.kv_dtype = w.kvdt; a.ldk = a.ldv = d; a.o = w.o; a.o_dtype = A; a.ldo = d;
-            a.nkv = (int)rows; a.H = H; a.Lq = 1; a.Lk = t + 1; a.dk = dk;
+            a.nkv = (int)rows; a.H = H; a.Lq = 1; a.Lk = jp ? T : t + 1; a.dk = dk;      // (joint: ONE upper bound for every step, so one kernel instance)
+            if (jp) { a.lk_row = jp->lk_row; a.kv_index_off = jp->kv_off; }
             if (kvidx) a.kv_index = kvidx; else a.kv_group_stride = T;
             if (pd > 0.f) { a.drop_p = pd; a.drop_seed = c.sub(dop(l, 0)); a.drop_tf_T = T; a.drop_tf_t = t; a.drop_tf_lk = T; }
             TRY(ortk_attention_fwd(&a, stream));
@@ -1852,7 +1875,16 @@ static int decoder_step(const Ctx& c, const Offsets& o, const StepBufs& w, int64
             a.ldk = a.ldv = o.ckv_slots * o.cw;
             a.o = w.o; a.o_dtype = A; a.ldo = d; a.kmask = att_masks; a.nkv = B; a.H = H; a.Lq = per_img; a.Lk = S; a.dk = dk;
             if (pd > 0.f) { a.drop_p = pd; a.drop_seed = c.sub(dop(l, 2)); a.drop_tf_T = T; a.drop_tf_t = t; a.drop_tf_lk = S; }
-            TRY(ortk_attention_fwd(&a, stream));
+            if (jp) {
+                const int64_t blk = (int64_t)B * per_img * d;       // elements of one block's rows
+                for (int g = jp->g_lo; g <= jp->g_hi; ++g) {
+                    ortk_attn_args ag = a;
+                    ag.q = reinterpret_cast<const float*>(off_elems(w.q, g * blk, w.xq16 ? ORTK_BF16 : ORTK_F32)); ag.o = off_elems(w.o, g * blk, A);
+                    TRY(ortk_attention_fwd(&ag, stream));
+                }
+            } else {
+                TRY(ortk_attention_fwd(&a, stream));
+            }
             TRY(fwd_gemm(cd, w.o, A, d, e.cow, P + e.cob, xn, ORTK_F32, d, rows, d, d, false, pd, c.sub(dop(l, 3)), x, d));
             std::swap(x, xn);
             TRY(ln_fwd(c, x, e.n2a, e.n2b, w.y, A, w.st, rows));
@@ -1971,6 +2003,75 @@ static int decode_diverse(const Ctx& c, const Offsets& o, const DecodeWS& w, con
     return 0;
 }
 
+// The joint diverse executor (ORTK_DEC_GROUPS_JOINT): decode_diverse's schedule and results with one decoder pass per GLOBAL step.
+// A group's pass reads only its own tokens, caches and ancestry table, so the passes of all groups of a global step are one launch
+// sequence over the G blocks of B * bd rows (group-major, as carved), every block at its own position t = Tg - g; only the selection of
+// group g needs the groups before it, and one launch walks them in order (beam_step_diverse_joint).  All G blocks run in EVERY global
+// step — the operators then see one row count for the whole decode and a row gets the same bits whichever step it is computed in (at
+// lambda = 0 every group reproduces group 0) — with the blocks that have not started (t < 1) or have finished (t > T - 1) idle: a valid
+// token (BOS from the start, then the group's last tokens) at position 0, no keys, no cache row or table entry touched, their outputs
+// never read.  Position 0 of a group stays the separate B-row pass (one row per image, transformer.py:488; same launches and bits for
+// every group) into logit rows of its own.  The ancestry tables number the cache rows over ALL groups' caches.  No host-to-device copy
+// and no synchronisation: a small kernel derives the per-row arrays from Tg.  Memory: every index is bounded by the carving for any
+// (B, bd, G, T), G > T included — the windows of active groups are computed here and in the kernels from Tg alone.
+static int decode_diverse_joint(const Ctx& c, const Offsets& o, const DecodeWS& w, const ortk_decode_opts* op, const float* att_masks, int B, int S,
+                                int bd, int G, int64_t* seq_out, float* logprob_out, float* score_out) {
+    const ortk_config* cfg = c.cfg;
+    hipStream_t s = c.s;
+    const int d = cfg->d_model, L = cfg->n_layers, V = cfg->vocab, T = cfg->seq_len, A = w.adt;
+    const int64_t grows = (int64_t)B * bd, rows_all = grows * G;
+    if (!w.logits0 || !w.jtok || c.train) return ORTK_EINVAL;
+    BeamState st0; std::memset(&st0, 0, sizeof(st0));
+    st0.B = B; st0.b = bd; st0.L = T; st0.V = V; st0.eos = cfg->eos_id; st0.ldv = w.ldv;
+    for (int i = 0; i < 2; ++i) { st0.seq[i] = w.bseq[i]; st0.tok_lp[i] = w.blp[i]; st0.kvidx[i] = w.kvidx[i]; }
+    st0.cum = w.cum; st0.it = w.it; st0.done_seq = w.done_seq; st0.done_lp = w.done_lp; st0.done_p = w.done_p; st0.done_len = w.done_len;
+    st0.done_cnt = w.done_cnt;
+    st0.decoding_constraint = op->decoding_constraint; st0.length_penalty = op->length_penalty; st0.length_alpha = op->length_alpha; st0.tmax = T;
+    const bool stats = w.gstats && w.gstats0 && op->temperature == 1.f && !op->sparse && A == ORTK_BF16 && d % 64 == 0 && w.ldv % 128 == 0 && w.ldv / 64 <= 256;
+    if (stats) { st0.gstats = w.gstats; st0.nblk = (int32_t)(w.ldv / 64); }      // (the plain beam search's condition, as decode_diverse)
+    JointGroups jg; std::memset(&jg, 0, sizeof(jg));
+    jg.G = G; jg.rows = grows; jg.logp = w.logits; jg.logp0 = w.logits0;
+    if (stats) { jg.gstats = w.gstats; jg.gstats0 = w.gstats0; }
+    TRY(fill_i64(w.it, rows_all, cfg->bos_id, s));               // every row holds a valid token from the first pass on
+    TRY(joint_kvidx_init(w.kvidx[0], grows, B, bd, G, T, s));
+    TRY(fill_i32(w.done_cnt, (int64_t)B * G, 0, s));
+    const bool fast_exp = cfg->precision == 1;
+    StepBufs sb{w.it, w.xa, w.xb, w.y, w.qkv, w.o, w.q, w.h, w.logits, w.st, w.ldv, w.ckv, att_masks};
+    sb.kvdt = w.kvdt; sb.ckvdt = w.ckvdt; sb.xq16 = w.xq16;
+    if (stats) { sb.gstats = w.gstats; sb.stat_ncols = V; }
+    for (int l = 0; l < L; ++l) { sb.cache_k[l] = w.cache_k[l]; sb.cache_v[l] = w.cache_v[l]; }
+    for (int Tg = 0; Tg < T + G - 1; ++Tg) {
+        // blocks at a position 1 .. T - 1: g = Tg - t
+        const int g_lo = std::max(0, Tg - (T - 1)), g_hi = std::min(G - 1, Tg - 1);
+        if (g_lo <= g_hi) {
+            TRY(joint_rows(w.it, w.jtok, w.jpos, w.jlk, w.jkvoff, grows, G, T, Tg, w.kvidx[1] - w.kvidx[0], s));
+            const JointPass jp{w.jtok, w.jpos, w.jlk, w.jkvoff, G, g_lo, g_hi};
+            TRY(decoder_step(c, o, sb, rows_all, B, bd, 1, S, T, 0, w.kvidx[0], &jp));
+        }
+        if (Tg < G) {      // group Tg starts: its position-0 pass, B rows on the block's first tokens and cache slots
+            StepBufs s0 = sb;
+            s0.it = w.it + Tg * grows; s0.logits = w.logits0;
+            if (stats) s0.gstats = w.gstats0;
+            TRY(decoder_step(c, o, s0, B, B, 1, bd, S, T, 0, w.kvidx[0] + Tg * grows * (T + 1)));
+        }
+        TRY(beam_step_diverse_joint(st0, jg, Tg, s, 1.f / op->temperature, fast_exp, op->diversity_lambda));
+    }
+    // seq_out[n, g * bd + q]: each group's stable top-bd of its finished list, as decode_diverse copies them
+    const size_t b_all = (size_t)bd * G;
+    for (int g = 0; g < G; ++g) {
+        BeamState st = st0;
+        st.done_seq += g * grows * T * T; st.done_lp += g * grows * T * T; st.done_p += g * grows * T; st.done_len += g * grows * T; st.done_cnt += (int64_t)g * B;
+        TRY(beam_finalize(st, w.fin_seq, w.fin_lp, score_out ? w.fin_score : nullptr, s));
+        if (hipMemcpy2DAsync(seq_out + (size_t)g * bd * T, b_all * T * sizeof(int64_t), w.fin_seq, (size_t)bd * T * sizeof(int64_t),
+                             (size_t)bd * T * sizeof(int64_t), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+        if (hipMemcpy2DAsync(logprob_out + (size_t)g * bd * T, b_all * T * sizeof(float), w.fin_lp, (size_t)bd * T * sizeof(float),
+                             (size_t)bd * T * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+        if (score_out && hipMemcpy2DAsync(score_out + (size_t)g * bd, b_all * sizeof(float), w.fin_score, (size_t)bd * sizeof(float),
+                                          (size_t)bd * sizeof(float), (size_t)B, hipMemcpyDeviceToDevice, s) != hipSuccess) return ORTK_EINVAL;
+    }
+    return 0;
+}
+
 extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
                            const float* att_masks, int32_t B, int32_t S, const ortk_decode_opts* op, void* ws, size_t ws_bytes,
                            int64_t* seq_out, float* logprob_out, float* score_out, ortk_stream stream) {
@@ -1998,7 +2099,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     const int split = pl.split;
     const bool greedy_rows = op->train && op->with_greedy;         // (=> stack)
     if (greedy_rows && (!att_feats || (!boxes && !cfg->no_box))) return ORTK_EINVAL;      // their eval-mode encoder pass runs here
-    DecodeWS w; carve_decode(*cfg, B, S, K / G, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows, pl.fp8, G);
+    DecodeWS w; carve_decode(*cfg, B, S, K / G, beam, ws, w, stack, sstream, op->train != 0, split, greedy_rows, pl.fp8, G, pl.joint);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
     hipStream_t s = ortk_s(stream);
     TRY(fill_i32(w.status, 64, 0, s));
@@ -2074,6 +2175,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     c.use_side = false;
     TRY(fwd_gemm(c, op->memory ? op->memory : w.mem, A, d, o.ckv_w, P + o.ckv_b, w.ckv, w.ckvdt, o.ckv_slots * o.cw, Me, (int)(o.ckv_slots * o.cw), d));
 
+    if (G > 1 && pl.joint) return decode_diverse_joint(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out);
     if (G > 1) return decode_diverse(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out);
     const int64_t rows_full = (int64_t)B * K;
     BeamState bs; std::memset(&bs, 0, sizeof(bs));

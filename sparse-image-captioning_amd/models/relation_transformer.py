@@ -580,6 +580,15 @@ class RelationTransformerModel(CaptionModelBase):
         o.diversity_lambda = float(opt.get("diversity_lambda", 0.5))
         if o.group_size < 1:
             raise ValueError(f"group_size={o.group_size}: expected an integer >= 1")
+        if opt.get("executor") == "unfused_joint":
+            # the joint diverse executor (ortk.h: ORTK_DEC_GROUPS_JOINT): all groups of a global step in one decoder pass; opt-in only
+            if o.num_random_sample > 0:
+                raise ValueError('executor="unfused_joint" decodes diverse beam groups: it does not serve num_random_sample > 0')
+            if opt.get("train_mode", False):
+                raise ValueError('executor="unfused_joint" decodes diverse beam groups: it does not serve train_mode')
+            if o.group_size <= 1:
+                raise ValueError(f'executor="unfused_joint" needs group_size > 1 (saw {o.group_size}): it joins the decoder passes of '
+                                 'the groups of a diverse beam search; a plain beam search has one')
         if o.group_size > 1:
             if o.num_random_sample > 0 or opt.get("train_mode", False):
                 raise ValueError(f"group_size={o.group_size}: diverse groups belong to beam decodes (num_random_sample <= 0, no train_mode)")
@@ -618,14 +627,15 @@ class RelationTransformerModel(CaptionModelBase):
                 raise ValueError(f"beam_size={o.beam_size}: the beam search serves at most ORTK_MAX_BEAM = {L.MAX_BEAM} beams "
                                  "(include/ortk.h)")
             K = o.beam_size
-        # executor choice (ortk_decode_opts.exec_flags): opt["executor"] = "auto" | "unfused" | "stack" | "sparse_stream" | "stack_fp8" ..;
+        # executor choice (ortk_decode_opts.exec_flags): opt["executor"] = "auto" | "unfused" | "unfused_joint" | "stack" | "sparse_stream" | "stack_fp8" ..;
         # "stack_fp8" (the stack kernel on FP8-quantised decoder weights, fp8_dequantized_decoder_state) is opt-in only: never "auto"
         # ORTK_DEC_STACK=0 / 2 in the environment (read here, on the host side, per call) = "unfused" / "stack"
         ex = opt.get("executor", {"0": "unfused", "2": "stack", "3": "stack_split"}.get(os.environ.get("ORTK_DEC_STACK", ""), "auto"))
         if o.group_size > 1:
-            # every group's decoder pass is a launch sequence of the unfused executor at the group's own position: "auto" resolves
-            # to it, a stack-family executor the caller named is refused
-            if ex not in ("auto", "unfused"):
+            # every group's decoder pass is a launch sequence of the unfused executor at the group's own position (or, opt-in, all
+            # groups of a step one sequence: "unfused_joint"): "auto" resolves to the former, a stack-family executor the caller named
+            # is refused
+            if ex not in ("auto", "unfused", "unfused_joint"):
                 raise ValueError(f'executor="{ex}" does not serve group_size={o.group_size}: diverse beam groups decode at different '
                                  'positions, the stack kernels take one position per launch; use "auto" or "unfused"')
         elif ex == "auto" and getattr(self, "_sparse_stream", False):
@@ -634,7 +644,8 @@ class RelationTransformerModel(CaptionModelBase):
         # this GPU at the same time: its workgroups spin on each other and must all be resident (ortk.h: ORTK_DEC_SPLIT_SMALL).
         # `model.exclusive_gpu = False` (two processes on one device) or decode_streams > 1 switch that off.
         small = L.DEC_SPLIT_SMALL if (getattr(self, "exclusive_gpu", True) and int(opt.get("decode_streams", 0) or 1) <= 1) else 0
-        o.exec_flags = {"auto": small, "unfused": L.DEC_UNFUSED, "stack": L.DEC_STACK, "sparse_stream": L.DEC_SPARSE_STREAM,
+        o.exec_flags = {"auto": small, "unfused": L.DEC_UNFUSED, "unfused_joint": L.DEC_UNFUSED | L.DEC_GROUPS_JOINT,
+                        "stack": L.DEC_STACK, "sparse_stream": L.DEC_SPARSE_STREAM,
                         "stack_rb20": L.DEC_STACK | L.DEC_STACK_RB20, "stack_split": L.DEC_STACK | L.DEC_STACK_SPLIT,
                         "sparse_stream_rb20": L.DEC_SPARSE_STREAM | L.DEC_STACK_RB20,
                         "sparse_gather": L.DEC_SPARSE_STREAM | L.DEC_SPARSE_GATHER,
@@ -709,7 +720,7 @@ class RelationTransformerModel(CaptionModelBase):
         greedy baseline as eval-mode rows of the same launches: the column-split stack kernel only).  No device work."""
         if int(opt.get("num_random_sample", 0)) <= 0 and int(opt.get("beam_size", 1)) > L.MAX_BEAM:
             return False                                                     # (the decode itself raises ValueError: _decode_opts)
-        if int(opt.get("group_size", 1)) != 1:
+        if int(opt.get("group_size", 1)) != 1 or opt.get("executor") == "unfused_joint":
             try:                                                             # (likewise: a refused group option or executor)
                 self._decode_opts(dict(opt, seed=opt.get("seed", 0)))
             except ValueError:
