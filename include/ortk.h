@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 18   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 19   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
@@ -309,6 +309,12 @@ typedef struct ortk_chain_args {
 } ortk_chain_args;
 size_t ortk_chain_packed_bytes(int32_t n_units);
 int ortk_row_chain(const ortk_chain_args* a, ortk_stream stream);
+/* How ortk_row_chain(a) would launch: launches nothing, needs no device, returns the code ortk_row_chain would return for these arguments
+ * (ORTK_EINVAL included) and on success writes (each pointer may be NULL) form = 0 the 48-row kernel | 1 the 76-row kernel
+ * (ortk_tuning.chain_wide), rows_per_block = the rows a compute workgroup owns (the last one may own fewer), workgroups = the compute
+ * workgroups, prefetchers = the L2 prefetcher workgroups at the head of the grid (8 with `progress`, else 0).  Built by the code that
+ * builds the launch itself, under the ortk_tuning values of the moment; pointers are tested for NULL only, never dereferenced. */
+int ortk_row_chain_plan(const ortk_chain_args* a, int32_t* form, int32_t* rows_per_block, int32_t* workgroups, int32_t* prefetchers);
 
 /* The backward counterpart: everything between two attention-backward calls except the weight gradients (which reduce over all
  * rows and stay GEMMs), through the TRANSPOSED bf16 weight copies `w16t` (block (N, K) of the arena stored (K, N) at the same offset):
@@ -336,6 +342,8 @@ typedef struct ortk_bchain_args {
     const int32_t* drop_rows;   /* optional (M ints): the masked copies dza / dzb / dz0 draw row m as row drop_rows[m] (see ortk_gemm_args) */
 } ortk_bchain_args;
 int ortk_row_bchain(const ortk_bchain_args* a, ortk_stream stream);
+/* As ortk_row_chain_plan, for ortk_row_bchain (one kernel form: up to 48 rows per workgroup, rounds of 256 workgroups). */
+int ortk_row_bchain_plan(const ortk_bchain_args* a, int32_t* rows_per_block, int32_t* workgroups);
 
 /* Process-wide A/B switches for measurements (the scripts under scratch/); the defaults are the product path and nothing in the library reads the
  * environment.  Not thread-safe against running calls: set them before the work starts. */

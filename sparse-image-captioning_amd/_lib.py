@@ -212,6 +212,8 @@ SIGNATURES = {
     "ortk_chain_packed_bytes": (_SZ, [_I32]),
     "ortk_row_chain": (_I32, [C.POINTER(ChainArgs), _P]),
     "ortk_row_bchain": (_I32, [C.POINTER(BChainArgs), _P]),
+    "ortk_row_chain_plan": (_I32, [C.POINTER(ChainArgs), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),
+    "ortk_row_bchain_plan": (_I32, [C.POINTER(BChainArgs), C.POINTER(_I32), C.POINTER(_I32)]),
     "ortk_get_tuning": (None, [C.POINTER(Tuning)]),
     "ortk_set_tuning": (_I32, [C.POINTER(Tuning)]),
     "ortk_gemm": (_I32, [C.POINTER(GemmArgs), _P]),
@@ -282,7 +284,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 18   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 19   # include/ortk.h: ORTK_VERSION
 
 
 def lib():
@@ -325,6 +327,22 @@ def gemm_plan(args):
     buf = C.create_string_buffer(256)
     check(lib().ortk_gemm_plan(C.byref(args), buf, len(buf)), "ortk_gemm_plan")
     return [k for k in buf.value.decode().split(";") if k]
+
+
+def row_chain_plan(args):
+    """How ortk_row_chain(args) would launch: {"form": 0 the 48-row kernel | 1 the 76-row kernel, "rows_per_block", "workgroups" (compute),
+    "prefetchers"} (include/ortk.h: ortk_row_chain_plan); raises OrtkError where the operator would refuse the arguments.  Launches nothing
+    and needs no device."""
+    v = [C.c_int32() for _ in range(4)]
+    check(lib().ortk_row_chain_plan(C.byref(args), *[C.byref(x) for x in v]), "ortk_row_chain_plan")
+    return dict(zip(("form", "rows_per_block", "workgroups", "prefetchers"), (x.value for x in v)))
+
+
+def row_bchain_plan(args):
+    """{"rows_per_block", "workgroups"} of ortk_row_bchain(args) (include/ortk.h: ortk_row_bchain_plan); raises OrtkError on a refusal."""
+    v = [C.c_int32() for _ in range(2)]
+    check(lib().ortk_row_bchain_plan(C.byref(args), *[C.byref(x) for x in v]), "ortk_row_bchain_plan")
+    return dict(zip(("rows_per_block", "workgroups"), (x.value for x in v)))
 
 
 def attention_plan(args, bwd=False):

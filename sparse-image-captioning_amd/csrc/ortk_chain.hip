@@ -994,8 +994,11 @@ int chain_pack_all(const void* w16, void* packed, const ChainPackTable& t, hipSt
     return 0;
 }
 
-int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
-    if (!p || !packed || !p->x_in || p->M < 1 || p->M > (int64_t)1 << 22) return ORTK_EINVAL;
+// Everything the launch of a forward chain is decided from: the argument checks, the kernel form, the block height and the grid.  Launches
+// nothing and needs no device: chain_run and ortk_row_chain_plan both go through it, so the plan cannot drift from the launch.
+struct ChainGeom { bool wide; int n_units, rb, npf, slots; unsigned grid; };
+static int chain_geom(const ortk_chain_args* p, ChainGeom& g) {
+    if (!p || !p->x_in || p->M < 1 || p->M > (int64_t)1 << 22) return ORTK_EINVAL;
     if (p->n1 < 0 || p->n1 > 3 || p->n2 < 0 || p->n2 > 3 || p->NC < 0 || p->NC > 8) return ORTK_EINVAL;
     if ((p->n1 > 0 && !p->g1) || (p->n2 > 0 && !p->g2)) return ORTK_EINVAL;
     if (p->a_in && (!p->bias_r || !p->x_mid)) return ORTK_EINVAL;
@@ -1003,9 +1006,27 @@ int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
     if (p->n2 > 0 && (!p->bias_s2 || !p->out2 || p->ld2 < p->n2 * CD || p->ld2 % 4)) return ORTK_EINVAL;
     if (p->NC > 0 && (!p->g1 || !p->bias_h || !p->bias_o || !p->x_out)) return ORTK_EINVAL;      // (h NULL: inference, the hidden units are not kept)
     if (p->drop_p < 0.f || p->drop_p >= 1.f) return ORTK_EINVAL;
-    const int n_units = (p->a_in ? 1 : 0) + p->n1 + 2 * p->NC + p->n2;
-    if (n_units < 1 || n_units != p->n_units) return ORTK_EINVAL;
+    g.n_units = (p->a_in ? 1 : 0) + p->n1 + 2 * p->NC + p->n2;
+    if (g.n_units < 1 || g.n_units != p->n_units) return ORTK_EINVAL;
     if ((int64_t)p->M * std::max(p->NC, 1) * CD >= ((int64_t)1 << 32)) return ORTK_EINVAL;       // 32-bit dropout element indices
+    g.wide = !p->progress && chain_wide(p->M);      // (the caller packed the stream for the same rule)
+    // with a progress array the grid starts with 8 L2 prefetcher workgroups (one per XCD): 248 compute workgroups per round
+    g.npf = p->progress ? 8 : 0; g.slots = 256 - g.npf;
+    g.rb = chain_rows_per_block(p->M, g.slots);
+    if (g.wide) g.rb = (int)std::min<int64_t>(WRB, ortk_cdiv(p->M, ortk_cdiv(ortk_cdiv(p->M, (int64_t)WRB), 256) * 256));
+    g.grid = (unsigned)(ortk_cdiv(p->M, g.rb) + g.npf);
+    return 0;
+}
+// what the operator form asks of its own arguments ahead of chain_geom / bchain_geom
+template <class Args> static int chain_op_check(const Args* p, const void* w) {
+    return (!p || !w || !p->units_dev || !p->packed || p->packed_bytes < chain_packed_bytes(p->n_units)) ? ORTK_EINVAL : 0;
+}
+
+int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
+    if (!packed) return ORTK_EINVAL;
+    ChainGeom geo;
+    if (int e = chain_geom(p, geo)) return e;
+    const int n_units = geo.n_units;
     static std::mutex mu;
     static bool done[64] = {};
     int dev = 0;
@@ -1019,14 +1040,12 @@ int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
             done[dev] = true;
         }
     }
-    const bool wide = !p->progress && chain_wide(p->M);      // (the caller packed the stream for the same rule)
+    const bool wide = geo.wide;
     ChainArgs a;
     a.wpk = reinterpret_cast<const uint4*>(packed); a.n_units = n_units;
-    // with a progress array the grid starts with 8 L2 prefetcher workgroups (one per XCD): 248 compute workgroups per round
-    a.progress = p->progress; a.npf = p->progress ? 8 : 0; a.slots = 256 - a.npf;
+    a.progress = p->progress; a.npf = geo.npf; a.slots = geo.slots;
     if (p->progress && hipMemsetAsync(p->progress, 0, 16 * sizeof(int32_t), s) != hipSuccess) return ORTK_EINVAL;
-    a.M = (int)p->M; a.rb = chain_rows_per_block(p->M, a.slots);
-    if (wide) a.rb = (int)std::min<int64_t>(WRB, ortk_cdiv(p->M, ortk_cdiv(ortk_cdiv(p->M, (int64_t)WRB), 256) * 256));
+    a.M = (int)p->M; a.rb = geo.rb;
     a.x_in = p->x_in;
     a.a_in = reinterpret_cast<const __bf16*>(p->a_in); a.bias_r = p->bias_r; a.x_mid = p->x_mid; a.seed_r = p->seed_r;
     a.g1 = p->g1; a.b1 = p->b1; a.y1 = reinterpret_cast<__bf16*>(p->y1); a.st1 = p->st1;
@@ -1036,7 +1055,7 @@ int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
     a.g2 = p->g2; a.b2 = p->b2; a.y2 = reinterpret_cast<__bf16*>(p->y2); a.st2 = p->st2;
     a.n2 = p->n2; a.bias_s2 = p->bias_s2; a.out2 = reinterpret_cast<__bf16*>(p->out2); a.ld2 = (int)p->ld2;
     a.drop_p = p->drop_p; a.eps = p->eps; a.drop_rows = p->drop_rows;
-    const unsigned grid = (unsigned)(ortk_cdiv(p->M, a.rb) + a.npf);
+    const unsigned grid = geo.grid;
     ProfMark pm;
     if (ortk_prof_active()) {
         // algorithmic HBM bytes: the weights once + every row tensor the chain reads or writes
@@ -1051,8 +1070,9 @@ int chain_run(const ortk_chain_args* p, const void* packed, hipStream_t s) {
     return 0;
 }
 
-int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
-    if (!p || !packed || p->M < 1 || p->M > (int64_t)1 << 22) return ORTK_EINVAL;
+struct BChainGeom { int n_units, rb; unsigned grid; };
+static int bchain_geom(const ortk_bchain_args* p, BChainGeom& g) {
+    if (!p || p->M < 1 || p->M > (int64_t)1 << 22) return ORTK_EINVAL;
     if ((p->nin != 0 && p->nin != 1 && p->nin != 3) || p->NC < 0 || p->NC > 8 || p->n2 < 0 || p->n2 > 1) return ORTK_EINVAL;
     if (p->nin > 0 && (!p->ain || p->ld_ain < p->nin * CD || p->ld_ain % 8 || !p->xa || !p->sta || !p->ga || !p->dxa || !p->daa || !p->dba)) return ORTK_EINVAL;
     if (p->nin == 0 && !p->dz0) return ORTK_EINVAL;
@@ -1061,9 +1081,19 @@ int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
     if ((p->NC > 0 || p->n2 > 0) && p->nin > 0 && !p->mask_a) return ORTK_EINVAL;       // P1 / P2 read the masked image LNa leaves
     if (p->n2 > 0 && p->NC > 0 && !p->mask_b) return ORTK_EINVAL;
     if (p->drop_p < 0.f || p->drop_p >= 1.f) return ORTK_EINVAL;
-    const int n_units = p->nin + 2 * p->NC + p->n2;
-    if (n_units < 1 || n_units != p->n_units) return ORTK_EINVAL;
+    g.n_units = p->nin + 2 * p->NC + p->n2;
+    if (g.n_units < 1 || g.n_units != p->n_units) return ORTK_EINVAL;
     if ((int64_t)p->M * CD >= ((int64_t)1 << 32)) return ORTK_EINVAL;
+    g.rb = chain_rows_per_block(p->M, 256);
+    g.grid = (unsigned)ortk_cdiv(p->M, g.rb);
+    return 0;
+}
+
+int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
+    if (!packed) return ORTK_EINVAL;
+    BChainGeom geo;
+    if (int e = bchain_geom(p, geo)) return e;
+    const int n_units = geo.n_units;
     static std::mutex mu;
     static bool done[64] = {};
     int dev = 0;
@@ -1077,7 +1107,7 @@ int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
         }
     }
     BChainArgs a;
-    a.wpk = reinterpret_cast<const uint4*>(packed); a.n_units = n_units; a.M = (int)p->M; a.rb = chain_rows_per_block(p->M, 256);
+    a.wpk = reinterpret_cast<const uint4*>(packed); a.n_units = n_units; a.M = (int)p->M; a.rb = geo.rb;
     a.nin = p->nin; a.ain = reinterpret_cast<const __bf16*>(p->ain); a.ld_ain = (int)p->ld_ain; a.dz0 = reinterpret_cast<const __bf16*>(p->dz0);
     a.xa = p->xa; a.sta = p->sta; a.ga = p->ga; a.dresa = p->dresa; a.dxa = p->dxa; a.daa = p->daa; a.dba = p->dba;
     a.dza = reinterpret_cast<__bf16*>(p->dza); a.seed_a = p->seed_a; a.mask_a = p->mask_a;
@@ -1088,7 +1118,7 @@ int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
     a.drop_p = p->drop_p; a.eps = p->eps; a.drop_rows = p->drop_rows;
     ProfMark pm;
     if (ortk_prof_active()) (void)prof_begin(PROF_KEY_CHAIN, 2.0 * p->M * n_units * CD * CD, (double)n_units * CD * CD * 2, s, pm); else pm.live = false;
-    hipLaunchKernelGGL(row_bchain_kernel, dim3((unsigned)ortk_cdiv(p->M, a.rb)), dim3(512), CHAIN_LDS, s, a);
+    hipLaunchKernelGGL(row_bchain_kernel, dim3(geo.grid), dim3(512), CHAIN_LDS, s, a);
     prof_end(pm, s);
     ORTK_CHECK_LAUNCH();
     return 0;
@@ -1098,19 +1128,40 @@ int bchain_run(const ortk_bchain_args* p, const void* packed, hipStream_t s) {
 
 // Operator form of the backward chain (tests, tools): packs the units of this call from `w16t` into `packed`, then runs it.
 extern "C" int ortk_row_bchain(const ortk_bchain_args* p, ortk_stream stream) {
-    if (!p || !p->w16t || !p->units_dev || !p->packed || p->packed_bytes < ortk::chain_packed_bytes(p->n_units)) return ORTK_EINVAL;
+    if (int e = ortk::chain_op_check(p, p ? p->w16t : nullptr)) return e;
     hipStream_t s = ortk_s(stream);
     if (int e = ortk::chain_pack(p->w16t, p->units_dev, p->n_units, p->packed, s)) return e;
     return ortk::bchain_run(p, p->packed, s);
+}
+
+extern "C" int ortk_row_bchain_plan(const ortk_bchain_args* p, int32_t* rows_per_block, int32_t* workgroups) {
+    if (int e = ortk::chain_op_check(p, p ? p->w16t : nullptr)) return e;
+    ortk::BChainGeom g;
+    if (int e = ortk::bchain_geom(p, g)) return e;
+    if (rows_per_block) *rows_per_block = g.rb;
+    if (workgroups) *workgroups = (int32_t)g.grid;
+    return 0;
 }
 
 extern "C" size_t ortk_chain_packed_bytes(int32_t n_units) { return n_units < 1 ? 0 : ortk::chain_packed_bytes(n_units); }
 
 // Operator form (tests, tools): packs the units of this call from `w16` into `packed`, then runs the chain.
 extern "C" int ortk_row_chain(const ortk_chain_args* p, ortk_stream stream) {
-    if (!p || !p->w16 || !p->units_dev || !p->packed || p->packed_bytes < ortk::chain_packed_bytes(p->n_units)) return ORTK_EINVAL;
+    if (int e = ortk::chain_op_check(p, p ? p->w16 : nullptr)) return e;
+    ortk::ChainGeom g;
+    if (int e = ortk::chain_geom(p, g)) return e;          // (the stream is packed for the form the launch will take)
     hipStream_t s = ortk_s(stream);
-    const bool wide = !p->progress && ortk::chain_wide(p->M);
-    if (int e = ortk::chain_pack(p->w16, p->units_dev, p->n_units, p->packed, s, wide, p->a_in ? 1 : 0, p->n1, p->NC)) return e;
+    if (int e = ortk::chain_pack(p->w16, p->units_dev, p->n_units, p->packed, s, g.wide, p->a_in ? 1 : 0, p->n1, p->NC)) return e;
     return ortk::chain_run(p, p->packed, s);
+}
+
+extern "C" int ortk_row_chain_plan(const ortk_chain_args* p, int32_t* form, int32_t* rows_per_block, int32_t* workgroups, int32_t* prefetchers) {
+    if (int e = ortk::chain_op_check(p, p ? p->w16 : nullptr)) return e;
+    ortk::ChainGeom g;
+    if (int e = ortk::chain_geom(p, g)) return e;
+    if (form) *form = g.wide ? 1 : 0;
+    if (rows_per_block) *rows_per_block = g.rb;
+    if (workgroups) *workgroups = (int32_t)(g.grid - g.npf);
+    if (prefetchers) *prefetchers = g.npf;
+    return 0;
 }
