@@ -24,11 +24,12 @@
 extern "C" {
 #endif
 
-#define ORTK_VERSION 19   /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
+#define ORTK_VERSION 20  /* bumped whenever a struct or a signature of this header changes: a binding must refuse another version */
 #define ORTK_EINVAL (-1)   /* bad argument / unsupported shape */
 #define ORTK_ENOSPC (-2)   /* workspace too small */
 #define ORTK_ENOSYS (-3)   /* option not implemented (e.g. ACORT weight sharing) */
 #define ORTK_EEXCHANGE (-4) /* ortk_decode_status: an exchange group of the column-split stack kernel never met (launch not fully resident) */
+#define ORTK_ESTALE (-5)    /* ortk_decode_status: ORTK_PACK_VERIFY found that the prepared packs were built from other params (ortk_decode_packs) */
 
 typedef void* ortk_stream;  /* hipStream_t */
 
@@ -423,6 +424,55 @@ int ortk_set_tuning(const ortk_tuning* t);
 #define ORTK_DEC_STACK_FP8 128
 #define ORTK_DEC_GROUPS_JOINT 65536   /* bit 16 (bits 8-15 are the measurement switches) */
 #define ORTK_MAX_BEAM 32      /* widest beam search ortk_decode serves: 2 .. 8 beams run the narrow selection step, 9 .. 32 the wide one */
+
+/* Prepared decode weights (ortk_decode_opts.packs): the weight images a decode derives from `params` — the bf16 arena, the encoder
+ * chains' units in streaming order, the stack kernel's image, the sparse stream — kept in a CALLER-OWNED buffer between calls, so
+ * that a loop over the batches of a split packs once.  The library keeps no state: the caller owns `buf` and tells every call, in
+ * `have`, which sections of it hold images of the params the call is given.
+ *   sections  fixes the layout: the ORTK_PACK_* sections `buf` has room for, in bit order behind a 256-byte header
+ *             (ortk_decode_packs_bytes); it may not change while `have` != 0.
+ *   have      HOST side, in / out.  A section the call needs (ortk_decode_packs_needed) whose bit is set is READ from buf: its packer
+ *             is not launched.  One whose bit is clear but that has room is BUILT into buf from this call's params, on the stream
+ *             (or side stream) today's packer runs on, and its bit is set before the call returns.  One without room is built in
+ *             the workspace as without packs.  0 = nothing yet; reset it to 0 whenever the params may have changed.
+ *   flags     ORTK_PACK_VERIFY: see below.
+ * ORTK_PACK_SPARSE_PLAN takes no room: the plan's buffers are the caller's (ortk_decode_opts.sparse); the bit records that
+ * ortk_sparse_build has run on that plan for these params, and the call skips it.
+ * Sharing: a handle that a call is FILLING (a needed section with room and without its bit) must not be used by a call on another
+ * stream at the same time.  A WARM handle (every needed section present, or without room) is only read and may be shared by
+ * concurrent decodes.
+ * `params` is still read wherever the executors read fp32 (biases, LayerNorm, embedding table, generator bias): it must hold the
+ * values the packs were built from.  The guard for a handle that outlives its weights: when a call takes a handle from have == 0 to
+ * filled it stores ortk_params_fingerprint of its params in the header; with ORTK_PACK_VERIFY every ortk_decode that reads a warm
+ * section fingerprints its params again and compares ON THE DEVICE (no host synchronisation inside the call): a mismatch sets a
+ * bit of the workspace status word, ortk_decode_status then returns ORTK_ESTALE and the outputs of that call are unspecified.  (The
+ * per-step entry points have no status word: they never verify.  Neither does a handle without sized sections — fp32 precision.)
+ * The fingerprint is written ONLY on that first fill: a later call that builds a further section (a lazy fill) writes none, and is
+ * verified only if it also reads a warm section.  Every call on one handle between two resets of `have` must be given the same
+ * params; a caller who lazy-fills from other params has a mixed handle that the next verified call reports, not this one.
+ * The images also depend on ortk_tuning.row_chain / chain_wide only through WHICH section a call needs, never through a section's
+ * contents.  In fp32 precision no section exists but ORTK_PACK_SPARSE_PLAN: the option is accepted and changes nothing else.
+ * Without packs (NULL) every call packs into its workspace; workspace sizes are the same either way. */
+#define ORTK_PACK_W16 1          /* the bf16 arena */
+#define ORTK_PACK_CHAIN 2        /* the encoder chains' weight units, 48-row form */
+#define ORTK_PACK_CHAIN_WIDE 4   /* ... 76-row form (12 289 .. 19 456 encoder rows: another streaming order) */
+#define ORTK_PACK_STACK 8        /* the dense stack kernel's image */
+#define ORTK_PACK_STACK_FP8 16   /* its fp8 image (ORTK_DEC_STACK_FP8) */
+#define ORTK_PACK_STACK_TP2 32   /* the column-split images: 2, */
+#define ORTK_PACK_STACK_TP4 64   /* 4, */
+#define ORTK_PACK_STACK_TP8 128  /* 8 workgroups per group */
+#define ORTK_PACK_SSTREAM 256    /* the sparse stream and its tables (ORTK_DEC_SPARSE_STREAM) */
+#define ORTK_PACK_SGATHER 512    /* the gather lists and their tables (ORTK_DEC_SPARSE_GATHER) */
+#define ORTK_PACK_SPARSE_PLAN 1024
+#define ORTK_PACK_VERIFY 1       /* ortk_decode_packs.flags */
+typedef struct ortk_decode_packs {
+    void*    buf;       /* device, 256-byte aligned, caller-owned (may be NULL when `bytes` is 0) */
+    size_t   bytes;     /* >= ortk_decode_packs_bytes(cfg, sections) */
+    uint32_t sections;  /* layout: the ORTK_PACK_* sections buf has room for; fixed when buf is sized */
+    uint32_t have;      /* in/out, HOST side: sections that hold images of the params these calls are given; 0 = none yet */
+    uint32_t flags;     /* ORTK_PACK_VERIFY */
+} ortk_decode_packs;
+
 typedef struct ortk_decode_opts {
     int32_t beam_size;            /* 1 = greedy; >1 = beam search, at most ORTK_MAX_BEAM beams (and at most cfg->vocab): wider is ORTK_EINVAL
                                    * and ortk_decode_workspace_bytes 0; <1 with num_random_sample > 0 = multinomial */
@@ -560,15 +610,31 @@ typedef struct ortk_decode_opts {
      * or not finite, num_random_sample > 0, train, an exec_flags bit of the stack family. */
     int32_t group_size;
     float   diversity_lambda;
+    /* Prepared decode weights (ortk_decode_packs above); NULL: every call packs into its workspace.  ORTK_EINVAL: a buf that is NULL
+     * (with bytes > 0) or not 256-byte aligned, bytes below ortk_decode_packs_bytes(cfg, sections), an unknown bit in sections or
+     * flags.  A train-mode call (`train`) takes packs like any other: its params are then the caller's business. */
+    ortk_decode_packs* packs;
 } ortk_decode_opts;
 
 size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o);
+/* Bytes of a packs buffer with room for `sections` (a multiple of 256; monotone in `sections`; 0 when no section of `sections` has a
+ * size under cfg: fp32 precision, ORTK_PACK_SPARSE_PLAN alone, a stack section of a configuration the stack kernel does not serve). */
+size_t ortk_decode_packs_bytes(const ortk_config* cfg, uint32_t sections);
+/* The sections ortk_decode(cfg, B images of S regions, o) reads (o->packs is not looked at); 0 for an option combination that
+ * ortk_decode refuses (ortk_decode_workspace_bytes: 0) — and in fp32 precision without a sparse plan.  Host arithmetic only. */
+uint32_t ortk_decode_packs_needed(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o);
+/* *out_dev (device, 8-byte aligned) = F(params, n) = sum over i < n of mix(bits32(params[i]) + (i + 1) * 0x9E3779B97F4A7C15) mod 2^64,
+ * mix = the finaliser of splitmix64.  Order-independent (any reduction tree gives the same value: two runs agree), sensitive to
+ * every single element (the finaliser is a bijection) and to bit patterns (NaN payloads, -0.0).  n = 0: 0.  params 4-byte aligned.
+ * Two launches on `stream` (a memset and one pass over the array), no host synchronisation. */
+int ortk_params_fingerprint(const float* params, int64_t n, uint64_t* out_dev, ortk_stream stream);
 /* seq_out (B,K,seq_len) int64, logprob_out (B,K,seq_len) fp32, score_out (B,K) fp32 or NULL; K = beam | samples | 1. */
 int ortk_decode(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
                 const float* att_masks, int32_t B, int32_t S, const ortk_decode_opts* o, void* ws, size_t ws_bytes,
                 int64_t* seq_out, float* logprob_out, float* score_out, ortk_stream stream);
 /* Status of the ortk_decode that last ran on workspace `ws` (waits for `stream`: the one host synchronisation of the decode API):
- * 0, or ORTK_EEXCHANGE (see ORTK_DEC_SPLIT_SMALL; only the column-split stack kernel can fail this way). */
+ * 0, ORTK_ESTALE (ORTK_PACK_VERIFY: the packs were built from other params; it wins over the next), or ORTK_EEXCHANGE (see
+ * ORTK_DEC_SPLIT_SMALL; only the column-split stack kernel can fail this way). */
 int ortk_decode_status(const void* ws, ortk_stream stream);
 
 /* Encoder only (EncoderDecoder.encode, relation_transformer.py:69-70): memory_out (B,S,d).
@@ -592,6 +658,17 @@ int ortk_decode_step(const ortk_config* cfg, const float* params, const int64_t*
                      int32_t kv_groups, int32_t S, const float* cross_kv, const float* att_masks, float* self_k,
                      float* self_v, int32_t tmax, void* ws, size_t ws_bytes, float* logp_out, int64_t ld_out,
                      ortk_stream stream);
+/* The same three with prepared decode weights (ortk_decode_packs; NULL = the calls above): they read — or fill — ORTK_PACK_W16, the
+ * only image they derive (the encoder of ortk_encode writes fp32 memory and runs no chains).  They never verify. */
+int ortk_encode_p(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
+                  const float* att_masks, int32_t B, int32_t S, void* ws, size_t ws_bytes, float* memory_out,
+                  ortk_stream stream, ortk_decode_packs* packs);
+int ortk_project_memory_p(const ortk_config* cfg, const float* params, const float* memory, int64_t mem_rows, void* ws,
+                          size_t ws_bytes, float* cross_kv, ortk_stream stream, ortk_decode_packs* packs);
+int ortk_decode_step_p(const ortk_config* cfg, const float* params, const int64_t* it, int32_t t, int32_t rows,
+                       int32_t kv_groups, int32_t S, const float* cross_kv, const float* att_masks, float* self_k,
+                       float* self_v, int32_t tmax, void* ws, size_t ws_bytes, float* logp_out, int64_t ld_out,
+                       ortk_stream stream, ortk_decode_packs* packs);
 
 /* ------------------------------------------------------------------------------------------------
  * Operator-level entry points (each is also what the executor calls; exported for parity tests).

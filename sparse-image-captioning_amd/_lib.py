@@ -125,12 +125,22 @@ DEC_UNFUSED, DEC_STACK, DEC_SPARSE_STREAM, DEC_STACK_RB20, DEC_STACK_SPLIT, DEC_
 DEC_GROUPS_JOINT = 1 << 16      # (bits 8-15: the measurement switches)
 
 
+# ortk_decode_packs.sections / .have (include/ortk.h: ORTK_PACK_*) and .flags
+PACK_W16, PACK_CHAIN, PACK_CHAIN_WIDE, PACK_STACK, PACK_STACK_FP8, PACK_STACK_TP2, PACK_STACK_TP4, PACK_STACK_TP8, PACK_SSTREAM, PACK_SGATHER, PACK_SPARSE_PLAN = (
+    1 << i for i in range(11))
+PACK_VERIFY = 1
+
+
+class DecodePacks(C.Structure):       # include/ortk.h: ortk_decode_packs
+    _fields_ = [("buf", C.c_void_p), ("bytes", C.c_size_t), ("sections", C.c_uint32), ("have", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class DecodeOpts(C.Structure):
     _fields_ = [("beam_size", C.c_int32), ("num_random_sample", C.c_int32), ("temperature", C.c_float),
                 ("decoding_constraint", C.c_int32), ("length_penalty", C.c_int32), ("length_alpha", C.c_double),
                 ("seed", C.c_uint64), ("sparse", C.POINTER(EllPlanStruct)), ("exec_flags", C.c_int32), ("with_greedy", C.c_int32), ("sample_row_offset", C.c_int64),
                 ("train", C.c_int32), ("drop_seed", C.c_uint64), ("memory", C.c_void_p), ("top_k", C.c_int32), ("top_p", C.c_float),
-                ("group_size", C.c_int32), ("diversity_lambda", C.c_float)]
+                ("group_size", C.c_int32), ("diversity_lambda", C.c_float), ("packs", C.POINTER(DecodePacks))]
 
 
 class GemmArgs(C.Structure):
@@ -208,6 +218,12 @@ SIGNATURES = {
     "ortk_decode_workspace_bytes": (_SZ, [_CFG, _I32, _I32, C.POINTER(DecodeOpts)]),
     "ortk_decode": (_I32, [_CFG, _P, _P, _P, _P, _I32, _I32, C.POINTER(DecodeOpts), _P, _SZ, _P, _P, _P, _P]),
     "ortk_decode_status": (_I32, [_P, _P]),
+    "ortk_decode_packs_bytes": (_SZ, [_CFG, _U32]),
+    "ortk_decode_packs_needed": (_U32, [_CFG, _I32, _I32, C.POINTER(DecodeOpts)]),
+    "ortk_params_fingerprint": (_I32, [_P, _I64, _P, _P]),
+    "ortk_encode_p": (_I32, [_CFG, _P, _P, _P, _P, _I32, _I32, _P, _SZ, _P, _P, C.POINTER(DecodePacks)]),
+    "ortk_project_memory_p": (_I32, [_CFG, _P, _P, _I64, _P, _SZ, _P, _P, C.POINTER(DecodePacks)]),
+    "ortk_decode_step_p": (_I32, [_CFG, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _SZ, _P, _I64, _P, C.POINTER(DecodePacks)]),
     "ortk_encode": (_I32, [_CFG, _P, _P, _P, _P, _I32, _I32, _P, _SZ, _P, _P]),
     "ortk_chain_packed_bytes": (_SZ, [_I32]),
     "ortk_row_chain": (_I32, [C.POINTER(ChainArgs), _P]),
@@ -284,7 +300,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 19   # include/ortk.h: ORTK_VERSION
+ABI_VERSION = 20   # include/ortk.h: ORTK_VERSION
 
 
 def lib():
@@ -391,7 +407,10 @@ def check(code, what):
         names = {-1: "ORTK_EINVAL (bad argument / unsupported shape)", -2: "ORTK_ENOSPC (workspace too small)",
                  -3: "ORTK_ENOSYS (option not implemented)",
                  -4: "ORTK_EEXCHANGE (column-split decode: an exchange group never met — the launch was not fully resident; "
-                     "outputs are poisoned; set model.exclusive_gpu = False when the GPU is shared)"}
+                     "outputs are poisoned; set model.exclusive_gpu = False when the GPU is shared)",
+                 -5: "ORTK_ESTALE (stale decode packs: the prepared decode weights were built from other parameter values than this "
+                     "call was given; the outputs are unspecified; call model.invalidate_decode_packs() after writing weights "
+                     "through .data or raw pointers)"}
         raise OrtkError(f"{what} failed: {names.get(code, 'hipError ' + str(code))}")
 
 

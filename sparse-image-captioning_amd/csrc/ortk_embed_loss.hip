@@ -321,6 +321,42 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) y[i] = (__bf16)x[i];
 }
 
+// ortk_params_fingerprint (include/ortk.h): *out += sum of fp_mix(bits of x[i], i) over the array.  A sum of 64-bit words mod 2^64: any
+// order of the lanes, waves and workgroups gives the same value.  16-byte loads from the first 16-byte boundary on (`head` elements
+// before it, < 4), the fewer than 4 + 4 elements before and behind them one per thread; 64-bit partials per lane, a shuffle reduction
+// per wave, one atomic per workgroup.
+constexpr uint64_t FP_GOLDEN = 0x9E3779B97F4A7C15ull;
+__device__ __forceinline__ uint64_t fp_mix(uint32_t bits, uint64_t ig /* (i + 1) * FP_GOLDEN */) {
+    uint64_t z = (uint64_t)bits + ig;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void params_fingerprint_kernel(const uint32_t* __restrict__ x, int64_t n, int64_t head,
+                                                                 unsigned long long* __restrict__ out) {
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
+    const uint4* x4 = reinterpret_cast<const uint4*>(x + head);
+    uint64_t acc = 0;
+    for (int64_t i = tid; i < n4; i += (int64_t)gridDim.x * 256) {
+        const uint4 v = x4[i];
+        const uint64_t g = (uint64_t)(head + (i << 2) + 1) * FP_GOLDEN;
+        acc += fp_mix(v.x, g) + fp_mix(v.y, g + FP_GOLDEN) + fp_mix(v.z, g + 2 * FP_GOLDEN) + fp_mix(v.w, g + 3 * FP_GOLDEN);
+    }
+    if (tid < head) acc += fp_mix(x[tid], (uint64_t)(tid + 1) * FP_GOLDEN);
+    if (tid < n - tail0) acc += fp_mix(x[tail0 + tid], (uint64_t)(tail0 + tid + 1) * FP_GOLDEN);
+    unsigned long long a = acc;
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+}
+// ORTK_PACK_VERIFY: the fingerprint of this call's params against the one in the packs header
+__global__ void packs_verify_kernel(const unsigned long long* __restrict__ want, const unsigned long long* __restrict__ got, int32_t* __restrict__ status, int32_t bit) {
+    if (threadIdx.x == 0 && *want != *got) atomicOr(status, bit);
+}
+
 // one 64 x 64 tile of one weight block per workgroup: fp32 (N, K) -> bf16 (K, N) through a padded LDS tile
 __global__ __launch_bounds__(256) void cast_bf16_t_kernel(const float* __restrict__ x, __bf16* __restrict__ yt, ortk::WBlockTable tab) {
     __shared__ float tile[64][65];
@@ -613,6 +649,29 @@ extern "C" int ortk_cast_bf16(const float* x, void* y, int64_t n, ortk_stream st
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, ortk_s(stream), x, reinterpret_cast<__bf16*>(y), n);
     ORTK_CHECK_LAUNCH();
     return 0;
+}
+
+namespace ortk {
+int params_fingerprint_add(const float* params, int64_t n, unsigned long long* out_dev, hipStream_t s) {
+    if (!params || !out_dev || n < 0 || (reinterpret_cast<uintptr_t>(params) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 7)) return ORTK_EINVAL;
+    if (n == 0) return 0;
+    const int64_t head = std::min<int64_t>(n, (int64_t)(((16 - (reinterpret_cast<uintptr_t>(params) & 15)) & 15) >> 2));
+    hipLaunchKernelGGL(params_fingerprint_kernel, dim3(ew_grid((n - head) / 4 + 1)), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(params), n, head, out_dev);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+int packs_verify(const void* want_dev, const unsigned long long* got_dev, int32_t* status, int32_t bit, hipStream_t s) {
+    hipLaunchKernelGGL(packs_verify_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const unsigned long long*>(want_dev), got_dev, status, bit);
+    ORTK_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace ortk
+
+extern "C" int ortk_params_fingerprint(const float* params, int64_t n, uint64_t* out_dev, ortk_stream stream) {
+    if (!out_dev || n < 0 || (n > 0 && !params) || (reinterpret_cast<uintptr_t>(out_dev) & 7)) return ORTK_EINVAL;
+    if (hipMemsetAsync(out_dev, 0, sizeof(uint64_t), ortk_s(stream)) != hipSuccess) return ORTK_EINVAL;
+    if (n == 0) return 0;
+    return ortk::params_fingerprint_add(params, n, reinterpret_cast<unsigned long long*>(out_dev), ortk_s(stream));
 }
 
 namespace ortk {

@@ -82,6 +82,10 @@ struct WBlock { int32_t off, N, K, tile0; };      // tile0: index of the block's
 constexpr int MAX_WBLOCKS = 200;
 struct WBlockTable { int32_t n, tiles; WBlock b[MAX_WBLOCKS]; };
 int cast_bf16_transposed(const float* x, void* yt, const WBlockTable& t, hipStream_t s);
+// *out_dev += ortk_params_fingerprint's sum over the array (the caller zeroes it); *status |= bit when *want_dev != *got_dev
+int params_fingerprint_add(const float* params, int64_t n, unsigned long long* out_dev, hipStream_t s);
+int packs_verify(const void* want_dev, const unsigned long long* got_dev, int32_t* status, int32_t bit, hipStream_t s);
+constexpr int32_t DEC_STATUS_STALE = 1 << 30;      // decode status word: ORTK_PACK_VERIFY mismatch (beside the exchange kernel's TP_ERR_*)
 
 struct BeamState {
     int32_t B, b, L, V, eos;

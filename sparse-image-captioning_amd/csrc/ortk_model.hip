@@ -1510,14 +1510,20 @@ extern "C" int ortk_backward_phase(const ortk_config* cfg, const float* params, 
 }
 
 static int encode_impl(const ortk_config*, const float*, const float*, const float*, const float*, int32_t, int32_t, void*,
-                       size_t, float*, ortk_stream);
+                       size_t, float*, ortk_stream, ortk_decode_packs*);
+static int packs_w16(const ortk_config*, const Offsets&, const float*, ortk_decode_packs*, void*&, ortk_stream);
 
 extern "C" int ortk_encode(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
                            const float* att_masks, int32_t B, int32_t S, void* ws, size_t ws_bytes, float* memory_out,
                            ortk_stream stream) {
+    return ortk_encode_p(cfg, params, att_feats, boxes, att_masks, B, S, ws, ws_bytes, memory_out, stream, nullptr);
+}
+extern "C" int ortk_encode_p(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
+                             const float* att_masks, int32_t B, int32_t S, void* ws, size_t ws_bytes, float* memory_out,
+                             ortk_stream stream, ortk_decode_packs* packs) {
     if (int e = check_cfg(cfg)) return e;
     if (!params || !att_feats || (!boxes && !cfg->no_box) || !att_masks || !ws || !memory_out || B < 1 || S < 1 || S > 128) return ORTK_EINVAL;
-    return encode_impl(cfg, params, att_feats, boxes, att_masks, B, S, ws, ws_bytes, memory_out, stream);
+    return encode_impl(cfg, params, att_feats, boxes, att_masks, B, S, ws, ws_bytes, memory_out, stream, packs);
 }
 
 namespace ortk {
@@ -1703,11 +1709,11 @@ static void carve_decode(const ortk_config& c, int B, int S, int K, bool beam, v
 
 static int encode_impl(const ortk_config* cfg, const float* params, const float* att_feats, const float* boxes,
                        const float* att_masks, int32_t B, int32_t S, void* ws, size_t ws_bytes, float* memory_out,
-                       ortk_stream stream) {
+                       ortk_stream stream, ortk_decode_packs* packs) {
     Offsets o; build_layout(*cfg, o, nullptr);
     DecodeWS w; carve_decode(*cfg, B, S, 1, false, ws, w);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
-    TRY(make_w16(cfg, o, params, w.w16, stream));
+    TRY(packs_w16(cfg, o, params, packs, w.w16, stream));
     Ctx c{cfg, ortk_s(stream), cfg->precision, 0, false, params, w.w16, w.adt};
     EncBuf ep[MAXLAYERS];
     for (int l = 0; l < cfg->n_layers; ++l) ep[l] = w.enc;
@@ -1770,6 +1776,132 @@ static DecodePlan plan_decode(const ortk_config& cfg, int B, int K, const ortk_d
     }
     return p;
 }
+// options ortk_decode serves (everything it refuses before it carves the workspace); K and G out
+static bool decode_opts_ok(const ortk_config* cfg, const ortk_decode_opts* o, int& K, int& G) {
+    K = decode_K(o);
+    if (K < 1 || decode_trunc(cfg, o) < 0) return false;
+    if (o->num_random_sample <= 0 && o->beam_size > 1 && (K > ORTK_MAX_BEAM || K > cfg->vocab)) return false;      // (ortk_decode: ORTK_EINVAL)
+    G = decode_groups(o);
+    return G >= 1;
+}
+
+// ------------------------------------------------------------------------------------------------ prepared decode weights
+// (ortk_decode_packs, include/ortk.h)  The buffer: a 256-byte header — [0] the 64-bit fingerprint of the params the handle was
+// filled from — then the sized sections the caller made room for, in bit order, each a multiple of 256 bytes.
+constexpr int PACK_NSEC = 10;                       // sized sections (ORTK_PACK_SPARSE_PLAN, the next bit, takes no room)
+constexpr uint32_t PACK_SIZED = (1u << PACK_NSEC) - 1, PACK_ALL = PACK_SIZED | ORTK_PACK_SPARSE_PLAN;
+constexpr size_t PACK_HEADER = 256;
+static_assert(ORTK_PACK_SPARSE_PLAN == (1u << PACK_NSEC) && ORTK_PACK_SGATHER == (1u << (PACK_NSEC - 1)), "section bits");
+
+static size_t pack_section_bytes(const ortk_config& c, const Offsets& o, uint32_t sec) {
+    if (!c.precision) return 0;
+    const int L = c.n_layers, NC = c.d_ff / 512;
+    const bool stk = stack_ok(c, 0, ORTK_DEC_STACK);          // (the configuration alone: the flag lifts the row rule)
+    size_t n = 0;
+    switch (sec) {
+    case ORTK_PACK_W16: n = (size_t)o.total * 2; break;
+    case ORTK_PACK_CHAIN: case ORTK_PACK_CHAIN_WIDE: { ChainSet cs; chain_layout(c, o, true, false, cs, 0, 0, true); n = cs.bytes; break; }
+    case ORTK_PACK_STACK: n = stk ? stack_packed_bytes(L, NC) : 0; break;
+    case ORTK_PACK_STACK_FP8: n = stk ? stack_packed_fp8_bytes(L, NC) : 0; break;
+    case ORTK_PACK_STACK_TP2: n = stk ? stack_tp_packed_bytes(L, NC, 2) : 0; break;
+    case ORTK_PACK_STACK_TP4: n = stk ? stack_tp_packed_bytes(L, NC, 4) : 0; break;
+    case ORTK_PACK_STACK_TP8: n = stk ? stack_tp_packed_bytes(L, NC, 8) : 0; break;
+    case ORTK_PACK_SSTREAM: case ORTK_PACK_SGATHER: n = stk ? sstack_bytes(L, NC, nullptr, nullptr) : 0; break;
+    default: break;
+    }
+    return (n + 255) & ~(size_t)255;
+}
+static uint32_t pack_tp_section(int tp) { return tp == 8 ? ORTK_PACK_STACK_TP8 : tp == 4 ? ORTK_PACK_STACK_TP4 : tp == 2 ? ORTK_PACK_STACK_TP2 : 0; }
+// whether the encoder pass of a decode runs its row chains, and on which form of the pack (the rule of ortk_decode)
+static uint32_t pack_chain_section(const ortk_config& cfg, const Offsets& o, int B, int S, const ortk_decode_opts* op, bool greedy_rows, ChainSet& ecs) {
+    chain_layout(cfg, o, true, false, ecs, (int64_t)B * S, 0);
+    const bool enc_bf16_attn = cfg.precision && attn16_shape_ok(S, S, cfg.d_model / cfg.n_heads);
+    if (ecs.on && (!ecs.bytes || op->sparse || !enc_bf16_attn || (op->memory && !greedy_rows))) ecs.on = false;
+    if (!ecs.on) return 0;
+    return chain_wide((int64_t)B * S) ? ORTK_PACK_CHAIN_WIDE : ORTK_PACK_CHAIN;
+}
+
+// One call's view of a handle.  place(): where a section lives for this call — in the handle (read there when warm(), built there
+// otherwise) or, without room, in the workspace as ever.  finish(): header fingerprint of a first fill, the verification of a warm
+// read, and the `have` bits of what this call built.
+struct PackUse {
+    ortk_decode_packs* p = nullptr; char* base = nullptr; size_t off[PACK_NSEC] = {}; uint32_t room = 0, had = 0, built = 0, read = 0;
+    int init(const ortk_config& c, const Offsets& o, ortk_decode_packs* packs) {
+        if (!packs) return 0;
+        if ((packs->sections & ~PACK_ALL) || (packs->flags & ~(uint32_t)ORTK_PACK_VERIFY)) return ORTK_EINVAL;
+        size_t at = PACK_HEADER;
+        for (int i = 0; i < PACK_NSEC; ++i) {
+            const uint32_t sec = 1u << i;
+            const size_t n = (packs->sections & sec) ? pack_section_bytes(c, o, sec) : 0;
+            if (n) { off[i] = at; at += n; room |= sec; }
+        }
+        if (room) {
+            if (!packs->buf || (reinterpret_cast<uintptr_t>(packs->buf) & 255) || packs->bytes < at) return ORTK_EINVAL;
+            base = reinterpret_cast<char*>(packs->buf);
+        }
+        room |= ORTK_PACK_SPARSE_PLAN;
+        had = packs->have & room;
+        p = packs;
+        return 0;
+    }
+    bool warm(uint32_t sec) const { return (had & sec) != 0; }
+    void* place(uint32_t sec, void* ws_ptr) {
+        if (!(room & sec & PACK_SIZED)) return ws_ptr;
+        int i = 0;
+        while ((1u << i) != sec) ++i;
+        ((had & sec) ? read : built) |= sec;
+        return base + off[i];
+    }
+    void plan_used() { ((had & ORTK_PACK_SPARSE_PLAN) ? read : built) |= (room & ORTK_PACK_SPARSE_PLAN); }
+    int finish(const float* params, int64_t n, int32_t* status, hipStream_t s) {
+        if (!p) return 0;
+        if (base && !(had & PACK_SIZED) && (built & PACK_SIZED)) TRY(ortk_params_fingerprint(params, n, reinterpret_cast<uint64_t*>(base), (ortk_stream)s));
+        // (status + 2: 8 bytes of the zeroed status block, the fingerprint of THIS call's params — a warm handle is never written)
+        if (base && status && (p->flags & ORTK_PACK_VERIFY) && read && (had & PACK_SIZED)) {
+            unsigned long long* got = reinterpret_cast<unsigned long long*>(status + 2);
+            TRY(params_fingerprint_add(params, n, got, s));
+            TRY(packs_verify(base, got, status, DEC_STATUS_STALE, s));
+        }
+        p->have |= built;
+        return 0;
+    }
+};
+
+// the bf16 arena of a call that derives nothing else (ortk_encode_p and the per-step entry points): w16 becomes the handle's when it has room
+static int packs_w16(const ortk_config* cfg, const Offsets& o, const float* params, ortk_decode_packs* packs, void*& w16, ortk_stream stream) {
+    PackUse pu;
+    if (int e = pu.init(*cfg, o, packs)) return e;
+    if (!cfg->precision) return 0;
+    w16 = pu.place(ORTK_PACK_W16, w16);
+    if (!pu.warm(ORTK_PACK_W16)) TRY(make_w16(cfg, o, params, w16, stream));
+    return pu.finish(params, o.total, nullptr, ortk_s(stream));
+}
+
+extern "C" size_t ortk_decode_packs_bytes(const ortk_config* cfg, uint32_t sections) {
+    if (check_cfg(cfg) || (sections & ~PACK_ALL)) return 0;
+    Offsets o; build_layout(*cfg, o, nullptr);
+    size_t at = 0;
+    for (int i = 0; i < PACK_NSEC; ++i) if (sections & (1u << i)) at += pack_section_bytes(*cfg, o, 1u << i);
+    return at ? at + PACK_HEADER : 0;
+}
+
+extern "C" uint32_t ortk_decode_packs_needed(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* op) {
+    if (check_cfg(cfg) || !op || B < 1 || S < 1) return 0;
+    int K, G;
+    if (!decode_opts_ok(cfg, op, K, G)) return 0;
+    const DecodePlan pl = plan_decode(*cfg, B, K, op);
+    if (!pl.ok) return 0;
+    uint32_t need = op->sparse ? ORTK_PACK_SPARSE_PLAN : 0;
+    if (!cfg->precision) return need;
+    need |= ORTK_PACK_W16;
+    Offsets o; build_layout(*cfg, o, nullptr);
+    ChainSet ecs;
+    need |= pack_chain_section(*cfg, o, B, S, op, op->train && op->with_greedy, ecs);
+    if (pl.stack && pl.sstream) need |= pl.gather ? ORTK_PACK_SGATHER : ORTK_PACK_SSTREAM;
+    else if (pl.stack && pl.split) need |= pack_tp_section(pl.split);
+    else if (pl.stack) need |= pl.fp8 ? ORTK_PACK_STACK_FP8 : ORTK_PACK_STACK;
+    return need;
+}
 
 extern "C" size_t ortk_decode_workspace_bytes(const ortk_config* cfg, int32_t B, int32_t S, const ortk_decode_opts* o) {
     if (check_cfg(cfg) || !o || B < 1 || S < 1) return 0;
@@ -1793,7 +1925,7 @@ extern "C" int ortk_decode_status(const void* ws, ortk_stream stream) {
     int32_t h = 0;
     if (hipMemcpyAsync(&h, ws, sizeof(h), hipMemcpyDeviceToHost, ortk_s(stream)) != hipSuccess) return ORTK_EINVAL;
     if (hipStreamSynchronize(ortk_s(stream)) != hipSuccess) return ORTK_EINVAL;
-    return h == 0 ? 0 : ORTK_EEXCHANGE;
+    return h == 0 ? 0 : (h & DEC_STATUS_STALE) ? ORTK_ESTALE : ORTK_EEXCHANGE;
 }
 
 // One position of the cached-attention decoder for `rows` rows (transformer.py:172-210 with the caches of :240-273):
@@ -2103,11 +2235,20 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
     hipStream_t s = ortk_s(stream);
     TRY(fill_i32(w.status, 64, 0, s));
-    TRY(make_w16(cfg, o, params, w.w16, stream));
+    // prepared decode weights (ortk_decode_packs): a section with room in the caller's handle lives THERE instead of in the workspace,
+    // and its packer runs only while the handle does not have it yet
+    PackUse pu;
+    if (int e = pu.init(*cfg, o, op->packs)) return e;
+    if (cfg->precision) {
+        w.w16 = pu.place(ORTK_PACK_W16, w.w16);
+        if (!pu.warm(ORTK_PACK_W16)) TRY(make_w16(cfg, o, params, w.w16, stream));
+    }
+    const uint32_t ss_sec = pl.gather ? ORTK_PACK_SGATHER : ORTK_PACK_SSTREAM;
+    const bool ss_build = stack && sstream && !pu.warm(ss_sec);
     // (the bf16 weight copy exists from here on in stream order: what the side stream's builders wait for)
     SideStream* const side0 = (w.adt == ORTK_BF16 && !ortk_prof_serial()) ? side_for(s) : nullptr;
     hipEvent_t w16_done = nullptr;
-    if (side0 && stack && sstream) {
+    if (side0 && ss_build) {
         w16_done = side0->take();
         if (hipEventRecord(w16_done, s) != hipSuccess) return ORTK_EINVAL;
     }
@@ -2120,17 +2261,23 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     if (stack) {
         if (sstream) { /* the sparse weight stream is built beside the encoder pass, below */ }
         else if (w.tp) {
-            TRY(stack_tp_pack(w.w16, w.tp_wpk, tp, w.tp, s));
+            w.tp_wpk = pu.place(pack_tp_section(w.tp), w.tp_wpk);
+            if (!pu.warm(pack_tp_section(w.tp))) TRY(stack_tp_pack(w.w16, w.tp_wpk, tp, w.tp, s));
             TRY(fill_i32(w.tp_flag, (int64_t)stack_tp_groups((int64_t)B * K) * TP_FLAG_STRIDE, 0, s));
             TRY(fill_i32(w.progress, 16, 0, s));
         } else {
-            TRY(pl.fp8 ? stack_pack_fp8(w.w16, w.wpk, tp, s) : stack_pack(w.w16, w.wpk, tp, s));
+            const uint32_t sec = pl.fp8 ? ORTK_PACK_STACK_FP8 : ORTK_PACK_STACK;
+            w.wpk = pu.place(sec, w.wpk);
+            if (!pu.warm(sec)) TRY(pl.fp8 ? stack_pack_fp8(w.w16, w.wpk, tp, s) : stack_pack(w.w16, w.wpk, tp, s));
             TRY(fill_i32(w.progress, 16, 0, s));
         }
     }
     Ctx c{cfg, s, cfg->precision, op->train ? op->drop_seed : 0, op->train != 0, params, w.w16, w.adt};
     if (op->sparse) {
-        TRY(ortk_sparse_build(op->sparse, cfg->precision ? (const void*)w.w16 : (const void*)params, cfg->precision ? ORTK_BF16 : ORTK_F32, stream));
+        // (ORTK_PACK_SPARSE_PLAN: the caller's plan already holds the images of these params)
+        if (!pu.warm(ORTK_PACK_SPARSE_PLAN))
+            TRY(ortk_sparse_build(op->sparse, cfg->precision ? (const void*)w.w16 : (const void*)params, cfg->precision ? ORTK_BF16 : ORTK_F32, stream));
+        pu.plan_used();
         c.ell_f = op->sparse;
     }
     const float* P = params;
@@ -2145,10 +2292,12 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     c.side = (c.adt == ORTK_BF16 && !ortk_prof_serial()) ? side_for(c.s) : nullptr;
     c.use_side = c.side != nullptr;
     // the encoder's row-wise operators as rows-stationary chains (ortk_chain.hip): bf16 Q|K|V (the buffer is fp32-sized) and memory
-    ChainSet ecs; chain_layout(*cfg, o, true, false, ecs, Me, 0);
-    const bool enc_bf16_attn = cfg->precision && attn16_shape_ok(S, S, d / cfg->n_heads);
-    if (ecs.on && (!w.chain_pk || op->sparse || !enc_bf16_attn || (op->memory && !greedy_rows))) ecs.on = false;
-    if (ecs.on) TRY(chain_pack_all(w.w16, w.chain_pk, ecs.t, s));
+    ChainSet ecs;
+    const uint32_t chain_sec = pack_chain_section(*cfg, o, B, S, op, greedy_rows, ecs);
+    if (ecs.on) {
+        w.chain_pk = pu.place(chain_sec, w.chain_pk);
+        if (!pu.warm(chain_sec)) TRY(chain_pack_all(w.w16, w.chain_pk, ecs.t, s));
+    }
     const int enc_qdt = ecs.on ? ORTK_BF16 : ORTK_F32;
     // ortk_decode_opts.memory: the encoder output of these images already exists (the training forward's, ortk_forward_phase 1)
     if (greedy_rows) {
@@ -2164,6 +2313,10 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     // pass, which does not read it; the first decoder position waits for it
     hipEvent_t sstream_done = nullptr;
     if (stack && sstream) {
+        void* const ssb = pu.place(ss_sec, w.ss.stream);      // (the stream heads the block sstack_bytes carves)
+        if (ssb != (void*)w.ss.stream) sstack_bytes(L, cfg->d_ff / 512, &w.ss, ssb);
+    }
+    if (ss_build) {
         if (c.use_side && w16_done) {
             if (hipStreamWaitEvent(c.side->s, w16_done, 0) != hipSuccess) return ORTK_EINVAL;     // (NOT a fork: the encoder pass is queued already)
             TRY(pl.gather ? gstack_pack(w.w16, w.ss, tp, c.side->s) : sstack_pack(w.w16, w.ss, tp, c.side->s));
@@ -2175,8 +2328,11 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     c.use_side = false;
     TRY(fwd_gemm(c, op->memory ? op->memory : w.mem, A, d, o.ckv_w, P + o.ckv_b, w.ckv, w.ckvdt, o.ckv_slots * o.cw, Me, (int)(o.ckv_slots * o.cw), d));
 
-    if (G > 1 && pl.joint) return decode_diverse_joint(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out);
-    if (G > 1) return decode_diverse(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out);
+    if (G > 1) {
+        TRY(pl.joint ? decode_diverse_joint(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out)
+                     : decode_diverse(c, o, w, op, att_masks, B, S, K / G, G, seq_out, logprob_out, score_out));
+        return pu.finish(params, o.total, w.status, s);
+    }
     const int64_t rows_full = (int64_t)B * K;
     BeamState bs; std::memset(&bs, 0, sizeof(bs));
     SampleState ss; std::memset(&ss, 0, sizeof(ss));
@@ -2248,7 +2404,7 @@ extern "C" int ortk_decode(const ortk_config* cfg, const float* params, const fl
     }
     // the column-split kernel's exchanges are bounded waits: a decode whose groups never met must not pass for a result
     if (w.tp) TRY(decode_poison(w.status, seq_out, logprob_out, score_out, rows_full * T, rows_full, s));
-    return 0;
+    return pu.finish(params, o.total, w.status, s);
 }
 
 // ------------------------------------------------------------------------------------------------ per-step host API
@@ -2276,12 +2432,16 @@ extern "C" size_t ortk_decode_step_workspace_bytes(const ortk_config* cfg, int32
 
 extern "C" int ortk_project_memory(const ortk_config* cfg, const float* params, const float* memory, int64_t mem_rows, void* ws,
                                    size_t ws_bytes, float* cross_kv, ortk_stream stream) {
+    return ortk_project_memory_p(cfg, params, memory, mem_rows, ws, ws_bytes, cross_kv, stream, nullptr);
+}
+extern "C" int ortk_project_memory_p(const ortk_config* cfg, const float* params, const float* memory, int64_t mem_rows, void* ws,
+                                     size_t ws_bytes, float* cross_kv, ortk_stream stream, ortk_decode_packs* packs) {
     if (int e = check_cfg(cfg)) return e;
     if (!params || !memory || !cross_kv || !ws || mem_rows < 1) return ORTK_EINVAL;
     Offsets o; build_layout(*cfg, o, nullptr);
     StepWS w; carve_step(*cfg, 1, ws, w);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
-    TRY(make_w16(cfg, o, params, w.w16, stream));
+    TRY(packs_w16(cfg, o, params, packs, w.w16, stream));
     Ctx c{cfg, ortk_s(stream), cfg->precision, 0, false, params, w.w16, cfg->precision ? ORTK_BF16 : ORTK_F32};
     const int d = cfg->d_model, L = cfg->n_layers;
     const int U = o.ckv_slots;      // distinct decoder layers (ortk_config.share_dec)
@@ -2293,13 +2453,20 @@ extern "C" int ortk_decode_step(const ortk_config* cfg, const float* params, con
                                 int32_t kv_groups, int32_t S, const float* cross_kv, const float* att_masks, float* self_k,
                                 float* self_v, int32_t tmax, void* ws, size_t ws_bytes, float* logp_out, int64_t ld_out,
                                 ortk_stream stream) {
+    return ortk_decode_step_p(cfg, params, it, t, rows, kv_groups, S, cross_kv, att_masks, self_k, self_v, tmax, ws, ws_bytes, logp_out, ld_out,
+                              stream, nullptr);
+}
+extern "C" int ortk_decode_step_p(const ortk_config* cfg, const float* params, const int64_t* it, int32_t t, int32_t rows,
+                                  int32_t kv_groups, int32_t S, const float* cross_kv, const float* att_masks, float* self_k,
+                                  float* self_v, int32_t tmax, void* ws, size_t ws_bytes, float* logp_out, int64_t ld_out,
+                                  ortk_stream stream, ortk_decode_packs* packs) {
     if (int e = check_cfg(cfg)) return e;
     if (!params || !it || !cross_kv || !att_masks || !self_k || !self_v || !ws || !logp_out) return ORTK_EINVAL;
     if (rows < 1 || kv_groups < 1 || rows % kv_groups || S < 1 || S > 128 || t < 0 || t >= tmax || ld_out < cfg->vocab) return ORTK_EINVAL;
     Offsets o; build_layout(*cfg, o, nullptr);
     StepWS w; carve_step(*cfg, rows, ws, w);
     if (w.bytes > ws_bytes) return ORTK_ENOSPC;
-    TRY(make_w16(cfg, o, params, w.w16, stream));
+    TRY(packs_w16(cfg, o, params, packs, w.w16, stream));
     Ctx c{cfg, ortk_s(stream), cfg->precision, 0, false, params, w.w16, cfg->precision ? ORTK_BF16 : ORTK_F32};
     const int64_t d = cfg->d_model;
     StepBufs sb{it, w.xa, w.xb, w.y, w.qkv, w.o, w.q, w.h, w.logits, w.st, w.ldv, cross_kv, att_masks};

@@ -131,6 +131,14 @@ class RelationTransformerModel(CaptionModelBase):
     DROPOUT = 0.1          # make_model(dropout=0.1), relation_transformer.py:306
     MASKED = False
     NO_BOX = False         # True in the plain `transformer` subclass (models/transformer.py)
+    # Prepared decode weights (include/ortk.h: ortk_decode_packs): None = every decode call derives its weight images
+    # (bf16 arena, chain pack, stack image, sparse stream, sparse plan) from the arena again; "cached" = the model keeps them in one
+    # handle between calls and rebuilds them when the weights may have changed (invalidate_decode_packs); "verified" = as "cached",
+    # and every decode fingerprints the arena on the device and reads the status afterwards — a HOST SYNCHRONISATION per decode — to
+    # raise OrtkError on a stale handle.  Only mode="sample" decodes verify: `encode` and `get_logprobs_state` (the per-step entry
+    # points have no status word) run "verified" as "cached", so a `.data` write is NOT caught there.  opt["packs"] overrides the
+    # attribute for one mode="sample" call.
+    decode_packs = None
 
     def __init__(self, config, precision=None):
         super().__init__()
@@ -228,6 +236,8 @@ class RelationTransformerModel(CaptionModelBase):
         self._ws_cache = {}
         self._vr_stage = {}
         self._plans = None                 # sparse plans live on the old device
+        self._packs = None                 # ... and so does the decode packs handle
+        self.invalidate_decode_packs()
         self._ccfg.sparse_fwd = None
         self._ccfg.sparse_bwd = None
         for par in self.parameters():
@@ -281,7 +291,60 @@ class RelationTransformerModel(CaptionModelBase):
               for k, v in densify_state_dict(state_dict).items()}
         out = super().load_state_dict(sd, strict=strict, **kw)
         self._plans = None          # sparse plans: block selection and capacities were taken from the OLD weights
+        self.invalidate_decode_packs()
         return out
+
+    # ------------------------------------------------------------------ prepared decode weights
+    def invalidate_decode_packs(self):
+        """Tell the model that its weights (or masks) may have changed in a way it cannot see, so that the next decode with
+        ``decode_packs`` on rebuilds its prepared weight images.  Seen without this call: a rebound or moved arena, in-place torch
+        operations on the parameters or the arenas (``p.mul_()``, ``p.copy_()`` under ``no_grad``: they bump ``_version``),
+        ``load_state_dict``, every ``NativeTrainer`` step and ``load_checkpoint``, the mask updates of the pruning mixin,
+        ``enable_sparse_kernels`` and a new sparse plan.  NOT seen: writes through ``p.data`` (``p.data`` is a fresh tensor with a
+        version counter of its own) and writes through raw device pointers by other code — call this after them, or decode with
+        ``decode_packs = "verified"``."""
+        self._packs_epoch = getattr(self, "_packs_epoch", 0) + 1
+
+    @staticmethod
+    def _packs_mode(mode):
+        if mode not in (None, "cached", "verified"):
+            raise ValueError(f'decode_packs must be None, "cached" or "verified", saw {mode!r}')
+        return mode
+
+    def _packs_key(self):
+        """What the prepared images were built from: arena addresses and version counters, the parameters' own version counters,
+        and the counter ``invalidate_decode_packs`` bumps."""
+        plist = getattr(self, "_packs_plist", None)
+        if plist is None:
+            plist = self._packs_plist = list(self.parameters())
+        arenas = tuple((t.data_ptr(), t._version) for t in (getattr(self, a, None) for a in ("_flat", "_mask_flat")) if t is not None)
+        return getattr(self, "_packs_epoch", 0), arenas, sum(p._version for p in plist)
+
+    def _decode_params_ptr(self, packs_mode, key=None):
+        """Device pointer of the eval-mode arena a decode reads (the `_prune` variant skips its mask pass on a warm handle);
+        ``key`` is this call's ``_packs_key()`` when packs are on."""
+        return self._eff_params_ptr(False, 0)
+
+    def _packs_handle(self, mode, needed, key):
+        """The model's ``ortk_decode_packs`` (one per model) with room for the sections ``needed`` and every section an earlier call
+        needed; re-allocated larger — and emptied — when a new section turns up, emptied when the weights may have changed
+        (``key``: this call's ``_packs_key()``, walked once per call — it reads every parameter's counter)."""
+        dev = self._flat.device
+        h = getattr(self, "_packs", None)
+        if h is not None and h["buf"].device != dev:
+            h = None
+        if h is None or (needed & ~h["st"].sections):
+            sections = needed | (h["st"].sections if h is not None else 0)
+            h = self._packs = None           # (release the smaller buffer first)
+            nbytes = L.lib().ortk_decode_packs_bytes(C.byref(self._ccfg), sections)
+            st = L.DecodePacks()
+            buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+            st.buf, st.bytes, st.sections, st.have = (buf.data_ptr() if nbytes else None), nbytes, sections, 0
+            h = self._packs = {"st": st, "buf": buf, "key": key}
+        if h["key"] != key:
+            h["st"].have, h["key"] = 0, key
+        h["st"].flags = L.PACK_VERIFY if mode == "verified" else 0
+        return h
 
     # ------------------------------------------------------------------ helpers
     def _eff_params_ptr(self, train, seed):
@@ -309,6 +372,7 @@ class RelationTransformerModel(CaptionModelBase):
         self._sparse_fmt = {None: None, "ell16": L.SP_ELL16, "gu16": L.SP_GU16, "ell32": L.SP_ELL32}[fmt]      # None: by precision
         self._sparse_train = bool(train) and min_sparsity is not None
         self._plans = None
+        self.invalidate_decode_packs()
         self._ccfg.sparse_fwd = None
         self._ccfg.sparse_bwd = None
         if min_sparsity is not None and self._flat.is_cuda:
@@ -349,6 +413,7 @@ class RelationTransformerModel(CaptionModelBase):
                 pf.build(eff[:self._n_train].bfloat16() if self.precision else eff)
                 pf.check_overflow()
             self._plans = (pf, pb)
+            self.invalidate_decode_packs()          # (a new plan holds no images yet)
             if self._sparse_train:
                 self._ccfg.sparse_fwd = C.cast(pf.ref(), C.c_void_p) if pf is not None else None
                 self._ccfg.sparse_bwd = C.cast(pb.ref(), C.c_void_p) if pb is not None else None
@@ -493,6 +558,8 @@ class RelationTransformerModel(CaptionModelBase):
     def _run_forward(self, batch, train, seed, want_logp, cache_ws):
         lib = L.lib()
         self._sparse_plans()       # (re)attach the training plans to the config after enable / a device move
+        if self._ccfg.sparse_fwd:
+            self.invalidate_decode_packs()      # (this forward refills the forward plan the decodes share, from ITS weights)
         nbytes = lib.ortk_train_workspace_bytes(C.byref(self._ccfg), batch.B, batch.S, batch.R, batch.T)
         ws = self._workspace(("train", batch.B, batch.S, batch.R, batch.T), nbytes, cache_ws)
         logp, ldv = None, 0
@@ -741,9 +808,17 @@ class RelationTransformerModel(CaptionModelBase):
         seq = torch.empty(B, K, self.seq_length, dtype=torch.long, device=dev)
         lp = torch.empty(B, K, self.seq_length, device=dev)
         score = torch.empty(B, K, device=dev)
-        pptr = self._eff_params_ptr(False, 0)
+        # prepared decode weights: opt["packs"] over model.decode_packs; train-mode decodes of a masked model read a Bernoulli sample of
+        # the weights, never the eval-mode image the handle holds
+        pmode = self._packs_mode(opt.get("packs", self.decode_packs))
+        if pmode and self.MASKED and o.train:
+            pmode = None
+        pkey = self._packs_key() if pmode else None
+        pptr = self._decode_params_ptr(pmode, pkey)
         fresh_plan = getattr(self, "_plans", None) is None
         plan = self._sparse_plans()[0]
+        if pmode and pkey[0] != getattr(self, "_packs_epoch", 0):
+            pkey = self._packs_key()       # (a plan made just now bumped the counter: the handle must not keep its SPARSE_PLAN bit)
         # (train-mode rollouts — the default SCST step of a pruned model with enable_sparse_kernels() — have no sparse form: every
         #  dropout site is an epilogue of the dense kernels; they run the dense products on the zero-filled effective weights, which
         #  is what the reference's MaskedLinear computes, pruning/masked_layer.py:134-135)
@@ -768,6 +843,14 @@ class RelationTransformerModel(CaptionModelBase):
             n = 1
 
         used_ws = []
+        bounds = [B * i // n for i in range(n + 1)]
+        packs = None
+        if pmode:
+            needed = 0
+            for i in range(n):
+                needed |= lib.ortk_decode_packs_needed(C.byref(self._ccfg), bounds[i + 1] - bounds[i], S, C.byref(o))
+            packs = self._packs_handle(pmode, needed, pkey)["st"]
+            o.packs = C.pointer(packs)
 
         def run(i, b0, b1, stream_ptr, out):
             oi = L.DecodeOpts.from_buffer_copy(o)
@@ -791,11 +874,16 @@ class RelationTransformerModel(CaptionModelBase):
             if len(getattr(self, "_dec_streams", [])) < n:
                 self._dec_streams = [torch.cuda.Stream(device=dev) for _ in range(n)]
             streams = self._dec_streams[:n]
-            bounds = [B * i // n for i in range(n + 1)]
+            # a handle that is being filled belongs to one stream: the leading chunks run on the caller's stream, one after the other,
+            # until the handle has every section the chunks need; the others then share the warm handle
+            first = 0
+            while packs is not None and first < n and (needed & ~packs.have):
+                run(first, bounds[first], bounds[first + 1], L.stream_ptr(), rc)
+                first += 1
             for s_ in streams:
                 s_.wait_stream(cur)
             ths = [threading.Thread(target=run, args=(i, bounds[i], bounds[i + 1], C.c_void_p(streams[i].cuda_stream), rc))
-                   for i in range(n)]
+                   for i in range(first, n)]
             for t in ths:
                 t.start()
             for t in ths:
@@ -808,6 +896,9 @@ class RelationTransformerModel(CaptionModelBase):
             L.check(r, "ortk_decode")
         if plan is not None and fresh_plan:
             plan.check_overflow()      # (host sync, first decode on a new plan: the images were built from THIS call's weights)
+        if pmode == "verified":        # (host sync: ORTK_ESTALE when the handle was built from other weights than this call read)
+            for ws in used_ws:
+                L.check(lib.ortk_decode_status(L.ptr(ws), L.stream_ptr()), "ortk_decode (status)")
         # The column-split stack kernel's exchanges are bounded waits (ortk.h: ORTK_DEC_SPLIT_SMALL): a decode whose groups never
         # met (another kernel held compute units) has poisoned outputs and a status word.  Reading it is a host synchronisation, so
         # it is read on the first decodes of a model, then every 64th, and whenever opt["check_status"] asks.
@@ -891,7 +982,10 @@ class RelationTransformerModel(CaptionModelBase):
         cw, vo = (d, 0) if kv_shared else (2 * d, d)
         it = it.to(dev).long().contiguous()
         masks = mask.reshape(rows, S).to(dev).float().contiguous()
-        pptr = self._eff_params_ptr(False, 0)
+        pmode = self._packs_mode(self.decode_packs)
+        pkey = self._packs_key() if pmode else None
+        pptr = self._decode_params_ptr(pmode, pkey)
+        packs = C.pointer(self._packs_handle(pmode, L.PACK_W16 if self.precision else 0, pkey)["st"]) if pmode else None
         nbytes = lib.ortk_decode_step_workspace_bytes(C.byref(self._ccfg), rows)
         ws = self._workspace(("step", rows), nbytes, True)
         self_k = torch.zeros(Lr, rows, T, d, device=dev)
@@ -900,8 +994,8 @@ class RelationTransformerModel(CaptionModelBase):
             t = 0
             ckv = torch.empty(rows * S, U * cw, device=dev)
             mem = memory.to(dev).float().contiguous()
-            L.check(lib.ortk_project_memory(C.byref(self._ccfg), pptr, L.ptr(mem), rows * S, L.ptr(ws), ws.numel(),
-                                            L.ptr(ckv), L.stream_ptr()), "ortk_project_memory")
+            L.check(lib.ortk_project_memory_p(C.byref(self._ccfg), pptr, L.ptr(mem), rows * S, L.ptr(ws), ws.numel(),
+                                              L.ptr(ckv), L.stream_ptr(), packs), "ortk_project_memory")
         else:
             caches = state[1:]
             assert len(caches) == 4 * Lr, "state must come from get_logprobs_state"
@@ -917,9 +1011,9 @@ class RelationTransformerModel(CaptionModelBase):
                     ckv[:, :, slot[l], d:2 * d] = unhead(caches[4 * l + 3])
             ckv = ckv.view(rows * S, U * cw)
         logp = torch.empty(rows, self.vocab_size, device=dev)
-        L.check(lib.ortk_decode_step(C.byref(self._ccfg), pptr, L.ptr(it), t, rows, rows, S, L.ptr(ckv), L.ptr(masks),
-                                     L.ptr(self_k), L.ptr(self_v), T, L.ptr(ws), ws.numel(), L.ptr(logp), self.vocab_size,
-                                     L.stream_ptr()), "ortk_decode_step")
+        L.check(lib.ortk_decode_step_p(C.byref(self._ccfg), pptr, L.ptr(it), t, rows, rows, S, L.ptr(ckv), L.ptr(masks),
+                                       L.ptr(self_k), L.ptr(self_v), T, L.ptr(ws), ws.numel(), L.ptr(logp), self.vocab_size,
+                                       L.stream_ptr(), packs), "ortk_decode_step")
         head = lambda x: x.reshape(rows, -1, H, dk).permute(2, 0, 1, 3).contiguous()  # (rows, len, d) -> (h, rows, len, dk)
         ckv4 = ckv.view(rows, S, U, cw)
         new_state = [it.view(1, rows, 1)]
@@ -938,8 +1032,12 @@ class RelationTransformerModel(CaptionModelBase):
         o.beam_size, o.temperature = 1, 1.0
         ws = self._workspace(("decode", B, S, 1, False), lib.ortk_decode_workspace_bytes(C.byref(self._ccfg), B, S, C.byref(o)), True)
         mem = torch.empty(B, S, self.d_model, device=self._flat.device)
-        L.check(lib.ortk_encode(C.byref(self._ccfg), self._eff_params_ptr(False, 0), L.ptr(feats), L.ptr(bxs), L.ptr(masks),
-                                B, S, L.ptr(ws), ws.numel(), L.ptr(mem), L.stream_ptr()), "ortk_encode")
+        pmode = self._packs_mode(self.decode_packs)
+        pkey = self._packs_key() if pmode else None
+        pptr = self._decode_params_ptr(pmode, pkey)
+        packs = C.pointer(self._packs_handle(pmode, L.PACK_W16 if self.precision else 0, pkey)["st"]) if pmode else None
+        L.check(lib.ortk_encode_p(C.byref(self._ccfg), pptr, L.ptr(feats), L.ptr(bxs), L.ptr(masks),
+                                  B, S, L.ptr(ws), ws.numel(), L.ptr(mem), L.stream_ptr(), packs), "ortk_encode")
         return mem
 
     @staticmethod

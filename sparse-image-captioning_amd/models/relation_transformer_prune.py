@@ -59,14 +59,30 @@ class RelationTransformerModel(PruningMixin, _Dense):
     def reset_masks(self):
         for _, m in self.all_pruning_masks():
             m.fill_(self.mask_init_value)
+        self.invalidate_decode_packs()
 
     def _mode(self, train):
         if not self._supermask:
             return 2
         return 1 if train else 0
 
+    def _decode_params_ptr(self, packs_mode, key=None):
+        # With decode_packs = "cached" the mask pass is skipped while `_weff` still holds the eval-mode image of the current weights
+        # and masks (`_weff_eval_key`: the packs key it was computed under; any other _eff_params_ptr call — a train-mode forward
+        # overwrites it with a Bernoulli sample, a decode without packs re-derives it — clears it).  When "cached" has to derive the
+        # image again, the handle is emptied with it: its sections and the fp32 values the executors read always come from ONE image.
+        # "verified" recomputes the image every time: the fingerprint is taken of it.
+        if packs_mode == "cached" and self._weff is not None and getattr(self, "_weff_eval_key", None) == key:
+            return L.ptr(self._weff)
+        ptr = self._eff_params_ptr(False, 0)
+        self._weff_eval_key = key          # (None with packs off: nothing to keep)
+        if packs_mode == "cached" and getattr(self, "_packs", None) is not None:
+            self._packs["st"].have = 0     # a fresh image: the handle is rebuilt from it, never mixed with an older one
+        return ptr
+
     def _eff_params_ptr(self, train, seed):
         lib = L.lib()
+        self._weff_eval_key = None
         if self._weff is None or self._weff.device != self._flat.device:
             self._weff = torch.empty_like(self._flat)
         if self._n_all > self._n_train:

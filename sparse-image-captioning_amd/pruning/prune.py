@@ -178,6 +178,13 @@ class PruningMixin:
         """Bake the masks into the weights in place."""
         for w, m in zip(self.all_pruned_weights(named=False), self._binarised(self.all_pruning_masks(named=False))):
             w.mul_(m)
+        self._weights_changed()
+
+    def _weights_changed(self):
+        """Weights or masks were written: prepared decode weights of an arena model are stale (invalidate_decode_packs)."""
+        hook = getattr(self, "invalidate_decode_packs", None)
+        if hook is not None:
+            hook()
 
     def state_dict_dense(self, destination=None, prefix="", keep_vars=False, discard_pruning_mask=False,
                          prune_weights=True, binarize_supermasks=False):
@@ -251,6 +258,7 @@ class PruningMixin:
             if hook is None:
                 raise ValueError("select='device' needs a model whose weights and masks live in device arenas")
             hook(sparsity_target)
+            self._weights_changed()
             self.sparsity_target = sparsity_target
             self.sparsity_check()
             return True
@@ -263,6 +271,7 @@ class PruningMixin:
         assert len(fresh) == len(masks)
         for m, f in zip(masks, fresh):
             m.data.view(-1).copy_(f.reshape(-1))
+        self._weights_changed()
         self.sparsity_target = sparsity_target
         self.sparsity_check()
         return True

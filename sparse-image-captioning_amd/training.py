@@ -472,6 +472,7 @@ class NativeTrainer:
         else:
             self.load_optimizer_state_dict(other, rate_step=rate_step)
         self.model.load_state_dict(weights, strict=False)
+        self.model.invalidate_decode_packs()
 
     # ------------------------------------------------------------------ steps
     def xe_step(self, data, train=True):
@@ -666,6 +667,7 @@ class NativeTrainer:
 
     def _step(self, data, tok_weight, norm_mask, train, seed=None, encoded=False, rollouts=False, smoothing=0.0):
         m = self.model
+        m.invalidate_decode_packs()        # (the update writes the arenas through raw pointers)
         self.step_count += 1
         self.optim_step += 1
         if not self._grads_clean:
